@@ -2,6 +2,7 @@
 """Headline benchmark: images/sec of RecNeXt-M3 224x224 bf16 with the HIP RecConv2d token mixers.
 
     python bench.py --gpus N --steps K --warmup W            (N > 1: starts its own N ranks, see below)
+    python bench.py ... --dump-outputs DIR                    (also writes the last timed step's logits to DIR, see dump_logits)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Called with --gpus N > 1 and no WORLD_SIZE in the environment, the still GPU-free parent starts N child ranks with
@@ -78,7 +79,28 @@ def parse_args():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="total budget of the cpu_baseline leg")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the logits of the last one to DIR/logits.npy (float32; DIR/logits_rank<r>.npy with --gpus > 1)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all ranks' files together
+
+
+def dump_logits(y, out_dir, rank, world):
+    """The logits of one step as float32 .npy.  Above this rank's share of DUMP_LIMIT_BYTES, a fixed (seed 0) sample of whole rows in
+    batch order, so that two builds run with the same arguments write the same rows."""
+    import numpy as np
+    a = y.float().cpu().numpy()
+    rows_max = max(1, (DUMP_LIMIT_BYTES // world) // max(1, a[0].nbytes))
+    if a.shape[0] > rows_max:
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows_max, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "logits.npy" if world == 1 else f"logits_rank{rank}.npy")
+    np.save(path, np.ascontiguousarray(a))
 
 
 class MixerTimers:
@@ -415,13 +437,15 @@ def main():
         timers.enabled = True
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            net(x)
+            y = net(x)
         torch.cuda.synchronize(device)
         own = time.perf_counter() - t0                        # this rank's K steps, before waiting for the others
         rdist.barrier(r)
         elapsed = rdist.max_over_ranks(r, time.perf_counter() - t0)
         per_rank = [args.batch * args.steps / t for t in rdist.gather_over_ranks(r, own)]
         timers.enabled = False
+    if args.dump_outputs:                                     # outside the timed region
+        dump_logits(y, args.dump_outputs, rank, world)
 
     if rank == 0:
         images = world * args.batch * args.steps

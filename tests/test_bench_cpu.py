@@ -73,3 +73,29 @@ def test_every_mixer_of_the_five_baseline_configs_has_a_traffic_record_in_this_r
         have = {k["kernel"] for k in traffic["kernels"] if k.get("hbm_bytes_per_launch") is not None}
         for ent in line["token_mixers"]["per_kernel"]:
             assert ent["kernel"] in have, (tag, ent["kernel"])
+
+
+def test_dump_outputs_writes_float32_logits_within_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: the last step's logits as float32 .npy, one file per rank; above the 64 MB limit a fixed sample of whole rows, the same from
+    run to run.  --steps sets the number of timed steps and must be positive."""
+    import sys
+    import numpy as np
+    import pytest
+    import torch
+    bench = _load("_rcx_bench_t4", "bench.py")
+    y = torch.randn(8, 1000, generator=torch.Generator().manual_seed(0)).bfloat16()
+    bench.dump_logits(y, str(tmp_path / "one"), 0, 1)
+    got = np.load(tmp_path / "one" / "logits.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 1000 * 4 * 2)            # two ranks, four rows each
+    for d in ("a", "b"):
+        bench.dump_logits(y, str(tmp_path / d), 1, 2)
+    a, b = np.load(tmp_path / "a" / "logits_rank1.npy"), np.load(tmp_path / "b" / "logits_rank1.npy")
+    assert a.shape == (4, 1000) and np.array_equal(a, b)
+    assert all(any(np.array_equal(r, full) for full in y.float().numpy()) for r in a)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--dump-outputs", "out"])
+    args = bench.parse_args()
+    assert args.steps == 7 and args.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
