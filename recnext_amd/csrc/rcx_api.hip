@@ -66,13 +66,10 @@ int check_common(const void* x, const void* y, int N, int C, int H, int W, int k
     return 0;
 }
 
-// Schedule choice: the fused plane kernel whenever it applies; RCX_FORCE_GENERIC=1 pins the
-// one-launch-per-ladder-step schedule (used by tests to cover both, and for A/B timing).
+// RCX_FORCE_GENERIC=1 (rcx::opt::hand_kernels_off) pins the one-launch-per-ladder-step generic schedule: tests cover both with it.
 bool use_plane(int N, int C, int H, int W, int level, int k, int dtype)
 {
-    const char* f = rcx::opt::value(rcx::opt::FORCE_GENERIC);
-    if (f && *f && *f != '0') return false;
-    return rcx::plane_applicable(N, C, H, W, level, k, dtype);
+    return !rcx::opt::hand_kernels_off() && rcx::plane_applicable(N, C, H, W, level, k, dtype);
 }
 
 // Split schedule for a plane whose level-1 plane does not fit the register file (128x128 / level 4): three launches,
@@ -80,12 +77,9 @@ bool use_plane(int N, int C, int H, int W, int level, int k, int dtype)
 //   y = conv_L(x + resize(C_1)) (step kernel).  F_1 and C_1 live in the caller's workspace.
 bool use_split(int N, int C, int H, int W, int level, int k, int dtype)
 {
-    const char* f = rcx::opt::value(rcx::opt::FORCE_GENERIC);
-    if (f && *f && *f != '0') return false;
-    if (level < 1 || k != 5 || H != W || (H & 1)) return false;
-    if (H < 64 && !rcx::opt::value(rcx::opt::FORCE_SPLIT)) return false;   // small planes: the fused LDS-pyramid kernel (or the nested schedule) decides
-    const char* force = rcx::opt::value(rcx::opt::FORCE_SPLIT);                  // A/B knob: three launches even where one fused kernel exists
-    if (rcx::lanes_applicable(N, C, H, W, level, k, dtype) && !(force && *force == '1')) return false;
+    if (rcx::opt::hand_kernels_off() || level < 1 || k != 5 || H != W || (H & 1)) return false;
+    if (H < 64) return false;                            // small planes: the fused LDS-pyramid kernel (or the nested schedule) decides
+    if (rcx::lanes_applicable(N, C, H, W, level, k, dtype)) return false;
     return rcx::down5_lanes_applicable(N, C, H, W, k, 2, dtype, RCX_DTYPE_F32) &&
            rcx::lanes_applicable(N, C, H / 2, W / 2, level - 1, k, RCX_DTYPE_F32) &&
            rcx::upadd_lanes_applicable(N, C, H, W, H / 2, W / 2, k, dtype, RCX_DTYPE_F32, dtype);
@@ -93,27 +87,15 @@ bool use_split(int N, int C, int H, int W, int level, int k, int dtype)
 
 size_t split_bytes(int N, int C, int H, int W) { return 2 * align256(sizeof(float) * (size_t)N * C * (H / 2) * (W / 2)); }
 
-// the register-resident schedule takes precedence where it applies (RCX_LANES=0 switches it off)
+// the register-resident schedule takes precedence where it applies
 bool use_lanes(int N, int C, int H, int W, int level, int k, int dtype)
 {
-    const char* f = rcx::opt::value(rcx::opt::FORCE_GENERIC);
-    if (f && *f && *f != '0') return false;
-    return rcx::lanes_applicable(N, C, H, W, level, k, dtype);
-}
-
-bool lanes_off()
-{
-    const char* f = rcx::opt::value(rcx::opt::FORCE_GENERIC);
-    return f && *f && *f != '0';
+    return !rcx::opt::hand_kernels_off() && rcx::lanes_applicable(N, C, H, W, level, k, dtype);
 }
 
 // one ladder rung / one up-recursion step: the register-resident kernel where it applies, else the generic one
 // RCX_UPADD_CPT=all: the tiled single-step kernels (rcx_upcpt.hip) also where the lanes kernels keep a ragged channel count (tests)
-bool upcpt_everywhere()
-{
-    const char* v = rcx::opt::value(rcx::opt::UPADD_CPT);
-    return v && *v == 'a';
-}
+bool upcpt_everywhere() { return rcx::opt::str(rcx::opt::UPADD_CPT)[0] == 'a'; }
 
 // Which single-step kernel a plane gets.  Never a function of N: a batch and its shards must give the same rows bit for bit.
 enum StepKernel { STEP_GENERIC, STEP_LANES, STEP_CPT, STEP_CPL14, STEP_CONV5_LANES };
@@ -125,7 +107,7 @@ enum StepKernel { STEP_GENERIC, STEP_LANES, STEP_CPT, STEP_CPL14, STEP_CONV5_LAN
 // 12.1 against 16.2, 64 x 64 16.2 / 16.6).
 StepKernel pick_dwconv(int N, int C, int H, int W, int k, int stride, int in_dt, int out_dt)
 {
-    if (lanes_off()) return STEP_GENERIC;
+    if (rcx::opt::hand_kernels_off()) return STEP_GENERIC;
     if (rcx::down5_cpl7_applicable(N, C, H, W, k, stride, in_dt, out_dt)) return STEP_CPL14;          // the 7 x 7 plane, whole (round 4)
     const bool lanes_ok = rcx::down5_lanes_applicable(N, C, H, W, k, stride, in_dt, out_dt);
     if (lanes_ok && !upcpt_everywhere() && !(W % 14 != 0 && C % 64 == 0)) return STEP_LANES;
@@ -142,7 +124,7 @@ StepKernel pick_dwconv(int N, int C, int H, int W, int k, int stride, int in_dt,
 // 64 rows, whose third tile row is mostly empty (32 x 256 x 32 x 32: 20 us against 14; 64 x 64: 31 against 35; 128 x 128: 47 - 52 against 85 - 91).
 StepKernel pick_upadd(int N, int C, int H, int W, int Hc, int Wc, int k, int x_dt, int c_dt, int out_dt, bool has_coarse)
 {
-    if (lanes_off()) return STEP_GENERIC;
+    if (rcx::opt::hand_kernels_off()) return STEP_GENERIC;
     if (!has_coarse) return rcx::conv5_lanes_applicable(N, C, H, W, k, x_dt, out_dt) ? STEP_CONV5_LANES : STEP_GENERIC;
     if (rcx::upadd_cpl14_applicable(N, C, H, W, Hc, Wc, k, x_dt, c_dt, out_dt)) return STEP_CPL14;
     const bool lanes_ok = rcx::upadd_lanes_applicable(N, C, H, W, Hc, Wc, k, x_dt, c_dt, out_dt);
@@ -156,18 +138,27 @@ StepKernel pick_upadd(int N, int C, int H, int W, int Hc, int Wc, int k, int x_d
 //   (lanes / LDS pyramid), or this schedule again -- ; y = conv5(x + resize(C_1)),
 // both outer steps on single-step kernels (rcx_upcpt.hip / the lanes step kernels).  200 x 336 / level 4: five launches (two down, the
 // LDS-pyramid kernel on 50 x 84 / level 2, two up) instead of the generic ladder's nine.  It only ever replaces the generic ladder.
+enum FwdSchedule { FWD_LANES, FWD_SPLIT, FWD_PLANE, FWD_NESTED, FWD_GENERIC };
+FwdSchedule fwd_schedule(int N, int C, int H, int W, int level, int k, int dtype);
+
+// (reached only where no fused schedule applies: fwd_schedule tries them first)
 bool use_nested(int N, int C, int H, int W, int level, int k, int dtype)
 {
-    if (lanes_off() || level < 1 || k != 5 || (H & 1) || (W & 1)) return false;
-    const char* v = rcx::opt::value(rcx::opt::NESTED);
-    if (v && *v == '0') return false;
-    if (use_lanes(N, C, H, W, level, k, dtype) || use_split(N, C, H, W, level, k, dtype) || use_plane(N, C, H, W, level, k, dtype)) return false;
+    if (rcx::opt::hand_kernels_off() || rcx::opt::off(rcx::opt::NESTED) || level < 1 || k != 5 || (H & 1) || (W & 1)) return false;
     const StepKernel d = pick_dwconv(N, C, H, W, k, 2, dtype, RCX_DTYPE_F32);
     const StepKernel u = pick_upadd(N, C, H, W, H / 2, W / 2, k, dtype, RCX_DTYPE_F32, dtype, true);
     if (d == STEP_GENERIC || u == STEP_GENERIC) return false;
-    const int h2 = H / 2, w2 = W / 2;
-    return use_lanes(N, C, h2, w2, level - 1, k, RCX_DTYPE_F32) || use_split(N, C, h2, w2, level - 1, k, RCX_DTYPE_F32) ||
-           use_plane(N, C, h2, w2, level - 1, k, RCX_DTYPE_F32) || use_nested(N, C, h2, w2, level - 1, k, RCX_DTYPE_F32);
+    return fwd_schedule(N, C, H / 2, W / 2, level - 1, k, RCX_DTYPE_F32) != FWD_GENERIC;
+}
+
+// The forward schedule of a RecConv2d block, in order of precedence.  The plan string, the workspace size and the launch all switch on it.
+FwdSchedule fwd_schedule(int N, int C, int H, int W, int level, int k, int dtype)
+{
+    if (use_lanes(N, C, H, W, level, k, dtype)) return FWD_LANES;
+    if (use_split(N, C, H, W, level, k, dtype)) return FWD_SPLIT;
+    if (use_plane(N, C, H, W, level, k, dtype)) return FWD_PLANE;
+    if (use_nested(N, C, H, W, level, k, dtype)) return FWD_NESTED;
+    return FWD_GENERIC;
 }
 
 size_t nested_own_bytes(int N, int C, int H, int W) { return 2 * align256(sizeof(float) * (size_t)N * C * (H / 2) * (W / 2)); }
@@ -198,10 +189,6 @@ hipError_t step_upadd(const void* x, const void* coarse, void* y, const float* w
 
 }  // namespace
 
-#ifdef RCX_STAMPS
-namespace rcx { hipError_t set_stamp_buffer(void* p); namespace lanes { hipError_t set_stamp_buffer(void* p); } }
-#endif
-
 extern "C" {
 
 int rcx_abi_version(void) { return RCX_ABI_VERSION; }
@@ -221,25 +208,21 @@ const char* rcx_recconv2d_fwd_plan(int N, int C, int H, int W, int level, int k,
 {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || level < 0 || level > RCX_MAX_LEVEL || k <= 0 || (k & 1) == 0) return "invalid";
     static thread_local char desc[256];
-    if (!(rcx::opt::value(rcx::opt::FORCE_SPLIT) && use_split(N, C, H, W, level, k, dtype)) && use_lanes(N, C, H, W, level, k, dtype) && rcx::lanes_describe(N, C, H, W, level, k, mode == RCX_MODE_NEAREST ? 1 : 0, dtype, desc, (int)sizeof(desc)) > 0) return desc;
-    if (use_split(N, C, H, W, level, k, dtype)) {
-        char inner[128];
-        rcx::lanes_describe(N, C, H / 2, W / 2, level - 1, k, mode == RCX_MODE_NEAREST ? 1 : 0, RCX_DTYPE_F32, inner, (int)sizeof(inner));
-        const bool dcpt = pick_dwconv(N, C, H, W, k, 2, dtype, RCX_DTYPE_F32) == STEP_CPT;
-        const bool ucpt = pick_upadd(N, C, H, W, H / 2, W / 2, k, dtype, RCX_DTYPE_F32, dtype, true) == STEP_CPT;
-        snprintf(desc, sizeof(desc), "split(%s + %s + %s)", dcpt ? "k_down5_cpt" : "k_down5_lanes", inner, ucpt ? "k_upadd_cpt" : "k_upadd_lanes");
-        return desc;
-    }
-    if (use_nested(N, C, H, W, level, k, dtype)) {
+    const int md = mode == RCX_MODE_NEAREST ? 1 : 0;
+    const FwdSchedule sch = fwd_schedule(N, C, H, W, level, k, dtype);
+    if (sch == FWD_SPLIT || sch == FWD_NESTED) {
         char inner[192];
-        snprintf(inner, sizeof(inner), "%s", rcx_recconv2d_fwd_plan(N, C, H / 2, W / 2, level - 1, k, mode, RCX_DTYPE_F32));   // (overwrites desc)
+        if (sch == FWD_SPLIT) rcx::lanes_describe(N, C, H / 2, W / 2, level - 1, k, md, RCX_DTYPE_F32, inner, (int)sizeof(inner));
+        else snprintf(inner, sizeof(inner), "%s", rcx_recconv2d_fwd_plan(N, C, H / 2, W / 2, level - 1, k, mode, RCX_DTYPE_F32));   // (overwrites desc)
         const bool dcpt = pick_dwconv(N, C, H, W, k, 2, dtype, RCX_DTYPE_F32) == STEP_CPT;
         const bool ucpt = pick_upadd(N, C, H, W, H / 2, W / 2, k, dtype, RCX_DTYPE_F32, dtype, true) == STEP_CPT;
-        snprintf(desc, sizeof(desc), "nested(%s + %s + %s)", dcpt ? "k_down5_cpt" : "k_down5_lanes", inner, ucpt ? "k_upadd_cpt" : "k_upadd_lanes");
+        snprintf(desc, sizeof(desc), "%s(%s + %s + %s)", sch == FWD_SPLIT ? "split" : "nested", dcpt ? "k_down5_cpt" : "k_down5_lanes", inner,
+                 ucpt ? "k_upadd_cpt" : "k_upadd_lanes");
         return desc;
     }
-    if (!use_plane(N, C, H, W, level, k, dtype)) return "generic";
-    if (rcx::plane_describe(N, C, H, W, level, k, dtype, desc, (int)sizeof(desc)) <= 0) return "generic";
+    if (sch == FWD_LANES) rcx::lanes_describe(N, C, H, W, level, k, md, dtype, desc, (int)sizeof(desc));
+    else if (sch == FWD_PLANE) rcx::plane_describe(N, C, H, W, level, k, dtype, desc, (int)sizeof(desc));
+    else return "generic";
     return desc;
 }
 
@@ -290,13 +273,14 @@ int rcx_pack_bias(const void* b, float* dst, int C, int dtype, void* stream)
 size_t rcx_recconv2d_fwd_workspace_bytes(int N, int C, int H, int W, int level, int k, int dtype)
 {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || level < 0 || level > RCX_MAX_LEVEL || k <= 0 || (k & 1) == 0) return 0;
-    if (rcx::opt::value(rcx::opt::FORCE_SPLIT) && use_split(N, C, H, W, level, k, dtype)) return split_bytes(N, C, H, W);
-    if (use_lanes(N, C, H, W, level, k, dtype)) return 0;          // registers only
-    if (use_split(N, C, H, W, level, k, dtype)) return split_bytes(N, C, H, W);
-    if (use_plane(N, C, H, W, level, k, dtype)) return 0;          // the fused schedule keeps every intermediate in LDS
-    if (use_nested(N, C, H, W, level, k, dtype))                    // F_1, C_1, then whatever the inner block needs
+    switch (fwd_schedule(N, C, H, W, level, k, dtype)) {
+    case FWD_LANES: return 0;                                       // registers only
+    case FWD_SPLIT: return split_bytes(N, C, H, W);
+    case FWD_PLANE: return 0;                                       // the fused schedule keeps every intermediate in LDS
+    case FWD_NESTED:                                                // F_1, C_1, then whatever the inner block needs
         return nested_own_bytes(N, C, H, W) + rcx_recconv2d_fwd_workspace_bytes(N, C, H / 2, W / 2, level - 1, k, RCX_DTYPE_F32);
-    return make_ladder(N, C, H, W, level, k).total;
+    default: return make_ladder(N, C, H, W, level, k).total;
+    }
 }
 
 // ---- rcx_time_next_launch: see rcx_launch.h
@@ -342,11 +326,12 @@ static int recconv2d_fwd_impl(const void* x, void* y, const float* wpack, const 
     if (x == y) return fail(RCX_ERR_BAD_ARG, "y must not alias x");
     if (level < 0 || level > RCX_MAX_LEVEL) return fail(RCX_ERR_BAD_ARG, "level %d outside [0,%d]", level, RCX_MAX_LEVEL);
     if (mode != RCX_MODE_BILINEAR && mode != RCX_MODE_NEAREST) return fail(RCX_ERR_BAD_ARG, "unknown mode %d", mode);
-    if (!(rcx::opt::value(rcx::opt::FORCE_SPLIT) && use_split(N, C, H, W, level, k, dtype)) && use_lanes(N, C, H, W, level, k, dtype)) {
+    const FwdSchedule sch = fwd_schedule(N, C, H, W, level, k, dtype);
+    if (sch == FWD_LANES) {
         hipError_t le = rcx::lanes_recconv(x, y, wpack, bpack, N, C, H, W, level, k, mode, dtype, (hipStream_t)stream);
         return le == hipSuccess ? 0 : hip_fail(le, "lanes schedule");
     }
-    if (use_split(N, C, H, W, level, k, dtype)) {
+    if (sch == FWD_SPLIT) {
         const size_t need = split_bytes(N, C, H, W);
         if (!workspace || workspace_bytes < need)
             return fail(RCX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
@@ -362,11 +347,11 @@ static int recconv2d_fwd_impl(const void* x, void* y, const float* wpack, const 
                        N, C, H, W, H / 2, W / 2, k, mode, dtype, RCX_DTYPE_F32, dtype, s);
         return e == hipSuccess ? 0 : hip_fail(e, "split schedule: final conv");
     }
-    if (use_plane(N, C, H, W, level, k, dtype)) {
+    if (sch == FWD_PLANE) {
         hipError_t pe = rcx::plane_recconv(x, y, wpack, bpack, N, C, H, W, level, k, mode, dtype, (hipStream_t)stream);
         return pe == hipSuccess ? 0 : hip_fail(pe, "plane schedule");
     }
-    if (use_nested(N, C, H, W, level, k, dtype)) {
+    if (sch == FWD_NESTED) {
         const size_t own = nested_own_bytes(N, C, H, W);
         const size_t need = own + rcx_recconv2d_fwd_workspace_bytes(N, C, H / 2, W / 2, level - 1, k, RCX_DTYPE_F32);
         if (!workspace || workspace_bytes < need)
@@ -487,8 +472,7 @@ int rcx_recconv2d_fwd_train(const void* x, void* y, const float* wpack, const fl
     // the blocks of RecNeXt at 224x224 (channel-per-lane kernels): the inference kernel itself leaves the pyramid behind --
     // one launch instead of 2 * level + 1 (RCX_TRAIN_FUSED=0: the per-step schedule, for A/B runs)
     {
-        const char* tf = rcx::opt::value(rcx::opt::TRAIN_FUSED);
-        const bool fused_ok = !(tf && *tf == '0') && !lanes_off() && !(rcx::opt::value(rcx::opt::FORCE_SPLIT));
+        const bool fused_ok = !rcx::opt::off(rcx::opt::TRAIN_FUSED) && !rcx::opt::hand_kernels_off();
         const int md = mode == RCX_MODE_NEAREST ? 1 : 0;
         if (fused_ok && rcx::cpt_train_applicable(N, C, H, W, level, k, md, dtype)) {
             hipError_t fe = rcx::cpt_recconv(x, y, wpack, bpack, N, C, H, level, md, dtype, s, (float*)saved, L.f_off, L.c_off);
@@ -526,16 +510,23 @@ int rcx_recconv2d_fwd_train(const void* x, void* y, const float* wpack, const fl
     return e == hipSuccess ? 0 : hip_fail(e, "train fwd: final conv");
 }
 
-// the fine levels above a 14 x 14 / level 2 tail run on the tiled adjoint kernels (rcx_cptbwd.hip) when every one of their planes is 56 x 56 or 28 x 28:
-// the number of such levels (2: the 56 x 56 / level 4 block, 1: 28 x 28 / level 3), 0 = the per-step schedule
-static int bwd_cpt_levels(const TrainLadder& L, int N, int C, int level, int k, int dtype)
+// A block deeper than level 2 whose level (level - 2) plane is 14x14 -- the 28x28 / level 3 and 56x56 / level 4 blocks of RecNeXt at 224x224 --
+// ends in exactly the 14x14 / level 2 block (input F_m, output C_m, convs[0..2], the shared down conv), whose whole backward is one fused launch:
+// m = level - 2, or 0 where there is no such tail
+static int bwd_tail14(const TrainLadder& L, int N, int C, int level, int k)
 {
-    if (level < 3 || lanes_off() || rcx::opt::is_zero(rcx::opt::BWD_FUSED) || rcx::opt::is_zero(rcx::opt::BWD_NESTED)) return 0;
+    if (level < 3) return 0;
     const int m = level - 2;
-    if (L.h[m] != 14 || L.w[m] != 14 || !rcx::cplbwd_applicable(N, C, 14, 14, 2, k, RCX_DTYPE_F32)) return 0;
+    return L.h[m] == 14 && L.w[m] == 14 && !rcx::opt::hand_kernels_off() && rcx::cplbwd_applicable(N, C, 14, 14, 2, k, RCX_DTYPE_F32) ? m : 0;
+}
+
+// the fine levels above the 14 x 14 tail run on the tiled adjoint kernels (rcx_cptbwd.hip) when every one of their planes is 56 x 56 or 28 x 28:
+// the number of such levels (2: the 56 x 56 / level 4 block, 1: 28 x 28 / level 3), 0 = the per-step schedule
+static int bwd_cpt_levels(const TrainLadder& L, int N, int C, int level, int k)
+{
+    const int m = bwd_tail14(L, N, C, level, k);
     for (int l = 0; l < m; ++l)
         if (!rcx::bwd_cpt_applicable(N, C, L.h[l], L.w[l], k) || L.h[l + 1] * 2 != L.h[l] || L.w[l + 1] * 2 != L.w[l]) return 0;
-    (void)dtype;
     return m;
 }
 
@@ -544,8 +535,8 @@ int rcx_recconv2d_bwd_gy_dtype(int N, int C, int H, int W, int level, int k, int
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || level < 0 || level > RCX_MAX_LEVEL || k <= 0 || (k & 1) == 0 || !known_dtype(dtype)) return RCX_DTYPE_F32;
     // bfloat16 only: with float16 rows on both sides the tiled weight-gradient kernel does not fit its register budget (rcx_cptbwd_kernels.h)
     if (dtype != RCX_DTYPE_BF16 || C % 4) return RCX_DTYPE_F32;
-    if (level >= 1 && !lanes_off() && rcx::cplbwd_applicable(N, C, H, W, level, k, dtype)) return dtype;      // the one-launch 14 x 14 / 7 x 7 backward
-    return bwd_cpt_levels(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype) > 0 ? dtype : RCX_DTYPE_F32;
+    if (level >= 1 && !rcx::opt::hand_kernels_off() && rcx::cplbwd_applicable(N, C, H, W, level, k, dtype)) return dtype;      // the one-launch 14 x 14 / 7 x 7 backward
+    return bwd_cpt_levels(make_train_ladder(N, C, H, W, level, k), N, C, level, k) > 0 ? dtype : RCX_DTYPE_F32;
 }
 
 int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* wpack, const float* wpack_flipped, const void* saved,
@@ -563,8 +554,8 @@ int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* 
     if (level >= 1 && !saved) return fail(RCX_ERR_BAD_ARG, "null saved-activation buffer");
     if (!workspace || workspace_bytes < L.bwd_total)
         return fail(RCX_ERR_WORKSPACE, "backward workspace too small: need %zu bytes, got %zu", L.bwd_total, workspace_bytes);
-    const int mcpt = bwd_cpt_levels(L, N, C, level, k, dtype);
-    const bool whole = level >= 1 && !lanes_off() && rcx::cplbwd_applicable(N, C, H, W, level, k, dtype);
+    const int mcpt = bwd_cpt_levels(L, N, C, level, k);
+    const bool whole = level >= 1 && !rcx::opt::hand_kernels_off() && rcx::cplbwd_applicable(N, C, H, W, level, k, dtype);
     if (gy_dtype != RCX_DTYPE_F32 && !((mcpt > 0 || whole) && gy_dtype == dtype && dtype == RCX_DTYPE_BF16))
         return fail(RCX_ERR_UNSUPPORTED, "gy of dtype %d: this problem takes float32 (rcx_recconv2d_bwd_gy_dtype)", gy_dtype);
     if (gw_out)
@@ -653,15 +644,8 @@ int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* 
     RCX_TRY(rcx::bwd_wgrad(x, dtype, level >= 1 ? C_(1) : nullptr, gyf, PART(slot), GW(1 + level), GB(1 + level), N, C, H, W,
                            level >= 1 ? L.h[1] : 0, level >= 1 ? L.w[1] : 0, H, W, k, 1, mode, 0, s, &rows), "bwd: final conv weight grad");
     add_slot(1 + level, PART(slot++), rows);
-    // A deeper block whose level (level - 2) plane is 14x14 -- the 28x28 / level 3 and 56x56 / level 4 blocks of RecNeXt at 224x224 --
-    // ends in exactly the 14x14 / level 2 block (input F_m, output C_m, convs[0..2], the shared down conv): its whole backward is
-    // the one fused launch, the levels above it keep the per-step kernels.
-    int m = 0;
-    if (level >= 3 && !lanes_off() && L.h[level - 2] == 14 && L.w[level - 2] == 14 &&
-        rcx::cplbwd_applicable(N, C, 14, 14, 2, k, RCX_DTYPE_F32)) {
-        const char* nv = rcx::opt::value(rcx::opt::BWD_NESTED);
-        if (!(nv && *nv == '0')) m = level - 2;
-    }
+    // the 14x14 / level 2 tail (bwd_tail14) as its one launch, the levels above it on the per-step kernels
+    const int m = bwd_tail14(L, N, C, level, k);
     // up recursion (:31-33), finest level first in the backward direction
     for (int l = 1; l <= level; ++l) {
         const int j = level - l;
@@ -725,8 +709,8 @@ int rcx_dwconv2d_mult2_fwd(const void* x, void* y, const float* w_kkc, const flo
     // (32 x 64 x 128 x 128: 55 us against 164; 64 x 64 x 112 x 112: 61 against 246), on 14 x 14 (20.6 against 25.9) and on everything the
     // lanes kernel has no plan for (float16; COCO stages 200 x 336: 17 us against the generic kernel's 62).  Never a function of N.
     hipError_t e;
-    const bool lanes_ok = !lanes_off() && rcx::down_lanes_applicable(N, Cin, H, W, k, stride, dtype);
-    const bool tiled_ok = !lanes_off() && rcx::down7m2_cpt_applicable(N, Cin, H, W, k, stride, dtype);
+    const bool lanes_ok = !rcx::opt::hand_kernels_off() && rcx::down_lanes_applicable(N, Cin, H, W, k, stride, dtype);
+    const bool tiled_ok = !rcx::opt::hand_kernels_off() && rcx::down7m2_cpt_applicable(N, Cin, H, W, k, stride, dtype);
     if (tiled_ok && (!lanes_ok || H > 64 || W > 64 || (H <= 14 && W <= 14) || upcpt_everywhere()))
         e = rcx::down7m2_cpt(x, y, w_kkc, bias, N, Cin, H, W, dtype, (hipStream_t)stream);
     else if (lanes_ok)
@@ -789,13 +773,13 @@ int rcx_dwconv2d_bwd(const void* x, const float* gy, const float* w_kkc, const f
     hipError_t e;
     if (gx) {
         // the stride-2 conv5 on the 56 x 56 / 28 x 28 planes (RecAttn2d's `down` conv): the tiled adjoint kernels of rcx_recconv2d_bwd (round 6)
-        const bool tiled = stride == 2 && !lanes_off() && rcx::bwd_cpt_applicable(N, C, H, W, k) && Ho * 2 == H && Wo * 2 == W;
+        const bool tiled = stride == 2 && !rcx::opt::hand_kernels_off() && rcx::bwd_cpt_applicable(N, C, H, W, k) && Ho * 2 == H && Wo * 2 == W;
         if (stride == 1) e = step_dwconv(gy, gx, w_flipped_kkc, nullptr, N, C, H, W, k, 1, RCX_DTYPE_F32, x_dtype, s);
         else if (tiled) e = rcx::bwd_dT_cpt(gy, gx, x_dtype, w_kkc, N, C, H, s);
         else e = rcx::bwd_down_input(nullptr, gy, gx, x_dtype, w_kkc, N, C, H, W, Ho, Wo, k, s);
         if (e != hipSuccess) return hip_fail(e, "rcx_dwconv2d_bwd: input gradient");
     }
-    if (stride == 2 && !lanes_off() && rcx::bwd_cpt_applicable(N, C, H, W, k) && Ho * 2 == H && Wo * 2 == W && N * (H / 14) <= 512) {      // 512 partial rows: the workspace above
+    if (stride == 2 && !rcx::opt::hand_kernels_off() && rcx::bwd_cpt_applicable(N, C, H, W, k) && Ho * 2 == H && Wo * 2 == W && N * (H / 14) <= 512) {      // 512 partial rows: the workspace above
         int rows = 0;
         e = rcx::bwd_wgrad_d_cpt(x, x_dtype, gy, (float*)workspace, N, C, H, s, &rows);
         if (e == hipSuccess) {
@@ -813,7 +797,7 @@ int rcx_dwconv2d_bwd(const void* x, const float* gy, const float* w_kkc, const f
 // ---- backward of conv(x + resize(coarse)) (RecAttn2d's last line in a training step) ----
 static bool upadd_bwd_tiled(int N, int C, int H, int W, int Hc, int Wc, int k)
 {
-    return !lanes_off() && rcx::bwd_cpt_applicable(N, C, H, W, k) && Hc * 2 == H && Wc * 2 == W;
+    return !rcx::opt::hand_kernels_off() && rcx::bwd_cpt_applicable(N, C, H, W, k) && Hc * 2 == H && Wc * 2 == W;
 }
 
 size_t rcx_upadd_dwconv_bwd_workspace_bytes(int N, int C, int H, int W, int Hc, int Wc, int k)
@@ -1053,10 +1037,5 @@ int rcx_linear_attention_bwd(const void* qpre, const void* kpre, const void* v, 
     hipError_t e = rcx::linattn_core_bwd(qpre, kpre, v, gout, gq, gk, gv, B, n, C, heads, dtype, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_linear_attention_bwd");
 }
-
-#ifdef RCX_STAMPS
-/* diagnostic build only: not part of include/recnext_amd.h */
-int rcx_debug_set_stamp_buffer(void* p) { int e = (int)rcx::set_stamp_buffer(p); return e ? e : (int)rcx::lanes::set_stamp_buffer(p); }
-#endif
 
 }  // extern "C"

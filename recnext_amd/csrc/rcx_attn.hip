@@ -11,7 +11,6 @@
 // Layout: all five tensors are (B, n, C) = NHWC; head h owns channels [h*D, (h+1)*D), D = C / heads.  G = 4 output columns per
 // thread when D % 4 == 0 (D <= 64), else G = 1 (D <= 32).
 #include <stdlib.h>
-#include "rcx_opts.h"
 
 #include "rcx_common.h"
 #include "rcx_launch.h"
@@ -359,10 +358,7 @@ template <> struct Mf<f16_t> {
     static __device__ __forceinline__ f32x16 mma(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
 
-#ifndef RCX_LM_NW
-#define RCX_LM_NW 4
-#endif
-constexpr int LM_NW = RCX_LM_NW;    // waves per (image, head): the tokens are dealt over them (phase 1 partial sums meet in LDS)
+constexpr int LM_NW = 4;    // waves per (image, head): the tokens are dealt over them (phase 1 partial sums meet in LDS)
 
 template <typename T>
 __global__ void __launch_bounds__(LM_NW * 64)
@@ -898,13 +894,10 @@ hipError_t linattn_core_bwd(const void* qpre, const void* kpre, const void* v, c
                             int B, int n, int C, int heads, int dtype, hipStream_t s)
 {
     const dim3 grid((unsigned)(B * heads)), block(LA_NT);
-    {
-        const char* m = rcx::opt::value(rcx::opt::ATTN_MFMA);                     // A/B knob: 0 = the vector-pipe kernel
-        if (C / heads == 32 && dtype != 0 && !(m && *m == '0')) {
-            if (dtype == 1) hipLaunchKernelGGL((k_linattn_bwd_mfma<bf16_t>), grid, dim3(LM_NW * 64), 0, s, (const bf16_t*)qpre, (const bf16_t*)kpre, (const bf16_t*)v, (const bf16_t*)gout, (bf16_t*)gq, (bf16_t*)gk, (bf16_t*)gv, n, C, heads);
-            else hipLaunchKernelGGL((k_linattn_bwd_mfma<f16_t>), grid, dim3(LM_NW * 64), 0, s, (const f16_t*)qpre, (const f16_t*)kpre, (const f16_t*)v, (const f16_t*)gout, (f16_t*)gq, (f16_t*)gk, (f16_t*)gv, n, C, heads);
-            return hipGetLastError();
-        }
+    if (C / heads == 32 && dtype != 0) {
+        if (dtype == 1) hipLaunchKernelGGL((k_linattn_bwd_mfma<bf16_t>), grid, dim3(LM_NW * 64), 0, s, (const bf16_t*)qpre, (const bf16_t*)kpre, (const bf16_t*)v, (const bf16_t*)gout, (bf16_t*)gq, (bf16_t*)gk, (bf16_t*)gv, n, C, heads);
+        else hipLaunchKernelGGL((k_linattn_bwd_mfma<f16_t>), grid, dim3(LM_NW * 64), 0, s, (const f16_t*)qpre, (const f16_t*)kpre, (const f16_t*)v, (const f16_t*)gout, (f16_t*)gq, (f16_t*)gk, (f16_t*)gv, n, C, heads);
+        return hipGetLastError();
     }
 #define RCX_LAB(T) hipLaunchKernelGGL((k_linattn_bwd<T>), grid, block, 0, s, (const T*)qpre, (const T*)kpre, (const T*)v, (const T*)gout, \
                                       (T*)gq, (T*)gk, (T*)gv, n, C, heads)
@@ -920,17 +913,9 @@ hipError_t linattn_core_bwd(const void* qpre, const void* kpre, const void* v, c
 // ... and only the vector-pipe kernel gains from it: on the matrix-core kernel (head dimension 32, 16-bit I/O, >= 512 tokens) a lane owns ONE
 // channel of 16 tokens, its nine taps are scalar loads, and the unit of RecNeXt-A3's stage 0 went from 239 to 394 us; the shorter
 // sequences (vector-pipe kernel, four channels per thread) went 80.4 -> 74.2 us (49 tokens x 256 channels), 118 -> 116.5, 99 -> 97.5.
-static bool linattn_uses_mfma(int n, int C, int heads, int dtype)
-{
-    const char* m = rcx::opt::value(rcx::opt::ATTN_MFMA);
-    return C / heads == 32 && dtype != 0 && n >= 512 && !(m && *m == '0');
-}
+static bool linattn_uses_mfma(int n, int C, int heads, int dtype) { return C / heads == 32 && dtype != 0 && n >= 512; }
 
-bool linattn_core_fuses_pe(int n, int C, int heads, int dtype)
-{
-    const char* old = rcx::opt::value(rcx::opt::ATTN_SCALAR);
-    return ((C / heads) % 4) == 0 && !(old && *old == '1') && !linattn_uses_mfma(n, C, heads, dtype);
-}
+bool linattn_core_fuses_pe(int n, int C, int heads, int dtype) { return ((C / heads) % 4) == 0 && !linattn_uses_mfma(n, C, heads, dtype); }
 
 hipError_t linattn_core(const void* qpre, const void* kpre, const void* v, const void* pe, void* out,
                         int B, int n, int C, int heads, int dtype, hipStream_t s, const float* pew, const float* peb, int Wp)
@@ -939,33 +924,27 @@ hipError_t linattn_core(const void* qpre, const void* kpre, const void* v, const
     const bool wide = ((C / heads) % 4) == 0;
     const PeConv pc{pew, peb, Wp > 0 ? Wp : 1};
     if (pew && !linattn_core_fuses_pe(n, C, heads, dtype)) return hipErrorInvalidConfiguration;
-    {
-        const char* m = rcx::opt::value(rcx::opt::ATTN_MFMA);                     // A/B knob: 0 = the vector-pipe kernels for every head dimension
-        // Measured (batch 256, bf16): 784 tokens 88 -> 61 us with 4 waves per head; 196 / 49 / 16 tokens no faster than the vector-pipe kernel
-        // (36 / 23 / 31 against 36 / 20 / 20 us: too few tokens per head to amortise the partial-sum exchange) -- so only the long sequences
-        (void)m;
-        if (linattn_uses_mfma(n, C, heads, dtype)) {
-            if (dtype == 1) hipLaunchKernelGGL((k_linattn_mfma<bf16_t>), grid, dim3(LM_NW * 64), 0, s, (const bf16_t*)qpre, (const bf16_t*)kpre, (const bf16_t*)v, (const bf16_t*)pe, (bf16_t*)out, n, C, heads, pc);
-            else hipLaunchKernelGGL((k_linattn_mfma<f16_t>), grid, dim3(LM_NW * 64), 0, s, (const f16_t*)qpre, (const f16_t*)kpre, (const f16_t*)v, (const f16_t*)pe, (f16_t*)out, n, C, heads, pc);
-            return hipGetLastError();
-        }
+    // Measured (batch 256, bf16): 784 tokens 88 -> 61 us with 4 waves per head; 196 / 49 / 16 tokens no faster than the vector-pipe kernel
+    // (36 / 23 / 31 against 36 / 20 / 20 us: too few tokens per head to amortise the partial-sum exchange) -- so only the long sequences
+    if (linattn_uses_mfma(n, C, heads, dtype)) {
+        if (dtype == 1) hipLaunchKernelGGL((k_linattn_mfma<bf16_t>), grid, dim3(LM_NW * 64), 0, s, (const bf16_t*)qpre, (const bf16_t*)kpre, (const bf16_t*)v, (const bf16_t*)pe, (bf16_t*)out, n, C, heads, pc);
+        else hipLaunchKernelGGL((k_linattn_mfma<f16_t>), grid, dim3(LM_NW * 64), 0, s, (const f16_t*)qpre, (const f16_t*)kpre, (const f16_t*)v, (const f16_t*)pe, (f16_t*)out, n, C, heads, pc);
+        return hipGetLastError();
     }
-#define RCX_LA_LAUNCH(T, G) hipLaunchKernelGGL((k_linattn_core<T, G>), grid, block, 0, s, (const T*)qpre, (const T*)kpre, (const T*)v, \
-                                               (const T*)pe, (T*)out, n, C, heads)
-    const char* old = rcx::opt::value(rcx::opt::ATTN_SCALAR);                 // A/B knob: the untiled kernel for every head dimension
-    const bool tiled = wide && !(old && *old == '1');
-    if (tiled) {
+    if (wide) {
 #define RCX_LA4(T, DM) hipLaunchKernelGGL((k_linattn_core4<T, DM>), grid, block, 0, s, (const T*)qpre, (const T*)kpre, (const T*)v, (const T*)pe, (T*)out, n, C, heads, pc)
         const bool small = C / heads <= 32;
         if (dtype == 1) { if (small) RCX_LA4(bf16_t, 32); else RCX_LA4(bf16_t, 64); }
         else if (dtype == 2) { if (small) RCX_LA4(f16_t, 32); else RCX_LA4(f16_t, 64); }
         else { if (small) RCX_LA4(float, 32); else RCX_LA4(float, 64); }
 #undef RCX_LA4
+        return hipGetLastError();
     }
-    else if (dtype == 1) { if (wide) RCX_LA_LAUNCH(bf16_t, 4); else RCX_LA_LAUNCH(bf16_t, 1); }
-    else if (dtype == 2) { if (wide) RCX_LA_LAUNCH(f16_t, 4); else RCX_LA_LAUNCH(f16_t, 1); }
-    else { if (wide) RCX_LA_LAUNCH(float, 4); else RCX_LA_LAUNCH(float, 1); }
-#undef RCX_LA_LAUNCH
+#define RCX_LA1(T) hipLaunchKernelGGL((k_linattn_core<T, 1>), grid, block, 0, s, (const T*)qpre, (const T*)kpre, (const T*)v, (const T*)pe, (T*)out, n, C, heads)
+    if (dtype == 1) RCX_LA1(bf16_t);
+    else if (dtype == 2) RCX_LA1(f16_t);
+    else RCX_LA1(float);
+#undef RCX_LA1
     return hipGetLastError();
 }
 

@@ -381,10 +381,9 @@ template <int MODE, int CT, typename TIO, typename TGY = float>
 static hipError_t launch14(const BwdArgs& A, hipStream_t s)
 {
     const unsigned planes = (unsigned)(A.N * ((A.C + 63) / 64));
-    const char* v = rcx::opt::value(rcx::opt::BWD_SPLIT);                                // A/B switch: 0 = one wave per plane always
     // two waves per plane while that still fits the chip's 1024 SIMDs in one round (and the split grid keeps whole XCD rounds)
     BwdArgs B = A;
-    B.split = !(v && *v == '0') && planes * 2 <= 1024 && planes % 8 == 0;
+    B.split = planes * 2 <= 1024 && planes % 8 == 0;
     hipLaunchKernelGGL((k_recconv_bwd_cpl14<MODE, CT, TIO, TGY>), dim3(B.split ? planes * 2 : planes), dim3(64), 0, s, B);
     return hipGetLastError();
 }
@@ -414,9 +413,7 @@ static hipError_t launch7_c(const BwdArgs& A, hipStream_t s)
 // the fused backward applies where the fused training forward does, and needs one partial row per image in a 512-row slot
 bool cplbwd_applicable(int N, int C, int H, int W, int level, int k, int dtype)
 {
-    const char* v = rcx::opt::value(rcx::opt::BWD_FUSED);
-    if (v && *v == '0') return false;
-    if (N > 512) return false;
+    if (rcx::opt::off(rcx::opt::BWD_FUSED) || rcx::opt::hand_kernels_off() || N > 512) return false;
     return cpl7b_applicable(N, C, H, W, level, k, dtype) || cpl14_applicable(N, C, H, W, level, k, dtype);
 }
 

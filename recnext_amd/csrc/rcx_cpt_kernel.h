@@ -41,58 +41,11 @@ using lanes::vtab;
 using lanes::VT;
 
 #define CPT_FENCE __builtin_amdgcn_sched_barrier(0)
-#ifndef RCX_CPT_AHEAD1
-#define RCX_CPT_AHEAD1 3                   /* rows of x in flight in front of the row being used, pass 1 / pass 2 (tools/cpt_one.hip sweeps them) */
-#endif
-#ifndef RCX_CPT_AHEAD2
-#define RCX_CPT_AHEAD2 2
-#endif
-#ifndef RCX_CPT_STAGGER
-#define RCX_CPT_STAGGER 0                  /* A/B (tools/cpt_one.hip): the second half of a workgroup's waves -- the SIMD partners of the first half -- sleep
-                                              64 x this many cycles behind the barrier in front of each streaming pass, so that partners do not burst their
-                                              loads and their FMAs in lockstep (MI355X_MICROARCH.md, two waves per SIMD, item 9) */
-#endif
-#ifndef RCX_CPT_PRIO
-#define RCX_CPT_PRIO 0                     /* A/B: s_setprio 1 for the second half of the waves (the arbitration losers by age; ibid. item 4) */
-#endif
-#ifndef RCX_CPT16_ALIAS
-#define RCX_CPT16_ALIAS 0                  /* A/B: 16-pixel tiles with the small planes aliased into the level-1 plane (two workgroups per CU); see Geo::ALIAS */
-#endif
-#ifndef RCX_CPT_STG_P2
-#define RCX_CPT_STG_P2 0                   /* staged x rows (STG, diagnostic build) in pass 2 as well as in pass 1 (round 5 measured pass 1 alone: no gain either) */
-#endif
-#ifndef RCX_CPT_SKIPW
-#define RCX_CPT_SKIPW 1                    /* piece rounds of the 7- and 4-wide planes: waves none of whose tile-lanes has a row skip the round (uniform branch) */
-#endif
-#ifndef RCX_CPT_ENDBAR
-#define RCX_CPT_ENDBAR 1                   /* A/B: the barrier at the end of a unit.  The barrier behind the next unit's tap loads already orders this unit's last reads of C1
-                                              (pass 2) before the next unit's first writes of F1 (pass 1); measured equal either way (profiles/r05_cpt_unit_timeline.txt) */
-#endif
-#ifndef RCX_CPT_PF
-#define RCX_CPT_PF 0                       /* wide-load L2 prefetch ahead of pass 1: measured slower, see pass 1 */
-#endif
-
-// diagnostic build only (-DRCX_STAMPS, tools/cpt_one.hip): lane 0 of every wave of the first workgroups writes the clock at the phase boundaries of
-// its first four units (`it` = the unit loop's counter)
-#ifdef RCX_STAMPS
-static __device__ unsigned long long* g_cpt_stamps = nullptr;
-#define CPT_STAMP(id)                                                                                                    \
-    do {                                                                                                                 \
-        if ((threadIdx.x & 63) == 0 && g_cpt_stamps && blockIdx.x < 512)                                                 \
-            g_cpt_stamps[((blockIdx.x * 8 + (threadIdx.x >> 6)) * 4 + (it < 3 ? it : 3)) * 16 + (id)] = __builtin_readcyclecounter();             \
-    } while (0)
-#define CPT_STAMP_RT(id)                                                                                                 \
-    do {                                                                                                                 \
-        if ((threadIdx.x & 63) == 0 && g_cpt_stamps && blockIdx.x < 512)                                                 \
-            g_cpt_stamps[((blockIdx.x * 8 + (threadIdx.x >> 6)) * 4 + (it < 3 ? it : 3)) * 16 + (id)] = __builtin_amdgcn_s_memrealtime();         \
-    } while (0)
-#else
-#define CPT_STAMP(id) do { } while (0)
-#define CPT_STAMP_RT(id) do { } while (0)
-#endif
+// rows of x in flight in front of the row being used, pass 1 / pass 2
+constexpr int AHEAD_P1 = 3;
+constexpr int AHEAD_P2 = 2;
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4pf __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) char* gcptr;
 typedef __attribute__((address_space(1))) char* gptr;
 
@@ -389,81 +342,17 @@ template <typename TIO> __device__ __forceinline__ uint32_t pk16(float lo, float
     else return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, bf16x2_t));
 }
 
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-// ---- staged x rows (STG, round 4).  What bounds the passes is the NUMBER of vector-memory wave-instructions: a load costs the CU ~7.3 cycles
-// (8.7 at 8 waves per CU) whatever its width up to 4 bytes per lane, 15.8 at 16 bytes (tools/ubench/vmem_rate.hip, profiles/archive/r04_vmem_rate.txt);
-// eighteen 2-byte loads per row and lane are 157 cycles of the CU's one texture-address path, three 16-byte LDS-DMA pieces are ~48, and the
-// row no longer waits in registers.  A row = the wave's 2 x 18 x 64-byte image (Geo::SLOTB) in LDS order = piece order: piece j, lane i =
-// 16-byte chunk 64 j + i; the source address is per lane (an out-of-range offset writes zeros: the padding left and right of the image;
-// probed: tools/ubench/ldsdma_probe.hip).  M0 = the LDS byte address of the piece; it is written and restored inside the statement (the
-// compiler owns M0), one wait state between an SALU write of M0 and the instruction that reads it, SCC declared.
-__device__ __forceinline__ void stage_row(unsigned v0, unsigned v1, unsigned v2, i32x4 rs, int rb, int ldsaddr)
-{
-    int t, keep;
-    unsigned long long ex;
-    asm volatile("s_add_i32 %[t], %[rb], 0\n\t"
-                 "s_mov_b32 %[keep], m0\n\t"
-                 "s_add_i32 m0, %[la], 0\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %[v0], %[rs], %[t] offen lds\n\t"
-                 "s_add_i32 m0, %[la], 1024\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %[v1], %[rs], %[t] offen lds\n\t"
-                 "s_add_i32 m0, %[la], 2048\n\t"
-                 "s_mov_b64 %[ex], exec\n\ts_mov_b64 exec, 0xffff\n\t"
-                 "buffer_load_dwordx4 %[v2], %[rs], %[t] offen lds\n\t"
-                 "s_mov_b64 exec, %[ex]\n\t"
-                 "s_mov_b32 m0, %[keep]"
-                 : [t] "=&s"(t), [keep] "=&s"(keep), [ex] "=&s"(ex)
-                 : [v0] "v"(v0), [v1] "v"(v1), [v2] "v"(v2), [rs] "s"(rs), [rb] "s"(rb), [la] "s"(ldsaddr)
-                 : "scc", "memory");
-}
-// The row back as 18 float32-position (bf16) / zero-extended (float16) elements of this lane's channel, exactly what row_load leaves: wait
-// until at most PENDING younger memory operations are outstanding, five transposing reads (four pixels of the lane's channel each: lane
-// 16 g + 4 q + p supplies the address of pixel 4 m + q, 8-byte chunk p of the group's 16 channels; lane 16 g + i receives channel i), their
-// wait, and one shift or mask per element.  Loads and waits in ONE statement: no register is in flight outside it.
-template <typename TIO, int PENDING, int OFF>
-__device__ __forceinline__ void fetch_row(uint32_t (&raw)[18], unsigned addr)
-{
-    u32x2 d0, d1, d2, d3, d4;
-    asm volatile("s_waitcnt vmcnt(%[n])\n\t"
-                 "ds_read_b64_tr_b16 %[d0], %[a] offset:%[o]\n\t"
-                 "ds_read_b64_tr_b16 %[d1], %[a] offset:%[o]+256\n\t"
-                 "ds_read_b64_tr_b16 %[d2], %[a] offset:%[o]+512\n\t"
-                 "ds_read_b64_tr_b16 %[d3], %[a] offset:%[o]+768\n\t"
-                 "ds_read_b64_tr_b16 %[d4], %[a] offset:%[o]+1024\n\t"
-                 "s_waitcnt lgkmcnt(0)"
-                 : [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [d3] "=&v"(d3), [d4] "=&v"(d4)
-                 : [a] "v"(addr), [n] "n"(PENDING), [o] "n"(OFF) : "memory");
-    const u32x2 d[5] = {d0, d1, d2, d3, d4};
-#pragma unroll
-    for (int m = 0; m < 5; ++m)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (4 * m + e >= 18) continue;
-            const uint32_t v = (e >> 1) ? d[m].y : d[m].x;
-            if constexpr (std::is_same<TIO, f16_t>::value) raw[4 * m + e] = (e & 1) ? (v >> 16) : (v & 0xffffu);
-            else raw[4 * m + e] = (e & 1) ? (v & 0xffff0000u) : (v << 16);
-        }
-}
-
 // XCD-aware workgroup order of the tile kernels (rcx_upcpt.hip, rcx_cptbwd_kernels.h).  Workgroups are dealt round-robin over the 8 XCDs, each with its own
 // L2: with the natural order the tiles of one (image, channel block) plane -- which read each other's halo rows and columns -- land on eight different L2s
 // and every halo row comes from HBM once per tile row (k_upadd_cpt at 32 x 64 x 128 x 128: 1.44 x its bytes).  Remapped, XCD x walks planes x, x + 8, ...
 // tile by tile: neighbours in space are neighbours in time on one L2.  b = blockIdx.x, G = workgroups per plane, NP = planes; planes past the last multiple
-// of 8 keep the natural order.  (RCX_UPCPT_XCD=0 at build time: natural order, for A/B runs.)
-#ifndef RCX_UPCPT_XCD
-#define RCX_UPCPT_XCD 1
-#endif
+// of 8 keep the natural order.
 __device__ __forceinline__ unsigned xcd_workgroup(unsigned b, unsigned G, unsigned NP)
 {
-#if RCX_UPCPT_XCD
     const unsigned npf = NP & ~7u;
     if (b >= npf * G) return b;
     const unsigned x = b & 7u, slot = b >> 3;
     return (x + 8u * (slot / G)) * G + slot % G;
-#else
-    return b;
-#endif
 }
 
 // the 25 taps of one conv for this lane's channel as three register pairs per tap row: (w0,w1) (w2,w3) (w4,0)
@@ -605,11 +494,11 @@ constexpr Rel rel2(int mode, int par, int c)
 // (56 x 56 / level 3, 28 x 28 / level 2: the same stages of a 448 x 448 input, and the inner blocks of the nested schedule)
 // TS_ = pixels per tile side: 14 (the 7 * 2^k planes of a 224 x 224 input) or 16 (round 5: the 64 x 64 / level 3 block of a 512 x 512 input, 16-channel
 // workgroups; every plane of its ladder is even, 64 -> 32 -> 16 -> 8)
-template <int T_, int HALVES, int MODE, typename TIO, int NL_ = (T_ == 4 ? 4 : 3), int STG_ = 0, int TS_ = 14>
+template <int T_, int HALVES, int MODE, typename TIO, int NL_ = (T_ == 4 ? 4 : 3), int TS_ = 14>
 struct Geo {
     static constexpr int T = T_;
     static constexpr int TS = TS_, TH = TS_ / 2;
-    static_assert(TS == 14 || (TS == 16 && T == 4 && HALVES == 4 && NL_ == 3 && STG_ == 0), "16-pixel tiles: 64 x 64 / level 3, 16-channel workgroups");
+    static_assert(TS == 14 || (TS == 16 && T == 4 && HALVES == 4 && NL_ == 3), "16-pixel tiles: 64 x 64 / level 3, 16-channel workgroups");
     static constexpr int NL = NL_;
     static_assert(NL == (T == 4 ? 4 : 3) || NL == (T == 4 ? 3 : 2), "levels");
     static constexpr int NW = T * T / HALVES;
@@ -621,27 +510,11 @@ struct Geo {
     // LDS, in pixels: zero row | guard | L1 | guard | L2 | L3 | L4
     static constexpr int ZR = P1;
     static constexpr int O1 = ZR + 2;
-    // ALIAS (A/B, round 5; off): the planes of levels >= 2 INSIDE the level-1 plane's region.  A lane keeps its F1 tile in registers until T1 is formed, so the
-    // LDS copy of F1 is dead once F2 = down(F1) has been read (compute, barrier, write), and T1 overwrites C2 only after every lane has read it (read, barrier,
-    // write): 68 KB instead of 88 KB per workgroup = two workgroups per CU with 16-pixel tiles -- at 256 registers instead of 512 per wave, one row less in
-    // flight and two more barriers.  Measured slower at every batch size (profiles/r05_cpt16_64x64.txt): 67.3 against 62.5 us at 32 images, 88.5 against
-    // 105.5 at 64 (the banded lanes kernel: 63.8)
-    static constexpr bool ALIAS = TS == 16 && RCX_CPT16_ALIAS != 0;
-    static constexpr int O2 = ALIAS ? O1 : O1 + P1 * P1 + 2;
+    static constexpr int O2 = O1 + P1 * P1 + 2;
     static constexpr int O3 = O2 + P2 * P2;
     static constexpr int O4 = O3 + P3 * P3;
-    static constexpr int NPIX = ALIAS ? O1 + P1 * P1 + 2 : O4 + (NL >= 4 ? P4 * P4 : 0);
-    static_assert(!ALIAS || (NL == 3 && O4 <= O1 + P1 * P1), "aliased small planes must fit the level-1 plane");
-    // STG (round 4): the two streaming passes fetch their x rows by LDS-DMA into per-wave slots behind the level-1 plane -- over the planes of
-    // the levels below, dead during both passes -- and read them back with the transposing read.  A slot = one row of the wave's window:
-    // two sub-images [18 pixels: tile columns -2 .. 15][64 bytes = 32 channels] (the wave's two tiles at T = 4, the two channel halves of its
-    // tile at T = 2): 2304 bytes = 144 16-byte pieces = three DMA instructions (the third on 16 lanes).  STG_ = slots per wave (rows in flight + 1).
-    static constexpr int NSLOT = STG_;
-    static constexpr int SLOTB = 2 * 18 * 64;
-    static constexpr int STGOFF = O2 * PIXF * 4;            // byte offset of the slots
-    static constexpr int STGEND = STGOFF + NW * NSLOT * SLOTB + 256;      // + what the last transposing read of the last slot reaches past its image
-    static constexpr int LDS_BYTES = STG_ && STGEND > NPIX * PIXF * 4 ? STGEND : NPIX * PIXF * 4;
-    static_assert(!STG_ || (sizeof(TIO) == 2 && ((T == 4 && HALVES == 2) || (T == 2 && HALVES == 1)) && LDS_BYTES <= 160 * 1024), "staged rows: 16-bit activations, 64-byte sub-images");
+    static constexpr int NPIX = O4 + (NL >= 4 ? P4 * P4 : 0);
+    static constexpr int LDS_BYTES = NPIX * PIXF * 4;
 };
 
 // T = 2, HALVES = 2 (round 3): a wave = 32 channels x the two tiles of one tile row, a workgroup = two waves = 32 channels of an image with
@@ -653,12 +526,13 @@ struct Geo {
 // in different phases: one's barrier-bound small-plane phases and load waits fill with the other's passes (a 32-channel workgroup
 // alone on its CU serialises ~105 k cycles of phases that each leave most of the CU idle).  Used where cb16() says so.
 template <int T, int HALVES, int MODE, int PIXB, typename TIO, bool TRAIN = false, int LV = (T == 4 ? 4 : 3), int STG = 0, int TS = 14>
-__global__ __launch_bounds__(T * T / HALVES * 64, ((T == 4 && HALVES == 2) || (TS == 16 && RCX_CPT16_ALIAS == 0)) ? 1 : 2)   // 256 registers, 8 waves per CU (16-pixel tiles:
+__global__ __launch_bounds__(T * T / HALVES * 64, ((T == 4 && HALVES == 2) || TS == 16) ? 1 : 2)   // 256 registers, 8 waves per CU (16-pixel tiles:
                                                                                               // one 4-wave workgroup per CU -- 88 KB of LDS -- with up to 512 registers a wave)
 void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* __restrict__ wpack, const float* __restrict__ bpack,
                    int N, int C, int has_bias, SavedPyr sv)
 {
-    using G = Geo<T, HALVES, MODE, TIO, LV, STG, TS>;
+    static_assert(STG == 0, "STG: a retired staged-rows form; the parameter stays so that the kernel keeps its name");
+    using G = Geo<T, HALVES, MODE, TIO, LV, TS>;
     static_assert(LV == (T == 4 ? 4 : 3) || !TRAIN, "the shorter ladder: inference");
     static_assert(TS == 14 || !TRAIN, "16-pixel tiles: inference");
     constexpr int NL = G::NL, PIXF = G::PIXF, NWORK = G::NWORK, P0 = G::P0, P1 = G::P1, P2 = G::P2, P3 = G::P3, P4 = G::P4;
@@ -676,18 +550,13 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
     constexpr int CHB = G::CB;                                     // channels per block
     const int nb = (C + CHB - 1) / CHB;
     const unsigned total = (unsigned)N * (unsigned)nb, GD = gridDim.x;
-#ifdef RCX_CPT_NOXCD
-    const bool xcd = false;
-#else
     const bool xcd = (total & 7u) == 0 && (GD & 7u) == 0;
-#endif
     const int tid = (int)threadIdx.x;
     // the wave index stays in a scalar register; the lane index is recomputed per unit from the execution mask (v_mbcnt: no input register), so
     // the workitem id is dead after the LDS clearing and nothing per-lane is kept live -- or spilled -- across the units
     const int w_all = __builtin_amdgcn_readfirstlane(tid >> 6);
     // ---- zero the whole LDS image once (zero row, guards; and every later read is of finite data)
     for (int i = tid; i < G::LDS_BYTES / 16; i += G::NT) reinterpret_cast<float4*>(lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (STG > 0) __syncthreads();                       // a row fetched by LDS-DMA before the first unit's barrier must not meet another wave's clearing stores
   for (unsigned it = 0;; ++it) {
     unsigned unit;
     if (xcd) {
@@ -723,8 +592,6 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
     };
     const bool svon = TRAIN && sv.base != nullptr && cvalid;
 
-    CPT_STAMP(0);
-    CPT_STAMP_RT(9);
     float* const L = lds + ch;
     const float* const Lzero = L;
     float* const L1 = L + G::O1 * PIXF;
@@ -770,47 +637,17 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
         trow_load<TIO, PIXB>(raw, voffL, voffM, voffR, rsrc, rb, pix);
     };
     auto row_valid = [&](int r) -> bool { const int ar = TS * tr + r; return ar >= 0 && ar < P0; };   // uniform
-    // STG: this lane's three source offsets (piece j, lane i = chunk 64 j + i of the row image: sub-image s = chunk / 72, pixel (chunk % 72) / 4 =
-    // tile column - 2, 16-byte quarter chunk % 4 of the sub-image's 32 channels; s = the wave's tile (T = 4) or the channel half (T = 2)), the
-    // LDS byte address of the wave's first slot, and this lane's address for the transposing reads
-    unsigned dv[3] = {0u, 0u, 0u};
-    int stg_lds = 0;
-    unsigned stg_tra = 0;
-    if constexpr (STG > 0) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int item = 64 * j + lane, sI = item >= 72 ? 1 : 0, rem = item - 72 * sI, px = rem >> 2, q4 = rem & 3;
-            const int col = 14 * (T == 4 ? tcb + WPR * sI : tc) + px - 2;
-            const int c0 = cb * CHB + (T == 4 ? 0 : 32 * sI) + 8 * q4;                       // first of the chunk's eight channels
-            dv[j] = (col >= 0 && col < P0 && c0 < C && item < 144) ? (unsigned)(col * pix + c0 * ESZ) : OOB;
-        }
-        const int lbase = G::STGOFF + w * (G::NSLOT * G::SLOTB);
-        stg_lds = __builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(__attribute__((address_space(3))) char*)(reinterpret_cast<char*>(lds) + lbase));
-        const int g = lane >> 4;
-        stg_tra = (unsigned)(size_t)(__attribute__((address_space(3))) char*)(reinterpret_cast<char*>(lds) + lbase + (g >> 1) * (18 * 64) + ((lane >> 2) & 3) * 64 + (g & 1) * 32 + (lane & 3) * 8);
-    }
-    auto stg_request = [&](auto sc, int r) {                      // request row r (tile-local) into slot sc
-        int ar = TS * tr + r;
-        ar = ar < 0 ? 0 : (ar > P0 - 1 ? P0 - 1 : ar);
-        const int rb = __builtin_amdgcn_readfirstlane(ar * (P0 * pix));
-        stage_row(dv[0], dv[1], dv[2], rsrc, rb, stg_lds + decltype(sc)::value * G::SLOTB);
-    };
     // pass 1's first rows are requested before the taps, the LDS clearing's tail and the barrier: their HBM latency runs behind those
-    constexpr int AHEAD1 = TS == 16 && RCX_CPT16_ALIAS != 0 ? 1 : (RCX_CPT_PF > 0 ? 2 : RCX_CPT_AHEAD1), R01 = -2, NR1 = TS + 3;     // 16-pixel tiles: 20-register rows, one row less in flight
+    constexpr int AHEAD1 = AHEAD_P1, R01 = -2, NR1 = TS + 3;
 
     uint32_t raw1[NR1][NCOL];
-    constexpr int SAH = STG > 0 ? STG - 1 : 0;                 // staged rows in flight in front of the row being used
-    if constexpr (STG > 0) sfor<SAH>([&](auto rc) { stg_request(IC<decltype(rc)::value % (STG > 0 ? STG : 1)>{}, R01 + decltype(rc)::value); });
-    else if constexpr (RCX_CPT_PF == 0) sfor<AHEAD1>([&](auto rc) { load_row(raw1[decltype(rc)::value], R01 + decltype(rc)::value); });
+    sfor<AHEAD1>([&](auto rc) { load_row(raw1[decltype(rc)::value], R01 + decltype(rc)::value); });
     const __amdgpu_buffer_rsrc_t wsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wpack, 0, (NL + 2) * 25 * C * 4, 0x00020000);
     // no bias: a buffer of zero records, every load returns 0 (no per-lane flag for an exec-masked load kept live -- or spilled -- across the units)
     const __amdgpu_buffer_rsrc_t bsrc = __builtin_amdgcn_make_buffer_rsrc((void*)bpack, 0, has_bias ? (NL + 2) * C * 4 : 0, 0x00020000);
     Taps td;
     load_taps(td, wsrc, bsrc, 0, C, cc);
     __syncthreads();
-    CPT_STAMP(1);
-    if constexpr (RCX_CPT_PRIO > 0) { if (w >= G::NW / 2) __builtin_amdgcn_s_setprio(RCX_CPT_PRIO); }
-    if constexpr (RCX_CPT_STAGGER > 0) { if (w >= G::NW / 2) __builtin_amdgcn_s_sleep(RCX_CPT_STAGGER); }
 
     // ================= pass 1: F1 tile = down(x), rows -2 .. 14 of the tile, input-row stationary (tap pairs) =================
     float f1[TH][TH];                                        // this lane's F1 tile stays in registers until T1 is formed
@@ -820,56 +657,19 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
         uint32_t (&raw)[NR][NCOL] = raw1;
         f32x2 facc[3][TH];
         // The per-lane loads move 2 bytes each and a wave holds at most 63 memory operations: 3 rows in flight do not cover the HBM
-        // latency (stamps: this pass takes 20 k cycles for 11 k cycles of issue).  Tried (-DRCX_CPT_PF=2): pull each row into L2 first
-        // with a few WIDE loads (16 bytes per lane, results discarded) PF rows ahead of the element loads.  Measured slower (pass 1:
-        // 26 k cycles, 56x56 launch 111.7 vs 105.3 us): a wave's memory operations complete in issue order, so the element loads
-        // queue behind the wide loads' HBM latency instead of overtaking them.  Off by default, kept for A/B builds.
-        constexpr int PF = RCX_CPT_PF;
-        constexpr int CPP = PIXF * ESZ / 16;                   // 16-byte chunks per pixel of the block
-        constexpr int PPI = (64 / HALVES) / CPP;               // pixels per instruction and tile
-        constexpr int NPF = PF > 0 ? (NCOL + PPI - 1) / PPI : 0; // instructions per row
-        u32x4pf sink = {0u, 0u, 0u, 0u};                       // destination of the wide loads: kept live to the end of the pass
-        const int pj = (lane & (64 / HALVES - 1)) / CPP, pchunk = lane & (CPP - 1);
-        unsigned pvo[NPF > 0 ? NPF : 1];                       // this lane's offsets inside a row, one per instruction
-#pragma unroll
-        for (int i = 0; i < NPF; ++i) {
-            int colp = TS * tc - 2 + i * PPI + pj;             // columns left of the image: re-read column 0; right of it: the next row or out of range
-            colp = colp < 0 ? 0 : colp;
-            pvo[i] = (unsigned)(colp * pix + (cb * PIXF) * ESZ + pchunk * 16);
-        }
-        auto prefetch_row = [&](int r) {
-            if constexpr (PF > 0) {
-                int ar = TS * tr + r;
-                ar = ar < 0 ? 0 : (ar > P0 - 1 ? P0 - 1 : ar);
-                const int rb = __builtin_amdgcn_readfirstlane(ar * (P0 * pix));
-#pragma unroll
-                for (int i = 0; i < NPF; ++i) {
-                    int t;
-                    asm volatile("s_add_i32 %[t], %[rb], 0\n\tbuffer_load_dwordx4 %[d], %[vo], %[rs], %[t] offen"
-                                 : [d] "+v"(sink), [t] "=&s"(t) : [vo] "v"(pvo[i]), [rs] "s"(rsrc), [rb] "s"(rb) : "scc");
-                }
-            }
-        };
-        if constexpr (STG == 0) sfor<AHEAD + PF>([&](auto rc) { prefetch_row(R0 + decltype(rc)::value); });
-        if constexpr (PF > 0 && STG == 0) sfor<AHEAD>([&](auto rc) { load_row(raw[decltype(rc)::value], R0 + decltype(rc)::value); });
+        // latency (this pass takes 20 k cycles for 11 k cycles of issue).  Pulling each row into L2 first with a few wide loads was measured
+        // slower (pass 1: 26 k cycles, 56x56 launch 111.7 vs 105.3 us): a wave's memory operations complete in issue order, so the element
+        // loads queue behind the wide loads' HBM latency instead of overtaking them.
         sfor<NR>([&](auto rc) {
             constexpr int ri = decltype(rc)::value, r = R0 + ri;
-            if constexpr (STG > 0) {
-                constexpr int SN = STG > 0 ? STG : 1;
-                if constexpr (ri + SAH < NR) stg_request(IC<(ri + SAH) % SN>{}, r + SAH);          // its slot held row ri - 1: read and waited for in the last iteration
-                constexpr int NYS = 3 * (NR - 1 - ri < SAH ? NR - 1 - ri : SAH);
-                fetch_row<TIO, NYS, (ri % SN) * G::SLOTB>(raw[ri], stg_tra);
-            } else {
-            if constexpr (ri + AHEAD + PF < NR) prefetch_row(r + AHEAD + PF);
             if constexpr (ri + AHEAD < NR) load_row(raw[ri + AHEAD], r + AHEAD);
-            // younger memory operations: what the iterations since row ri was requested have issued (wide loads first, then a row)
+            // younger memory operations: what the iterations since row ri was requested have issued
             constexpr int NY = [] {
                 int k = 0;
-                for (int j = 1; j <= AHEAD; ++j) k += (ri + j < NR ? NCOL : 0) + (ri + j + PF < NR ? NPF : 0);
+                for (int j = 1; j <= AHEAD; ++j) k += ri + j < NR ? NCOL : 0;
                 return k > 63 ? 63 : k;
             }();
             trow_pin<NY>(raw[ri]);
-            }
             f32x2 xr[NCOL / 2];
 #pragma unroll
             for (int k = 0; k < NCOL / 2; ++k) xr[k] = f32x2{raw_f32<TIO>(raw[ri][2 * k]), raw_f32<TIO>(raw[ri][2 * k + 1])};
@@ -909,11 +709,8 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
             for (int o = 0; o < TH; ++o) if (r - 2 * o + 2 >= 0 && r - 2 * o + 2 < 4) pin(facc[o % 3]);
             CPT_FENCE;
         });
-        asm volatile("" : "+v"(sink));                         // every wide load has landed by now (the last rows' waits were vmcnt(0))
     }
-    CPT_STAMP(2);
     __syncthreads();
-    CPT_STAMP(3);
 
     // ================= chain: the small planes, pieces dealt over the T*T tile-lanes =================
     // conv j of the pack: 0 = down, 1 + (NL - l) = the conv of level l, 1 + NL = the final conv
@@ -937,7 +734,7 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
                 const bool act = rr < P;
                 // the wave's smallest row of this round (its first tile-lane's; scalar): a wave with no row at all leaves the round to the others --
                 // the LDS pipe and the SIMD partner see half (7-wide planes at T = 4) or a quarter (4-wide) of the instructions
-                if constexpr (RCX_CPT_SKIPW != 0 && !TRAIN) {
+                if constexpr (!TRAIN) {
                     if (tr * T + tcb + NWORK * rnd >= P) return;
                 }
                 f(rc, IC<0>{}, IC<P>{}, act ? rr : 0, act);
@@ -948,22 +745,6 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
     sfor<NL - 1>([&](auto lc) {
         constexpr int l = 2 + decltype(lc)::value;
         constexpr int PIN = PL[l - 1], PO = PL[l];
-        if constexpr (G::ALIAS && l == 2) {
-            // F2 lands where F1 was read from: every piece is computed before the first one is written
-            static_assert(PO > 8, "two column segments");
-            float o2[2][PO / 2];
-            for_pieces(IC<PO>{}, [&](auto rc, auto col0c, auto noutc, int row, bool) {
-                down_piece<PIN, decltype(col0c)::value, decltype(noutc)::value, PIXF>(LP[1], Lzero, row, td, o2[decltype(rc)::value]);
-            });
-            __syncthreads();
-            for_pieces(IC<PO>{}, [&](auto rc, auto col0c, auto noutc, int row, bool act) {
-                if (act) {
-                    float* dst = LP[2] + (row * PO + decltype(col0c)::value) * PIXF;
-#pragma unroll
-                    for (int i = 0; i < decltype(noutc)::value; ++i) dst[i * PIXF] = o2[decltype(rc)::value][i];
-                }
-            });
-        } else
         for_pieces(IC<PO>{}, [&](auto, auto col0c, auto noutc, int row, bool act) {
             constexpr int COL0 = decltype(col0c)::value, NOUT = decltype(noutc)::value;
             float out[NOUT];
@@ -980,7 +761,6 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
         });
         __syncthreads();
     });
-    CPT_STAMP(4);
     // up recursion on the piece planes: l = NL .. 2: T_l = F_l + resize(C_{l+1}) in place (l < NL), C_l = conv(T_l) in place.
     // (Requesting a level's taps one level ahead was measured: no gain -- the small planes are issue-bound -- and 20 VGPRs.)
     sfor<NL - 1>([&](auto lc) {
@@ -1021,7 +801,6 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
         __syncthreads();
     });
 
-    CPT_STAMP(5);
     // ================= level 1, per tile: T1 = F1 + resize(C2) (exact 2x), C1 = conv(T1) =================
     Taps t1;
     load_taps(t1, wsrc, bsrc, NL, C, cc);         // conv of level 1 = pack 1 + (NL - 1)
@@ -1109,7 +888,6 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
         if constexpr (LANE_PARITY) form_lane();
         else if (cpar) { if (rpar) form(IC<1>{}, IC<1>{}); else form(IC<1>{}, IC<0>{}); }
         else { if (rpar) form(IC<0>{}, IC<1>{}); else form(IC<0>{}, IC<0>{}); }
-        if constexpr (G::ALIAS) __syncthreads();             // C2 lives inside the level-1 plane: every lane has read it (form() reads it up front) before T1 overwrites it
         float* dst = L1 + ((TH * tr) * P1 + TH * tc) * PIXF;
 #pragma unroll
         for (int r = 0; r < TH; ++r)
@@ -1117,7 +895,6 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
             for (int cI = 0; cI < TH; ++cI) dst[(r * P1 + cI) * PIXF] = f1[r][cI];
     }
     __syncthreads();
-    CPT_STAMP(6);
     // halo masks of the tile (per lane): columns outside the plane contribute nothing
     const float lmask = ledge ? 0.f : 1.f, rmask = redge ? 0.f : 1.f;
     {
@@ -1179,12 +956,10 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
     Taps tf;
     load_taps(tf, wsrc, bsrc, 1 + NL, C, cc);
     __syncthreads();
-    CPT_STAMP(7);
-    if constexpr (RCX_CPT_STAGGER > 0) { if (w >= G::NW / 2) __builtin_amdgcn_s_sleep(RCX_CPT_STAGGER); }
 
     // ================= pass 2: y tile = conv(x + resize(C1)), input rows -2 .. 15, five accumulator rows in flight =================
     {
-        constexpr int AHEAD = (std::is_same<TIO, f16_t>::value || (TS == 16 && RCX_CPT16_ALIAS != 0)) && RCX_CPT_AHEAD2 > 1 ? 1 : RCX_CPT_AHEAD2, R0 = -2, NR = TS + 4;   // float16: one row less in flight (its
+        constexpr int AHEAD = std::is_same<TIO, f16_t>::value && AHEAD_P2 > 1 ? 1 : AHEAD_P2, R0 = -2, NR = TS + 4;   // float16: one row less in flight (its
                                                                                   // per-element conversions otherwise spill eight registers at 256)
         {                                                     // see set_voffs
             int l2 = lane;
@@ -1241,16 +1016,12 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
             Hs[0] = Hs[0] * splat(lmaskG);
             Hs[NHP - 1] = Hs[NHP - 1] * splat(rmaskG);
         };
-        constexpr bool STG2 = STG > 0 && RCX_CPT_STG_P2 != 0;
-        if constexpr (STG2) sfor<SAH>([&](auto rc) { stg_request(IC<decltype(rc)::value % (STG > 0 ? STG : 1)>{}, R0 + decltype(rc)::value); });
-        else sfor<AHEAD>([&](auto rc) { load_row(raw[decltype(rc)::value], R0 + decltype(rc)::value); });
+        sfor<AHEAD>([&](auto rc) { load_row(raw[decltype(rc)::value], R0 + decltype(rc)::value); });
         build_H(H[0], -2);
         build_H(H[1], -1);
         sfor<NR>([&](auto rc) {
             constexpr int ri = decltype(rc)::value, t = R0 + ri;
-            if constexpr (STG2) {
-                if constexpr (ri + SAH < NR) stg_request(IC<(ri + SAH) % (STG > 0 ? STG : 1)>{}, t + SAH);
-            } else if constexpr (ri + AHEAD < NR) load_row(raw[ri + AHEAD], t + AHEAD);
+            if constexpr (ri + AHEAD < NR) load_row(raw[ri + AHEAD], t + AHEAD);
             // vertical source rows (tile origin is even): t even -> (t/2 - 1, t/2) weight 0.75; t odd -> ((t-1)/2, (t+1)/2) weight 0.25
             constexpr int te = (t + 2) & 1;                  // parity of t (t + 2 >= 0)
             constexpr int i0 = MODE == 1 ? ((t + 2) >> 1) - 1 : (te ? (t - 1) / 2 : t / 2 - 1);
@@ -1263,14 +1034,7 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
             // end of the iterations in between (14 stores each; iteration i stores a row for 4 <= i <= 17); the counter holds 63
             constexpr int NLD = NR - 1 - ri < AHEAD ? NR - 1 - ri : AHEAD;
             constexpr int NST = [] { int k = 0; for (int j = 1; j <= AHEAD; ++j) k += (ri - j >= 4 && ri - j <= TS + 3) ? 1 : 0; return k; }();
-            if constexpr (STG2) {
-                // younger: the pieces of the rows requested since (3 each) and the output rows stored at the end of the iterations in between
-                constexpr int SLD = NR - 1 - ri < SAH ? NR - 1 - ri : SAH;
-                constexpr int SST = [] { int k = 0; for (int j = 1; j <= SAH; ++j) k += (ri - j >= 4 && ri - j <= 17) ? 1 : 0; return k; }();
-                constexpr int SNY = 3 * SLD + (sizeof(TIO) == 2 ? 14 : 14) * SST;
-                fetch_row<TIO, (SNY > 63 ? 63 : SNY), (ri % (STG > 0 ? STG : 1)) * G::SLOTB>(raw[ri], stg_tra);
-            }
-            if constexpr (!STG2) trow_pin<(NCOL * NLD + TS * NST > 63 ? 63 : NCOL * NLD + TS * NST)>(raw[ri]);
+            trow_pin<(NCOL * NLD + TS * NST > 63 ? 63 : NCOL * NLD + TS * NST)>(raw[ri]);
             if (row_valid(t)) {
                 f32x2 row[NHP], odd[NHP - 1];
 #pragma unroll
@@ -1314,50 +1078,21 @@ void k_recconv_cpt(const TIO* __restrict__ x, TIO* __restrict__ y, const float* 
             CPT_FENCE;
         });
     }
-    CPT_STAMP(8);
-    CPT_STAMP_RT(10);
-    if constexpr (RCX_CPT_ENDBAR != 0) __syncthreads();      // the next unit's pass 1 writes F1 where this unit's pass 2 read C1
+    __syncthreads();                                          // the next unit's pass 1 writes F1 where this unit's pass 2 read C1
   }
 }
 
-static inline bool enabled()
-{
-    const char* v = rcx::opt::value(rcx::opt::CPT);
-    const char* l = rcx::opt::value(rcx::opt::LANES);
-    return !(v && *v == '0') && !(l && *l == '0');
-}
+static inline bool enabled() { return !rcx::opt::off(rcx::opt::CPT) && !rcx::opt::hand_kernels_off(); }
 
-// x rows by LDS-DMA + transposing reads (STG) where the kernel has the form and the data allow it: 16-bit activations, whole 16-byte chunks of
-// eight channels (C % 8 == 0: every RecNeXt width) at 16-byte-aligned addresses, inference.  Parity-green (the 820 bf16 / float16 / golden cases of
-// tests/test_recconv_gpu.py) and NOT faster inside a model -- 56x56 x 64: 123.3 us either way (a loop over one input: 112.2 against 113.8), 28x28 x 128:
-// 55.6 against 53.6 (loop: 49.2 against 53.7), profiles/archive/r04_staged_rows.txt: with two waves per SIMD these kernels are bound by their vector-ALU
-// issue, not by the 976 -> 451 vector-memory instructions per wave this removes.  So the instantiations exist in the diagnostic build only
-// (make diag, RCX_AB_VARIANTS; RCX_CPT_STG=0 there: element loads).
-template <int T, int HALVES, typename TIO, bool TRAIN> constexpr int stg_slots()
-{
-#ifndef RCX_AB_VARIANTS
-    return 0;
-#endif
-    if (TRAIN || sizeof(TIO) != 2) return 0;
-    if (T == 4 && HALVES == 2) return 3;
-    if (T == 2 && HALVES == 1) return 2;
-    return 0;
-}
-static inline bool stg_enabled() { return !rcx::opt::is_zero(rcx::opt::CPT_STG); }
-
-template <int T, int HALVES, int MODE, int PIXB, typename TIO, bool TRAIN = false, int LV = (T == 4 ? 4 : 3), int STG = 0, int TS = 14>
+template <int T, int HALVES, int MODE, int PIXB, typename TIO, bool TRAIN = false, int LV = (T == 4 ? 4 : 3), int TS = 14>
 static hipError_t launch(const void* x, void* y, const float* wpack, const float* bpack, int N, int C, hipStream_t s, const SavedPyr& sv)
 {
-    using G = Geo<T, HALVES, MODE, TIO, LV, STG, TS>;
-    if constexpr (TS == 14 && STG == 0 && stg_slots<T, HALVES, TIO, TRAIN>() > 0) {
-        if (!sv.base && C % 8 == 0 && ((size_t)x & 15) == 0 && stg_enabled())
-            return launch<T, HALVES, MODE, PIXB, TIO, TRAIN, LV, stg_slots<T, HALVES, TIO, TRAIN>()>(x, y, wpack, bpack, N, C, s, sv);
-    }
+    using G = Geo<T, HALVES, MODE, TIO, LV, TS>;
     if constexpr (TS == 14 && !TRAIN && MODE == 0 && HALVES != 4 && !(T == 2 && HALVES == 2) && LV == (T == 4 ? 4 : 3)) {      // training forward: bilinear only (what RecConv2d trains with), whole-block variants, full ladder
         if (sv.base) return launch<T, HALVES, MODE, PIXB, TIO, true>(x, y, wpack, bpack, N, C, s, sv);
     }
     if (!TRAIN && sv.base) return hipErrorInvalidConfiguration;
-    auto kfn = k_recconv_cpt<T, HALVES, MODE, PIXB, TIO, TRAIN, LV, STG, TS>;
+    auto kfn = k_recconv_cpt<T, HALVES, MODE, PIXB, TIO, TRAIN, LV, 0, TS>;
     RCX_SET_LDS_ONCE(kfn, G::LDS_BYTES);                       // once per instantiation and device
     static std::atomic<int> cus_cache{0};
     int cus = cus_cache.load(std::memory_order_relaxed);
@@ -1369,10 +1104,9 @@ static hipError_t launch(const void* x, void* y, const float* wpack, const float
     }
     const unsigned total = (unsigned)(N * ((C + G::CB - 1) / G::CB));
     // workgroups resident at once: 8 waves per CU (256 registers each) and 160 KB of LDS
-    constexpr unsigned PER_CU = ((T == 4 && HALVES == 2) || (TS == 16 && RCX_CPT16_ALIAS == 0)) ? 1u : ((T == 2 && HALVES == 2) ? 4u : 2u);
+    constexpr unsigned PER_CU = ((T == 4 && HALVES == 2) || TS == 16) ? 1u : ((T == 2 && HALVES == 2) ? 4u : 2u);
     static_assert(PER_CU * G::LDS_BYTES <= 160 * 1024 && PER_CU * G::NW <= 8, "residency");
     unsigned cap = (unsigned)cus * PER_CU;
-    if (const char* e = rcx::opt::value(rcx::opt::CPT_GRID)) { const int g = atoi(e); if (g > 0) cap = (unsigned)g; }    // A/B knob
     cap &= ~7u;
     const unsigned grid = total <= cap || cap == 0 ? total : cap;
     RCX_LAUNCH_TIMED(kfn, dim3(grid), dim3(G::NT), G::LDS_BYTES, s, (const TIO*)x, (TIO*)y, wpack, bpack, N, C, bpack != nullptr, sv);
@@ -1404,9 +1138,9 @@ static hipError_t launch_c(const void* x, void* y, const float* wpack, const flo
 // of 32 or where 32-channel units would not fill the chip; RCX_CPT_CB=16 / 32 pins either (A/B).
 static inline bool cb16(int N, int C)
 {
-    const char* v = rcx::opt::value(rcx::opt::CPT_CB);
-    if (v && v[0] == '1') return true;
-    if (v && v[0] == '3') return false;
+    const int cb = rcx::opt::int_or(rcx::opt::CPT_CB, 0);
+    if (cb == 16) return true;
+    if (cb == 32) return false;
     return C % 32 != 0 || (long long)N * ((C + 31) / 32) < 256;
 }
 
@@ -1423,7 +1157,7 @@ template <int MODE, typename TIO>
 static hipError_t launch16(const void* x, void* y, const float* wpack, const float* bpack, int N, int C, hipStream_t s)
 {
     const SavedPyr sv{};
-    return launch<4, 4, MODE, 0, TIO, false, 3, 0, 16>(x, y, wpack, bpack, N, C, s, sv);
+    return launch<4, 4, MODE, 0, TIO, false, 3, 16>(x, y, wpack, bpack, N, C, s, sv);
 }
 
 }  // namespace cpt

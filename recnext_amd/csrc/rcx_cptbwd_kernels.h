@@ -28,15 +28,13 @@
 #include "rcx_opts.h"
 // Compiled as five translation units (rcx_cptbwd_gx.hip, _gc.hip, _wk.hip, _wd.hip, _dn.hip: RCX_CPTBWD_PART = 1 .. 5), each instantiating one kernel family.
 
-#ifndef RCX_GX_AHEAD
-#define RCX_GX_AHEAD 1              /* g rows in flight in front of the row being used (k_bwd_gx: two measured 31.1 vs 30.0 us at 128 x 64 x 56 x 56 -- these kernels move 3 - 4.3 TB/s, not latency-bound) */
-#endif
-#ifndef RCX_GC_AHEAD
-#define RCX_GC_AHEAD 1
-#endif
-
 namespace rcx {
 namespace cptbwd {
+
+// g rows in flight in front of the row being used, k_bwd_gx / k_bwd_gc (k_bwd_gx: two measured 31.1 vs 30.0 us at 128 x 64 x 56 x 56 -- these
+// kernels move 3 - 4.3 TB/s, not latency-bound)
+constexpr int GX_AHEAD = 1;
+constexpr int GC_AHEAD = 1;
 
 using namespace cpt;
 
@@ -204,7 +202,7 @@ template <int AHEAD> struct SchedGC {
 // PG / PO: bytes per pixel of g / out when known at compile time (0 = run time).  AH = g rows requested ahead of use, OCC = workgroups per CU the
 // register budget is set for.
 // HAS_K = false: out = D^T G alone (the input gradient of a plain stride-2 conv5: RecAttn2d's `down` conv in a training step); g and wf are not read.
-template <typename TG, typename TO, int H, bool HAS_D, int PG, int PO, int AH = RCX_GX_AHEAD, int OCC = 2, bool HAS_K = true>
+template <typename TG, typename TO, int H, bool HAS_D, int PG, int PO, int AH = GX_AHEAD, int OCC = 2, bool HAS_K = true>
 __global__ __launch_bounds__(256, OCC)
 void k_bwd_gx(const TG* __restrict__ g, const float* __restrict__ Gc, TO* __restrict__ out, const float* __restrict__ wf,
               const float* __restrict__ wd, int N, int C)
@@ -315,7 +313,7 @@ void k_bwd_gx(const TG* __restrict__ g, const float* __restrict__ Gc, TO* __rest
 // k_bwd_gc: gC = R^T (K^ g) on the 7 x 7 coarse pixels of a 14 x 14 tile.  g: N x H x H x C (TG); gC: N x H/2 x H/2 x C float32.
 // Local frames: g row s = image row r0 - 3 + s, column q = image column c0 - 3 + q (20 x 20); gT row o = image row r0 - 1 + o,
 // column p = image column c0 - 1 + p (16 x 16: pairs start at an ODD image column); gT(o, p) = sum_{u,v} K^[u][v] g(o + u, p + v).
-template <int MODE, typename TG, int H, int PG, int AH = RCX_GC_AHEAD, int OCC = 2>
+template <int MODE, typename TG, int H, int PG, int AH = GC_AHEAD, int OCC = 2>
 __global__ __launch_bounds__(256, OCC)
 void k_bwd_gc(const TG* __restrict__ g, float* __restrict__ gC, const float* __restrict__ wf, int N, int C)
 {
@@ -988,9 +986,9 @@ static hipError_t launch_dT(const float* G, void* out, const float* wd, int N, i
     const long long units = (long long)N * ((C + 63) / 64) * (H / 14) * (H / 14);
     const int po = C * (int)sizeof(TO);
     const dim3 grid((unsigned)((units + 3) / 4)), block(256);
-    if (po == 128) hipLaunchKernelGGL((k_bwd_gx<float, TO, H, true, 0, 128, RCX_GX_AHEAD, 2, false>), grid, block, 0, s, (const float*)nullptr, G, (TO*)out, (const float*)nullptr, wd, N, C);
-    else if (po == 256) hipLaunchKernelGGL((k_bwd_gx<float, TO, H, true, 0, 256, RCX_GX_AHEAD, 2, false>), grid, block, 0, s, (const float*)nullptr, G, (TO*)out, (const float*)nullptr, wd, N, C);
-    else hipLaunchKernelGGL((k_bwd_gx<float, TO, H, true, 0, 0, RCX_GX_AHEAD, 2, false>), grid, block, 0, s, (const float*)nullptr, G, (TO*)out, (const float*)nullptr, wd, N, C);
+    if (po == 128) hipLaunchKernelGGL((k_bwd_gx<float, TO, H, true, 0, 128, GX_AHEAD, 2, false>), grid, block, 0, s, (const float*)nullptr, G, (TO*)out, (const float*)nullptr, wd, N, C);
+    else if (po == 256) hipLaunchKernelGGL((k_bwd_gx<float, TO, H, true, 0, 256, GX_AHEAD, 2, false>), grid, block, 0, s, (const float*)nullptr, G, (TO*)out, (const float*)nullptr, wd, N, C);
+    else hipLaunchKernelGGL((k_bwd_gx<float, TO, H, true, 0, 0, GX_AHEAD, 2, false>), grid, block, 0, s, (const float*)nullptr, G, (TO*)out, (const float*)nullptr, wd, N, C);
     return hipGetLastError();
 }
 template <typename TG, typename TO, int H>
@@ -1080,7 +1078,7 @@ hipError_t bwd_wgrad_d_cpt(const void* a, int a_dt, const float* G, float* parti
 // ... and of Downsample's 7 x 7 stride-2 multiplier-2 conv (a: H x H with Cout / 2 channels, G: H/2 x H/2 with Cout): one partial row of 50 Cout sums per (image, band)
 bool bwd_wgrad_dm_cpt_applicable(int N, int Cout, int H, int W, int k)
 {
-    if (rcx::opt::is_zero(rcx::opt::BWD_CPT)) return false;
+    if (rcx::opt::hand_kernels_off()) return false;
     return k == 7 && H == W && (H == 56 || H == 28 || H == 14) && Cout >= 2 && Cout % 2 == 0 && N * (H / 14) <= 512;      // 512 partial rows: rcx_dwconv2d_bwd_workspace_bytes
 }
 hipError_t bwd_wgrad_dm_cpt(const void* a, int a_dt, const float* G, float* partial, int N, int Cout, int H, hipStream_t s, int* rows_out)
@@ -1114,9 +1112,9 @@ hipError_t bwd_wgrad_k_cpt(const void* a, int a_dt, const float* coarse, const v
 
 #endif
 #if RCX_CPTBWD_PART == 1
+// (shape only -- it also sizes the backward workspace, whatever the switches; the dispatch checks rcx::opt::hand_kernels_off beside it)
 bool bwd_cpt_applicable(int N, int C, int H, int W, int k)
 {
-    if (rcx::opt::is_zero(rcx::opt::BWD_CPT)) return false;
     return k == 5 && H == W && (H == 56 || H == 28) && N >= 1 && C >= 1 && (long long)N * ((C + 63) / 64) * (H / 14) * (H / 14) < (1LL << 31);
 }
 
@@ -1149,7 +1147,7 @@ hipError_t bwd_dT_cpt(const float* G, void* out, int out_dt, const float* wd, in
 // input gradient of the 7 x 7 stride-2 multiplier-2 conv (Downsample) on the 56 x 56 / 28 x 28 / 14 x 14 input planes
 bool bwd_down7m2_cpt_applicable(int N, int Cin, int H, int W, int k)
 {
-    if (rcx::opt::is_zero(rcx::opt::BWD_CPT)) return false;
+    if (rcx::opt::hand_kernels_off()) return false;
     return k == 7 && H == W && (H == 56 || H == 28 || H == 14) && N >= 1 && Cin >= 1 && (long long)N * ((2 * Cin + 63) / 64) * (H / 14) * (H / 14) < (1LL << 31);
 }
 hipError_t bwd_down7m2_cpt(const float* g, void* gx, int x_dt, const float* w, int N, int Cin, int H, hipStream_t s)

@@ -255,16 +255,10 @@ struct DownPlan {
     DownArgs args;
 };
 
-static int env_int_d(rcx::opt::Id id, int dflt)
-{
-    const char* v = rcx::opt::value(id);
-    return v && *v ? atoi(v) : dflt;
-}
-
 static DownPlan plan_down(int N, int Cin, int H, int W, int k, int stride, int dtype)
 {
     DownPlan p{};
-    if (env_int_d(rcx::opt::LANES, 1) == 0) return p;
+    if (rcx::opt::hand_kernels_off()) return p;
     if (k != 7 || stride != 2 || H != W) return p;
     int lpc;
     if (W == 56 || W == 128 || W == 64 || W == 32) lpc = 16;

@@ -16,13 +16,7 @@ template <int N, class F>
 __device__ __forceinline__ void sfor(F&& f) { sfor_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{}); }
 
 #define RCX_INL __attribute__((always_inline))
-#ifndef RCX_ROW_FENCE
 #define RCX_ROW_FENCE __builtin_amdgcn_sched_barrier(0)
-#endif
-
-#ifndef RCX_PK_FMA
-#define RCX_PK_FMA 1
-#endif
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // plain vector loads/stores (HIP's uint4 copies as memcpy)
 
@@ -133,62 +127,15 @@ constexpr VT vtab(int mode, int n_in, int n_out, int d)
 }
 
 // ------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) float lds_float;     // explicit LDS pointers: a generic float* member would become flat_load
 
 // per-lane context
 struct Ctx {
     int lane_in_group;       // 0 .. LPC-1
     int mode;                // 0 bilinear, 1 nearest
-    lds_float* xl[3];        // RCX_XCH_LDS: the lane's exchange lines for B = 1, 2, 4 columns per lane (lowest address it touches)
 };
 
-// ------------------------------------------------------------------------------------------------
-// Neighbour exchange through LDS instead of DPP (compiled in with -DRCX_XCH_LDS=1; measured, not the default).
-// On gfx950 ANY DPP/SDWA instruction drops the SIMD out of its 2-cycle VALU issue mode for the next ~100
-// instructions (tools/ubench/xlane.hip, dpp_window.hip: 5 v_fmac + 1 v_mov_dpp run at 4.1 cycles per instruction
-// however many waves are resident; the same stream with ds_swizzle or LDS reads instead runs at 2.2-2.7), so a kernel
-// with one DPP move per dozen FMAs never leaves the slow mode.  Here a row goes through a per-channel line in LDS
-// instead: the lane writes its B values and reads the neighbours' (one wave owns the whole channel and its LDS
-// operations execute in order, so no barrier is involved).  Result on MI355X: bit-identical output, no DPP left, but
-// the LDS pipe becomes the limiter (LDS busy 26 % -> 58 %, SQ_WAIT_INST_LDS x7.5) and the kernels are 5-12 % SLOWER
-// (14x14: 32.3 vs 30.8 us, 28x28: 71 vs 62, 56x56: 157 vs 141), so the DPP form stays the default.  DESIGN.md 6.
-// Layout of a channel's lines:
-//   B = 1:  [XCH_PAD zeros][LPC slots][XCH_PAD zeros]
-//   B >= 2: B planes of [zero][LPC slots][zero], plane i holds column i of every lane
-// The zeros (and the slots of the EXEC-disabled guard lanes, which are never written) are the horizontal padding.
-#ifndef RCX_XCH_LDS
-#define RCX_XCH_LDS 0
-#endif
-constexpr int XCH_PAD = 8;                                   // zeros each side of the B = 1 line: 2 * the largest lane stride (4)
-constexpr int xch_dmax(int b0, int level)
-{
-    int b = b0, d = 1;
-    for (int l = 0; l < level; ++l) { if (b >= 2) b /= 2; else d *= 2; }
-    return d;
-}
-constexpr int xch_pl(int lpc) { return lpc + 2; }
-constexpr int xch_line1(int lpc) { return lpc + 2 * XCH_PAD; }
-// floats per channel, padded so that the channels of a 32-lane half start on different banks
-constexpr int xch_stride(int lpc, int b0)
-{
-    int n = xch_line1(lpc) + (b0 >= 2 ? 2 * xch_pl(lpc) : 0) + (b0 >= 4 ? 4 * xch_pl(lpc) : 0);
-    while (n % 16 != lpc % 16 || n % 32 == 0) ++n;            // lpc 8: stride = 8 or 24 (mod 32); lpc 16: 16 (mod 32)
-    return n;
-}
-// the lane's three line pointers inside the workgroup's exchange area; every access is at a non-negative immediate offset:
-// B = 1 line: own slot at +XCH_PAD; planes: own slot at +1 (the left neighbour's at +0, the right one's at +2)
-template <int LPC>
-__device__ __forceinline__ void xch_setup(Ctx& c, float* area, int ch, int b0)
-{
-    lds_float* base = (lds_float*)area + ch * xch_stride(LPC, b0) + c.lane_in_group;
-    c.xl[0] = base;
-    c.xl[1] = base + xch_line1(LPC);
-    c.xl[2] = c.xl[1] + 2 * xch_pl(LPC);
-}
-__device__ __forceinline__ void xch_put(lds_float* p, float v) { *reinterpret_cast<volatile lds_float*>(p) = v; }
-__device__ __forceinline__ float xch_get(const lds_float* p) { return *reinterpret_cast<const volatile lds_float*>(p); }
-
-// row with two halo columns each side: ext[0]=col-2, ext[1]=col-1, ext[2..B+1]=own, ext[B+2], ext[B+3]
+// row with two halo columns each side: ext[0]=col-2, ext[1]=col-1, ext[2..B+1]=own, ext[B+2], ext[B+3].  (The same exchange through a
+// per-channel line in LDS instead of DPP was measured 5-12 % slower: the LDS pipe becomes the limiter)
 template <int LPC, int B, int D>
 __device__ __forceinline__ void make_ext(const float (&row)[B], float (&ext)[B + 4])
 {
@@ -205,38 +152,6 @@ __device__ __forceinline__ void make_ext(const float (&row)[B], float (&ext)[B +
         ext[3] = from_right<D, LPC>(row[0]);
         ext[4] = from_right<D, LPC>(ext[3]);
     }
-}
-
-// the same through the channel's LDS exchange line (RCX_XCH_LDS), else the DPP form above
-template <int LPC, int B, int D>
-__device__ __forceinline__ void make_ext(const float (&row)[B], float (&ext)[B + 4], const Ctx& c)
-{
-#if RCX_XCH_LDS
-    if constexpr (RCX_XCH_LDS == 2 && B == 1) { make_ext<LPC, B, D>(row, ext); return; }   // hybrid: DPP below the B >= 2 levels
-    static_assert(B == 1 || B == 2 || B == 4, "exchange lines exist for 1, 2 and 4 columns per lane");
-    constexpr int PL = xch_pl(LPC);
-#pragma unroll
-    for (int j = 0; j < B; ++j) ext[2 + j] = row[j];
-    if constexpr (B >= 2) {
-        lds_float* p = c.xl[B == 2 ? 1 : 2];
-#pragma unroll
-        for (int i = 0; i < B; ++i) xch_put(p + i * PL + 1, row[i]);
-        ext[0] = xch_get(p + (B - 2) * PL);
-        ext[1] = xch_get(p + (B - 1) * PL);
-        ext[B + 2] = xch_get(p + 2);
-        ext[B + 3] = xch_get(p + PL + 2);
-    } else {
-        static_assert(2 * D <= XCH_PAD, "lane stride beyond the exchange line's padding");
-        lds_float* p = c.xl[0] + XCH_PAD;
-        xch_put(p, row[0]);
-        ext[0] = xch_get(p - 2 * D);
-        ext[1] = xch_get(p - D);
-        ext[3] = xch_get(p + D);
-        ext[4] = xch_get(p + 2 * D);
-    }
-#else
-    make_ext<LPC, B, D>(row, ext);
-#endif
 }
 
 // The 25 taps + bias of one conv as 15 aligned register pairs, three per tap row: (w0,w1) (w2,w3) (w4,-), the bias in the
@@ -277,7 +192,7 @@ __device__ __forceinline__ void conv5_s1(const Taps& w, InRow&& in_row, OutRow&&
 {
     const float bias = w.bias();
     // B odd: two taps per v_pk_fma_f32 into two partial sums per output (taps 0,2,4 / 1,3), added when the row is complete
-    constexpr bool TP = RCX_PK_FMA && PK && (B % 2) == 1;
+    constexpr bool TP = PK && (B % 2) == 1;
     float acc[H][B];
     f32x2 acc2[TP ? H : 1][B];
     auto emit = [&](auto O) RCX_INL {
@@ -291,36 +206,18 @@ __device__ __forceinline__ void conv5_s1(const Taps& w, InRow&& in_row, OutRow&&
             out_row(O, acc[o]);
         }
     };
-#if RCX_XCH_LDS
-    float ahead[B + 4];                                               // row r+1 goes through the exchange under row r's FMAs
-    {
-        float row[B];
-        in_row(IC<0>{}, row);
-        make_ext<LPC, B, D>(row, ahead, c);
-    }
-#endif
     sfor<H>([&](auto R) RCX_INL {
         constexpr int r = decltype(R)::value;
         float ext[B + 4];
-#if RCX_XCH_LDS
-#pragma unroll
-        for (int k = 0; k < B + 4; ++k) ext[k] = ahead[k];
-        if constexpr (r + 1 < H) {
-            float row[B];
-            in_row(IC<r + 1>{}, row);
-            make_ext<LPC, B, D>(row, ahead, c);
-        }
-#else
         float row[B];
         in_row(R, row);
-        make_ext<LPC, B, D>(row, ext, c);
-#endif
+        make_ext<LPC, B, D>(row, ext);
         sfor<5>([&](auto U) RCX_INL {
             constexpr int u = decltype(U)::value;
             constexpr int o = r + 2 - u;
             if constexpr (o >= 0 && o < H) {
                 constexpr bool first = (u == 0) || (r == 0);             // input row max(o-2, 0) is the first to reach output row o
-                if constexpr (RCX_PK_FMA && PK && B % 2 == 0) {
+                if constexpr (PK && B % 2 == 0) {
                     // two adjacent columns per v_pk_fma_f32 (the tap is splat through op_sel): same products, same order of
                     // summation as the scalar form, half the instructions -- and a packed FMA costs the same 4 cycles as
                     // any other VALU instruction once a DPP move has put the SIMD into its slow issue mode
@@ -369,32 +266,14 @@ __device__ __forceinline__ void conv5_s2(const Taps& w, InRow&& in_row, float (&
 {
     const float bias = w.bias();
     // two taps per v_pk_fma_f32 into two partial sums per output (taps 0,2,4 / 1,3), added when the output row is complete
-    constexpr bool TP = RCX_PK_FMA && PK;
+    constexpr bool TP = PK;
     f32x2 out2[TP ? HO : 1][BO];
-#if RCX_XCH_LDS
-    float ahead[BI + 4];
-    {
-        float row[BI];
-        in_row(IC<0>{}, row);
-        make_ext<LPC, BI, D>(row, ahead, c);
-    }
-#endif
     sfor<HI>([&](auto R) RCX_INL {
         constexpr int r = decltype(R)::value;
         float ext[BI + 4];
-#if RCX_XCH_LDS
-#pragma unroll
-        for (int k = 0; k < BI + 4; ++k) ext[k] = ahead[k];
-        if constexpr (r + 1 < HI) {
-            float row[BI];
-            in_row(IC<r + 1>{}, row);
-            make_ext<LPC, BI, D>(row, ahead, c);
-        }
-#else
         float row[BI];
         in_row(R, row);
-        make_ext<LPC, BI, D>(row, ext, c);
-#endif
+        make_ext<LPC, BI, D>(row, ext);
         sfor<5>([&](auto U) RCX_INL {
             constexpr int u = decltype(U)::value;
             constexpr int t = r + 2 - u;                                 // = 2 * o
@@ -493,35 +372,6 @@ __device__ __forceinline__ void hresize_row(const float (&cr)[BC], const float (
     for (int j = 0; j < BF; ++j) out[j] = fmaf(wt[j][1], cext[j / 2 + (j & 1) + 1], wt[j][0] * cext[j / 2 + (j & 1)]);
 }
 
-template <int LPC, int BC, int BF>
-__device__ __forceinline__ void hresize_row(const float (&cr)[BC], const float (&wt)[BF][2], float (&out)[BF], const Ctx& c)
-{
-#if RCX_XCH_LDS
-    if constexpr (RCX_XCH_LDS == 2 && BF == 1) { hresize_row<LPC, BC, BF>(cr, wt, out); return; }
-    static_assert(BC == 1 || BC == 2 || BC == 4, "exchange lines exist for 1, 2 and 4 columns per lane");
-    constexpr int PL = xch_pl(LPC);
-    float cext[BC + 2];
-#pragma unroll
-    for (int i = 0; i < BC; ++i) cext[1 + i] = cr[i];
-    if constexpr (BC == 1) {
-        lds_float* p = c.xl[0] + XCH_PAD;
-        xch_put(p, cr[0]);
-        cext[0] = xch_get(p - 1);
-        cext[2] = xch_get(p + 1);
-    } else {
-        lds_float* p = c.xl[BC == 2 ? 1 : 2];
-        xch_put(p + 1, cr[0]);
-        xch_put(p + (BC - 1) * PL + 1, cr[BC - 1]);
-        cext[0] = xch_get(p + (BC - 1) * PL);
-        cext[BC + 1] = xch_get(p + 2);
-    }
-#pragma unroll
-    for (int j = 0; j < BF; ++j) out[j] = fmaf(wt[j][1], cext[j / 2 + (j & 1) + 1], wt[j][0] * cext[j / 2 + (j & 1)]);
-#else
-    hresize_row<LPC, BC, BF>(cr, wt, out);
-#endif
-}
-
 // Level l of the pyramid.  run_io() is the general form: in_row(IC<r>, row) yields row r of F_l (it is called
 // TWICE per row when l < LEVEL: once for the stride-2 conv, once to build T_l = F_l + resize(C_{l+1})), and
 // out_row(IC<o>, row) receives C_l = conv_{LEVEL-l}(T_l) row by row.  run() is the all-in-registers wrapper
@@ -585,23 +435,15 @@ struct Level {
         if constexpr (B >= 2) {
             float wt[B][2];
             hweights_2x<BN, B>(c, WN, W, wt);
-            sfor<WN>([&](auto R) RCX_INL { hresize_row<LPC, BN, B>(Cn[decltype(R)::value], wt, hrow[decltype(R)::value], c); });
+            sfor<WN>([&](auto R) RCX_INL { hresize_row<LPC, BN, B>(Cn[decltype(R)::value], wt, hrow[decltype(R)::value]); });
         } else {
             float wt[5];
             hweights_off<D>(c, WN, W, wt);
             sfor<WN>([&](auto R) RCX_INL {
                 constexpr int r = decltype(R)::value;
                 const float v = Cn[r][0];
-#if RCX_XCH_LDS == 1
-                static_assert(2 * D <= XCH_PAD, "lane stride beyond the exchange line's padding");
-                lds_float* p = c.xl[0] + XCH_PAD;
-                xch_put(p, v);
-                const float l2 = xch_get(p - 2 * D), l1 = xch_get(p - D);
-                const float r1 = xch_get(p + D), r2 = xch_get(p + 2 * D);
-#else
                 const float l1 = from_left<D, LPC>(v), l2 = from_left<D, LPC>(l1);
                 const float r1 = from_right<D, LPC>(v), r2 = from_right<D, LPC>(r1);
-#endif
                 float a = wt[0] * l2;
                 a = fmaf(wt[1], l1, a);
                 a = fmaf(wt[2], v, a);

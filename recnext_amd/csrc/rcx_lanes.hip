@@ -17,25 +17,6 @@
 #include "rcx_lanes.h"
 #include "rcx_launch.h"
 
-namespace rcx {
-namespace lanes {
-
-// Diagnostic build only (-DRCX_STAMPS): thread 0 of the first workgroups records the cycle counter at phase boundaries
-// (tools/stamps_lanes.py).  The shipped library compiles these to nothing.
-#ifdef RCX_STAMPS
-__device__ unsigned long long* g_lane_stamps = nullptr;
-#define RCX_LSTAMP(id)                                                                                   \
-    do {                                                                                                \
-        if (threadIdx.x == 0 && g_lane_stamps && blockIdx.x < 256)                                      \
-            g_lane_stamps[blockIdx.x * 64 + (id)] = __builtin_readcyclecounter();                       \
-    } while (0)
-#else
-#define RCX_LSTAMP(id) do { } while (0)
-#endif
-
-}  // namespace lanes
-}  // namespace rcx
-
 #include "rcx_lanes_kernels.h"
 
 namespace rcx {
@@ -50,15 +31,6 @@ static hipError_t launch_m(const void* x, void* y, const float* wpack, const flo
     if (p.w0 == 56) return launch_b<56, 4, 16, MODE, 4, TIO>(x, y, wpack, bpack, p, s);
     return hipErrorInvalidConfiguration;
 }
-
-
-#ifdef RCX_STAMPS
-hipError_t set_stamp_buffer(void* p)
-{
-    unsigned long long* q = (unsigned long long*)p;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_lane_stamps), &q, sizeof(q));
-}
-#endif
 
 }  // namespace lanes
 

@@ -5,20 +5,10 @@
 #include "rcx_opts.h"
 #include "rcx_launch.h"
 
-#ifndef RCX_LSTAMP
-#define RCX_LSTAMP(id) do { } while (0)
-#endif
-#ifdef RCX_STAMPS
-#define RCX_LABLATE(a, bit) ((a).ablate & (bit))
-#else
-#define RCX_LABLATE(a, bit) 0
-#endif
-
 namespace rcx {
 namespace lanes {
 
 struct LanesArgs {
-    int ablate;        // diagnostic build only (RCX_LANES_ABLATE): 1 = skip the arithmetic, 2 = skip the global loads, 4 = skip the stores
     int N, C;
     int nblk;          // channel blocks per image (C / CBW)
     int ni;            // images per workgroup (consecutive)
@@ -50,8 +40,6 @@ void k_recconv_lanes(const TIO* __restrict__ x, TIO* __restrict__ y, const float
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* taps = reinterpret_cast<float*>(smem);                 // [NCONV][26][CBW]
     unsigned char* img = smem + TAPS_BYTES;                        // [HW][PITCH]
-    float* xarea = reinterpret_cast<float*>(img + HW * PITCH);     // [CBW][xch_stride]: neighbour-exchange lines (rcx_lanes.h)
-    constexpr int XFLOATS = RCX_XCH_LDS ? CBW * xch_stride(LPC, B0) : 0;
 
     const int tid = threadIdx.x;
     // workgroup -> (channel block, image group): the channel blocks of one image group get ids that are equal mod 8,
@@ -74,11 +62,9 @@ void k_recconv_lanes(const TIO* __restrict__ x, TIO* __restrict__ y, const float
         g_off[i] = p * a.C * ESZ + part * 16;
         l_off[i] = lds_slot<W0, B0, LA>(p) * PITCH + part * 16;
     });
-    RCX_LSTAMP(32);
     u32x4 v[STAGE];
     auto prefetch = [&](int n) RCX_INL {
         const unsigned char* xg = reinterpret_cast<const unsigned char*>(x + (size_t)n * img_stride + c0);
-        if (RCX_LABLATE(a, 2)) { sfor<STAGE>([&](auto I) RCX_INL { v[decltype(I)::value] = u32x4{0u, 0u, 0u, 0u}; }); return; }
         sfor<STAGE>([&](auto I) RCX_INL { v[decltype(I)::value] = *reinterpret_cast<const u32x4*>(xg + g_off[decltype(I)::value]); });
     };
     if (n0 < n1) prefetch(n0);
@@ -106,14 +92,11 @@ void k_recconv_lanes(const TIO* __restrict__ x, TIO* __restrict__ y, const float
         });
     }
 
-    for (int i = tid; i < XFLOATS; i += NT) xarea[i] = 0.f;           // the zeros are the horizontal padding; ordered by the first barrier below
-
     const int lane = tid & 63, wave = tid >> 6;
     Ctx c;
     c.lane_in_group = lane % LPC;
     c.mode = MODE;
     const int ch = wave * CPW + lane / LPC;
-    xch_setup<LPC>(c, xarea, ch, B0);
     const bool active = c.lane_in_group < LA;
     unsigned char* mine = img + c.lane_in_group * PITCH + ch * ESZ;   // + (row * W0 + j * LA) * PITCH for column j of the lane
     const float* my_taps = taps + ch;
@@ -128,12 +111,10 @@ void k_recconv_lanes(const TIO* __restrict__ x, TIO* __restrict__ y, const float
             constexpr int i = decltype(I)::value;
             if (have[i]) *reinterpret_cast<u32x4*>(img + l_off[i]) = v[i];
         });
-        if (n == n0) RCX_LSTAMP(33);
         __syncthreads();
-        if (n == n0) RCX_LSTAMP(34);
         if (n + 1 < n1) prefetch(n + 1);
         // ---- the whole block in registers; every output row overwrites the lane's own (already consumed) x bytes
-        if (active && !RCX_LABLATE(a, 1)) {
+        if (active) {
             // x rows are read one row ahead into two alternating register sets (even / odd rows), so that the LDS round trip
             // of row r+1 runs under the FMAs of row r.  bf16 lands in the upper half of a register whose lower half stays zero
             // (Raw::ld_hi), which is the f32 value.  Output rows trail the input by two rows, so the bytes are still x.
@@ -158,17 +139,14 @@ void k_recconv_lanes(const TIO* __restrict__ x, TIO* __restrict__ y, const float
                 },
                 my_taps, c);
         }
-        if (n == n0) RCX_LSTAMP(35);
         __syncthreads();
-        if (n == n0) RCX_LSTAMP(36);
         // ---- y: raw LDS image -> coalesced 16-byte stores (same thread <-> chunk mapping as the loads, so the next
         //      image's LDS writes need no barrier after these reads)
         unsigned char* yg = reinterpret_cast<unsigned char*>(y + (size_t)n * img_stride + c0);
-        if (!RCX_LABLATE(a, 4)) sfor<STAGE>([&](auto I) RCX_INL {
+        sfor<STAGE>([&](auto I) RCX_INL {
             constexpr int i = decltype(I)::value;
             if (have[i]) *reinterpret_cast<u32x4*>(yg + g_off[i]) = *reinterpret_cast<const u32x4*>(img + l_off[i]);
         });
-        if (n == n0) RCX_LSTAMP(37);
     }
 }
 
@@ -178,11 +156,8 @@ void k_recconv_lanes(const TIO* __restrict__ x, TIO* __restrict__ y, const float
 // final conv, y rows written back into the ring and stored band by band).  Levels >= 1 run in registers between the passes.
 // One __syncthreads per band; the partial sums that straddle a band boundary are carried in registers; the plane P is a
 // register array indexed through a uniform switch on the band number (only the taken case executes).
-#ifndef RCX_BANDED_WPE
-#define RCX_BANDED_WPE
-#endif
 template <int W0, int LEVEL, int LPC, int MODE, int NW, int SR, typename TIO>
-__global__ __launch_bounds__(NW * 64) RCX_BANDED_WPE
+__global__ __launch_bounds__(NW * 64)
 void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, const float* __restrict__ wpack, const float* __restrict__ bpack, LanesArgs a)
 {
     constexpr int LA = lanes_active(W0, LPC);
@@ -200,8 +175,6 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* taps = reinterpret_cast<float*>(smem);
     unsigned char* ring = smem + TAPS_BYTES;      // [3][BAND_PX][PITCH]
-    float* xarea = reinterpret_cast<float*>(ring + 3 * BAND_BYTES);   // [CBW][xch_stride]: neighbour-exchange lines (rcx_lanes.h)
-    constexpr int XFLOATS = RCX_XCH_LDS ? CBW * xch_stride(LPC, B0) : 0;
 
     const int tid = threadIdx.x;
     // workgroup -> (channel block, image group): the channel blocks of one image group get ids that are equal mod 8,
@@ -277,22 +250,18 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
         });
     }
 
-    for (int i = tid; i < XFLOATS; i += NT) xarea[i] = 0.f;           // the zeros are the horizontal padding; ordered by the barrier below
-
     const int lane = tid & 63, wave = tid >> 6;
     Ctx c;
     c.lane_in_group = lane % LPC;
     c.mode = MODE;
     const int ch = wave * CPW + lane / LPC;
-    xch_setup<LPC>(c, xarea, ch, B0);
     const bool active = c.lane_in_group < LA;
     const int mine = c.lane_in_group * PITCH + ch * ESZ;              // + (row * W0 + j * LA) * PITCH for column j of the lane
     const float* my_taps = taps + ch;
     constexpr VT te = vtab(MODE, H1, H0, 2), to = vtab(MODE, H1, H0, 3);   // vertical weights of an interior even / odd row
     // packed FMAs in pass 2 only where the register pairs still leave two waves per SIMD (float32 I/O stages twice the bytes)
-    constexpr bool PK2 = RCX_PK_FMA && sizeof(TIO) == 2;
+    constexpr bool PK2 = sizeof(TIO) == 2;
 
-    RCX_LSTAMP(0);
     __syncthreads();                               // taps are read (pass 1 keeps them in registers) before the first band barrier
     int slot = 0;
     auto slot_ptr = [&](int k) RCX_INL { return ring + ((slot + k) % 3) * BAND_BYTES; };
@@ -309,9 +278,7 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
             for (int s = 0; s < NS; ++s) {
                 unsigned char* cur = slot_ptr(0);
                 stage_in(cur);
-                if (n == n0 && s < 4) RCX_LSTAMP(8 + 3 * s);
                 __syncthreads();
-                if (n == n0 && s < 4) RCX_LSTAMP(9 + 3 * s);
                 prefetch(n, s + 1 < NS ? s + 1 : 0);
                 if (active) {
                     float L[HS + 2][B1];
@@ -330,7 +297,7 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
 #pragma unroll
                             for (int j = 0; j < B0; ++j) nxt[j] = Raw<TIO>::ld(xb + ((i + 1) * W0 + j * LA) * PITCH);
                         }
-                        make_ext<LPC, B0, 1>(row, ext, c);
+                        make_ext<LPC, B0, 1>(row, ext);
                         sfor<5>([&](auto U) RCX_INL {
                             constexpr int u = decltype(U)::value;
                             constexpr int t = i + 2 - u;
@@ -364,7 +331,6 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
 #pragma unroll
                     for (int q = 0; q < B1; ++q) { A[0][q] = L[HS][q]; A[1][q] = L[HS + 1][q]; }
                 }
-                if (n == n0 && s < 4) RCX_LSTAMP(10 + 3 * s);
                 slot = (slot + 1) % 3;
             }
             if (active) {
@@ -373,7 +339,6 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
             }
         }
         // ================= levels >= 1 in registers: P <- C_1 =================
-        if (n == n0) RCX_LSTAMP(1);
         float wt[B0][2];
         if (active) {
             float Q[H1][B1];
@@ -385,7 +350,6 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
             hweights_2x<B1, B0>(c, W1, W0, wt);
         }
         // ================= pass 2: y = conv_L(x + resize(C_1)) =================
-        if (n == n0) RCX_LSTAMP(2);
         {
             f32x2 Cy[4][B0 / 2];
             Taps w;
@@ -396,13 +360,10 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
                 unsigned char* cur = slot_ptr(0);
                 unsigned char* prev = slot_ptr(2);
                 stage_in(cur);
-                if (n == n0 && s < 4) RCX_LSTAMP(24 + 4 * s);
                 __syncthreads();
-                if (n == n0 && s < 4) RCX_LSTAMP(25 + 4 * s);
                 if (s + 1 < NS) prefetch(n, s + 1);
                 else if (n + 1 < n1) prefetch(n + 1, 0);
                 if (s >= 2) lift_band(slot_ptr(1));
-                if (n == n0 && s < 4) RCX_LSTAMP(26 + 4 * s);
                 if (active) {
                     // coarse rows HS*s - 1 .. HS*s + HS (clamped) out of the register plane, then resized horizontally.
                     // The empty asm keeps the resize inside the band loop (hoisted, it would hold every band's rows live).
@@ -421,7 +382,7 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
                     sfor<HS + 2>([&](auto K) RCX_INL {
 #pragma unroll
                         for (int q = 0; q < B1; ++q) asm volatile("" : "+v"(cw[decltype(K)::value][q]));
-                        hresize_row<LPC, B1, B0>(cw[decltype(K)::value], wt, hw[decltype(K)::value], c);
+                        hresize_row<LPC, B1, B0>(cw[decltype(K)::value], wt, hw[decltype(K)::value]);
                     });
                     // partial sums of the band's rows as column pairs (v_pk_fma_f32: two columns per instruction, the tap
                     // splat through op_sel; same products and order of summation as the scalar form)
@@ -450,7 +411,7 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
 #pragma unroll
                             for (int j = 0; j < B0; ++j) nxt[j] = Raw<TIO>::ld(xb + ((i + 1) * W0 + j * LA) * PITCH);
                         }
-                        make_ext<LPC, B0, 1>(row, ext, c);
+                        make_ext<LPC, B0, 1>(row, ext);
                         // the row as aligned pairs E[k] = (ext[2k], ext[2k+1]) and the odd ones O[k] = (ext[2k+1], ext[2k+2])
                         f32x2 E[B0 / 2 + 2], O[B0 / 2 + 1];
                         if constexpr (PK2) {
@@ -499,7 +460,6 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
                         for (int q = 0; q < B0 / 2; ++q) Cy[k][q] = L[SR + k][q];
                 }
                 if (s >= 2) drop_band(n, s - 2);
-                if (n == n0 && s < 4) RCX_LSTAMP(27 + 4 * s);
                 slot = (slot + 1) % 3;
             }
             // rows H0-2, H0-1 into the last band's slot
@@ -513,7 +473,6 @@ void k_recconv_lanes_banded(const TIO* __restrict__ x, TIO* __restrict__ y, cons
             __syncthreads();
             if (NS >= 2) store_band(n, NS - 2, slot_ptr(1));
             store_band(n, NS - 1, slot_ptr(2));
-            if (n == n0) RCX_LSTAMP(3);
         }
     }
 }
@@ -526,16 +485,10 @@ struct LanesPlan {
     LanesArgs args;
 };
 
-static inline int env_int(rcx::opt::Id id, int dflt)
-{
-    const char* v = rcx::opt::value(id);
-    return v && *v ? atoi(v) : dflt;
-}
-
 static inline LanesPlan plan(int N, int C, int H, int W, int level, int k, int dtype)
 {
     LanesPlan p{};
-    if (env_int(rcx::opt::LANES, 1) == 0) return p;
+    if (rcx::opt::hand_kernels_off()) return p;
     if (k != 5 || H != W) return p;
     if (dtype > 1) return p;                       // float16 I/O: the channel-per-lane kernels and the generic schedule (rcx_api.hip)
     int natural = -1, lpc = 8;
@@ -551,24 +504,19 @@ static inline LanesPlan plan(int N, int C, int H, int W, int level, int k, int d
     const int cpw = 64 / lpc;
     const bool banded = W >= 28 && W != 16;
     const int sr = 4;
-    int waves = env_int(rcx::opt::LANES_WAVES, W == 7 || lpc == 16 ? 8 : 4);
-    if (waves != 8 && waves != 4 && waves != 2 && waves != 1) waves = 8;
+    int waves = W == 7 || lpc == 16 ? 8 : 4;
     while (waves > 1 && C % (waves * cpw) != 0) waves >>= 1;
     if (W % 16 == 0 && waves < 4) return p;                  // the 16-family is instantiated for 8 and 4 waves only
     const int cbw = waves * cpw;
     if (C % cbw != 0 || (cbw * esz) % 16 != 0) return p;
     p.lds = (size_t)(level + 2) * 26 * cbw * 4 + (size_t)(banded ? 3 * sr : H) * W * (cbw * esz + 16);
-    if (RCX_XCH_LDS) p.lds += (size_t)cbw * xch_stride(lpc, W / lanes_active(W, lpc)) * 4;
     if (p.lds > 160 * 1024) return p;
     p.banded = banded; p.sr = sr;
     p.w0 = W; p.level = level; p.lpc = lpc; p.waves = waves;
     p.args.N = N; p.args.C = C; p.args.nblk = C / cbw;
     // enough workgroups to fill 256 CUs a few times over, the rest of the batch looped inside (taps staged once)
-    int ni = env_int(rcx::opt::LANES_NI, 0);
-    if (ni <= 0) {
-        ni = 1;
-        while ((long)p.args.nblk * ((N + 2 * ni - 1) / (2 * ni)) >= 2048 && ni < 4) ni *= 2;
-    }
+    int ni = 1;
+    while ((long)p.args.nblk * ((N + 2 * ni - 1) / (2 * ni)) >= 2048 && ni < 4) ni *= 2;
     p.args.ni = ni;
     p.ok = true;
     return p;
@@ -581,7 +529,6 @@ static hipError_t launch_w(const void* x, void* y, const float* wpack, const flo
     RCX_SET_LDS_ONCE(kfn, p.lds);
     LanesArgs a = p.args;
     a.has_bias = bpack != nullptr;
-    a.ablate = env_int(rcx::opt::LANES_ABLATE, 0);
     const unsigned grid = (unsigned)(a.nblk * (((a.N + a.ni - 1) / a.ni + 7) / 8 * 8));
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(NW * 64), p.lds, s, (const TIO*)x, (TIO*)y, wpack, bpack, a);
     return hipGetLastError();

@@ -18,7 +18,6 @@
 // in gelu -- a fiftieth of a bf16 ulp; the library's erff would be most of this kernel's vector work.
 #include "rcx_common.h"
 #include "rcx_launch.h"
-#include "rcx_opts.h"
 #include "rcx_gelu.h"
 
 namespace rcx {
@@ -209,7 +208,7 @@ k_channel_mlp(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf1
         }
         return;
     }
-    // ---- three output tiles or more (C = 80, 96; C = 128 with RCX_MLP_STREAM=0): the weights take the LDS the images would need; a token per lane straight from / to memory
+    // ---- three output tiles or more (C = 80, 96): the weights take the LDS the images would need; a token per lane straight from / to memory
     u32x4q zf[KS1];
     auto load_z = [&](int t) {
         const unsigned row = (unsigned)(32 * t + r) * (unsigned)C * 2u;       // (a token past M: past the buffer, reads 0)
@@ -474,8 +473,7 @@ hipError_t channel_mlp(const void* z, const void* x, void* y, const void* wfrag,
                                             : launch_mlp<4, 4, 2, false, false>(z, x, y, wfrag, bias, M, C, ncu, s);         // ... M2 (56 channels)
     if (ks1 == 8 && ht == 8) {
         if (C != 128) return hipErrorInvalidConfiguration;
-        const char* v = rcx::opt::value(rcx::opt::MLP_STREAM);              // RCX_MLP_STREAM=0: the whole-weights-in-LDS kernel (A/B)
-        return v && *v == '0' ? launch_mlp<8, 8, 4, true, true>(z, x, y, wfrag, bias, M, C, ncu, s) : launch_mlp_stream<8, 8, 4, 8>(z, x, y, wfrag, bias, M, C, ncu, s);
+        return launch_mlp_stream<8, 8, 4, 8>(z, x, y, wfrag, bias, M, C, ncu, s);
     }
     if (ks1 == 3 && ht == 3) return C == 48 ? launch_mlp<3, 3, 2, true, false>(z, x, y, wfrag, bias, M, C, ncu, s)            // M1 stage 0 ...
                                             : launch_mlp<3, 3, 2, false, false>(z, x, y, wfrag, bias, M, C, ncu, s);         // ... M0 (40 channels)

@@ -21,28 +21,12 @@
 //            D bands ahead are issued before the current band is convolved (register FIFO with
 //            static slots), which is what keeps HBM latency off the critical path at 1-2 waves/SIMD.
 #include "rcx_common.h"
-#include "rcx_opts.h"
 #include "rcx_launch.h"
 
 #include <cstdio>
 #include <cstdlib>
 
 namespace rcx {
-
-// Diagnostic build only (-DRCX_STAMPS): wave 0 of the first workgroups writes s_memtime at phase
-// boundaries into a debug buffer that nothing else reads. The shipped library has no stamps.
-#ifdef RCX_STAMPS
-__device__ unsigned long long* g_stamp_buf = nullptr;
-#define RCX_STAMP(id)                                                                                   \
-    do {                                                                                                \
-        if (threadIdx.x == 0 && g_stamp_buf && blockIdx.x < 256)                                        \
-            g_stamp_buf[blockIdx.x * 64 + (id)] = __builtin_readcyclecounter();                         \
-    } while (0)
-#define RCX_ABLATE(a, bit) (((a).ablate >> (bit)) & 1)
-#else
-#define RCX_STAMP(id) do { } while (0)
-#define RCX_ABLATE(a, bit) 0
-#endif
 
 constexpr int PL_MAXL = 8;
 constexpr int PL_K = 5;
@@ -70,7 +54,6 @@ struct PlaneArgs {
     int has_bias;
     int mode;                 // 0 bilinear, 1 nearest
     int single;               // 1: the whole zero-bordered plane lives in the band; pass 2 reuses it in place
-    int ablate;               // diagnostic build only: bit mask of work to skip (results are then wrong)
 };
 
 // q / d for 0 <= q < 2^20 via a float reciprocal: (q + 0.5) / d is never within rounding distance of an integer
@@ -196,7 +179,7 @@ struct Stage {
     static constexpr int G = LPP / CPL;            // 16-byte groups per pixel of this block
     static_assert(LPP % CPL == 0, "channel block narrower than one 16-byte chunk");
 
-    const TIO* xn; int c0; int H, W, C, wp, nr; int ablate;
+    const TIO* xn; int c0; int H, W, C, wp, nr;
 
     __device__ __forceinline__ bool decode(int it, int r0, int& r, int& px, int& g, float inv_row) const
     {
@@ -226,7 +209,7 @@ __device__ __forceinline__ void stage_issue(const Stage<LPP, TIO>& sg, uint4 (&p
         const int it = threadIdx.x + j * blockDim.x;
         int r, px, g;
         pre[j] = make_uint4(0u, 0u, 0u, 0u);
-        if (it < items && sg.decode(it, r0, r, px, g, inv_row) && !RCX_ABLATE(sg, 5)) pre[j] = sg.load(r, px, g);
+        if (it < items && sg.decode(it, r0, r, px, g, inv_row)) pre[j] = sg.load(r, px, g);
     }
 }
 
@@ -250,7 +233,7 @@ __device__ __forceinline__ void stage_write(const Stage<LPP, TIO>& sg, float2* _
         float2 v[CPL];
         IO<TIO>::unpack(pre[j], v);                          // zeros when outside (issue stored zeros)
         if constexpr (HAS_COARSE) {
-            if (inside && !RCX_ABLATE(sg, 3)) {
+            if (inside) {
                 const UpTap t = up_tap(trow, tcol, wc, r, px - PL_P);
 #pragma unroll
                 for (int i = 0; i < CPL; ++i) v[i] = add2(v[i], up_sample<LPP>(coarse, t, g * CPL + i));
@@ -258,7 +241,6 @@ __device__ __forceinline__ void stage_write(const Stage<LPP, TIO>& sg, float2* _
         }
         const int slot = wrap(slot0 + (r - r0), sg.nr);
         float2* dst = band + ((slot * sg.wp + px) * LPP + g * CPL);
-        if (RCX_ABLATE(sg, 4) && v[0].x != 123456.f) continue;
 #pragma unroll
         for (int i = 0; i < CPL; i += 2) *reinterpret_cast<float4*>(dst + i) = make_float4(v[i].x, v[i].y, v[i + 1].x, v[i + 1].y);
     }
@@ -385,23 +367,16 @@ __device__ __forceinline__ void conv_band(const float2* __restrict__ band, const
                 const float2* row = band + roff;
                 const float2* trow_ = tp + (u * PL_K * LPP + cp);
                 float2 v[SPAN], tw[PL_K];
-                if (!RCX_ABLATE(a, 2)) {
 #pragma unroll
-                    for (int s = 0; s < SPAN; ++s) v[s] = row[s * LPP];
-                } else {
-#pragma unroll
-                    for (int s = 0; s < SPAN; ++s) v[s] = make_float2(1.f, 1.f);
-                }
+                for (int s = 0; s < SPAN; ++s) v[s] = row[s * LPP];
 #pragma unroll
                 for (int i = 0; i < PL_K; ++i) tw[i] = trow_[i * LPP];
-                if (!RCX_ABLATE(a, 1)) {
 #pragma unroll
-                    for (int s = 0; s < SPAN; ++s) {
+                for (int s = 0; s < SPAN; ++s) {
 #pragma unroll
-                        for (int j = 0; j < TW; ++j) {
-                            const int tap = s - j * S;
-                            if (tap >= 0 && tap < PL_K) acc[j] = fma2(tw[tap], v[s], acc[j]);
-                        }
+                    for (int j = 0; j < TW; ++j) {
+                        const int tap = s - j * S;
+                        if (tap >= 0 && tap < PL_K) acc[j] = fma2(tw[tap], v[s], acc[j]);
                     }
                 }
                 ++slot;
@@ -409,14 +384,12 @@ __device__ __forceinline__ void conv_band(const float2* __restrict__ band, const
                 if (slot == a.band_rows) { slot = 0; roff -= ring_span; }
             }
             if (!hooked) { hook(); hooked = true; }
-            if (!(RCX_ABLATE(a, 0) && acc[0].x != 123456.f)) {
 #pragma unroll
-                for (int j = 0; j < TW; ++j) {
-                    const int ox = ox0 + j;
-                    if (ox < Wo) {
-                        if constexpr (TO_GLOBAL) IO<TIO>::st2(yn + ((oy * Wo + ox) * a.C + c0 + 2 * cp), acc[j]);
-                        else dst_lds[(oy * Wo + ox) * LPP + cp] = acc[j];
-                    }
+            for (int j = 0; j < TW; ++j) {
+                const int ox = ox0 + j;
+                if (ox < Wo) {
+                    if constexpr (TO_GLOBAL) IO<TIO>::st2(yn + ((oy * Wo + ox) * a.C + c0 + 2 * cp), acc[j]);
+                    else dst_lds[(oy * Wo + ox) * LPP + cp] = acc[j];
                 }
             }
         }
@@ -547,12 +520,10 @@ struct Pass {
         stage_issue<LPP, TIO>(sg, cur, first(0), row_end(0));
         for (int b = 0; b < nb; ++b) {
             __syncthreads();                              // band b-1's readers are done with the slots we overwrite
-            if (S == 1 && b < 8) RCX_STAMP(8 + 3 * b);
             // one band ahead: these loads have the whole of band b's staging + conv to arrive
             if (b + 1 < nb) stage_issue<LPP, TIO>(sg, pre, first(b + 1), row_end(b + 1));
             stage_write<LPP, HAS_COARSE, TIO>(sg, band, cur, first(b), row_end(b), coarse, wc, trow, tcol);
             __syncthreads();
-            if (S == 1 && b < 8) RCX_STAMP(9 + 3 * b);
             const int o0 = b * Bo, o1 = min(o0 + Bo, Ho);
             // Retire the prefetch between this band's FMAs and its stores: the wait then covers loads issued
             // a whole band ago and no store that was issued a moment ago (vmcnt counts both on gfx950).
@@ -591,7 +562,7 @@ k_recconv_plane(const TIO* __restrict__ x, TIO* __restrict__ y, const float* __r
     float2* taps = lds + a.taps_off;
     const int L = a.level;
     auto taps_of = [&](int i) { return taps + i * PL_TAPROWS * LPP; };
-    const Stage<LPP, TIO> sg{xn, c0, a.H, a.W, a.C, a.band_wp, a.band_rows, a.ablate};
+    const Stage<LPP, TIO> sg{xn, c0, a.H, a.W, a.C, a.band_wp, a.band_rows};
 
     // Whole-plane mode: put the first batch of x loads in flight before anything else, so the tap / table
     // preload below (L2 round trips) hides under the same HBM round trip.
@@ -599,7 +570,6 @@ k_recconv_plane(const TIO* __restrict__ x, TIO* __restrict__ y, const float* __r
     if (a.single) direct_issue<LPP, TIO>(sg, first, -PL_P, a.H + PL_P, threadIdx.x);
     // all (L+2) tap sets of this channel block and the resize tables, once; their first readers are
     // behind the first staging barrier
-    RCX_STAMP(0);
     preload_taps<LPP>(taps, wpack, a.has_bias ? bpack : nullptr, a.C, c0, L + 2);
     AxisTab* tabs = reinterpret_cast<AxisTab*>(lds + a.tab_off);
     for (int l = 0; l < L; ++l) {
@@ -623,16 +593,13 @@ k_recconv_plane(const TIO* __restrict__ x, TIO* __restrict__ y, const float* __r
             p1.run();
         }
         __syncthreads();
-        RCX_STAMP(1);
         // ---- ladder: F_{l+1} = down(F_l) ----
         for (int l = 1; l < L; ++l) {
             conv_lds<LPP, 2>(lds + a.f_off[l], a.h[l], a.w[l], lds + a.f_off[l + 1], a.h[l + 1], a.w[l + 1], taps_of(0));
             __syncthreads();
         }
-        RCX_STAMP(2);
         // ---- up recursion, coarsest first: C_l = conv_j(T_l); T_{l-1} = F_{l-1} + resize(C_l) ----
         for (int l = L, j = 0; l >= 1; --l, ++j) {
-            if (l == 1) RCX_STAMP(3);
             conv_lds<LPP, 1>(lds + a.f_off[l], a.h[l], a.w[l], lds + a.c_off[l], a.h[l], a.w[l], taps_of(1 + j));
             __syncthreads();
             if (l > 1) {
@@ -642,7 +609,6 @@ k_recconv_plane(const TIO* __restrict__ x, TIO* __restrict__ y, const float* __r
             }
         }
     }
-    RCX_STAMP(4);
     // ---- pass 2: y = conv_L(x + resize(C_1)) ----
     const float2* C1 = L >= 1 ? lds + a.c_off[1] : nullptr;
     const int wc = L >= 1 ? a.w[1] : 1;
@@ -661,17 +627,13 @@ k_recconv_plane(const TIO* __restrict__ x, TIO* __restrict__ y, const float* __r
                                           a.H, a.W, a.B2, (a.H + a.B2 - 1) / a.B2};
         p2.run();
     }
-    RCX_STAMP(5);
 }
 
 // Whole-plane planes only (the zero-bordered plane is the band): same phases as k_recconv_plane's `single`
 // path, but compiled on its own so the register allocator is not dragged to 200+ VGPRs by the banded
 // machinery (capping it at 128 VGPRs for 4 waves/SIMD still spills into the hot loops: see DESIGN.md section 6).
-#ifndef RCX_WHOLE_WAVES
-#define RCX_WHOLE_WAVES 2
-#endif
 template <int LPP, typename TIO>
-__global__ void __launch_bounds__(PL_NT, RCX_WHOLE_WAVES)
+__global__ void __launch_bounds__(PL_NT, 2)
 k_recconv_whole(const TIO* __restrict__ x, TIO* __restrict__ y, const float* __restrict__ wpack, const float* __restrict__ bpack,
                 PlaneArgs a)
 {
@@ -689,7 +651,7 @@ k_recconv_whole(const TIO* __restrict__ x, TIO* __restrict__ y, const float* __r
     float2* taps = lds + a.taps_off;
     const int L = a.level;
     auto taps_of = [&](int i) { return taps + i * PL_TAPROWS * LPP; };
-    const Stage<LPP, TIO> sg{xn, c0, a.H, a.W, a.C, a.band_wp, a.band_rows, 0};
+    const Stage<LPP, TIO> sg{xn, c0, a.H, a.W, a.C, a.band_wp, a.band_rows};
     {
         DirectBatch first;
         direct_issue<LPP, TIO>(sg, first, -PL_P, a.H + PL_P, threadIdx.x);
@@ -735,12 +697,6 @@ struct PlanePlan {
 };
 
 static inline int down_size5(int h) { return (h + 2 * PL_P - PL_K) / 2 + 1; }
-
-static int env_int(rcx::opt::Id id, int dflt)
-{
-    const char* v = rcx::opt::value(id);
-    return v && *v ? atoi(v) : dflt;
-}
 
 static void fill_args(PlaneArgs& a, int N, int C, int H, int W, int level, int lpp, int B2cand, size_t& lds_bytes)
 {
@@ -829,15 +785,11 @@ PlanePlan plan_plane(int N, int C, int H, int W, int level, int k, int dtype)
     if ((long long)H * W * C >= (1LL << 30)) return none; // per-image element offsets are 32-bit in the kernels
     const size_t LDS_CU = 160 * 1024;
     const int cpl = dtype == 1 ? 4 : 2;                    // channel pairs per 16-byte chunk
-    const int force_lpp = env_int(rcx::opt::PLANE_LPP, 0), force_b2 = env_int(rcx::opt::PLANE_B2, 0);
-    const int force_nt = env_int(rcx::opt::PLANE_NT, 0);
     static const int lpps[] = {32, 16, 8, 4};
     constexpr int WHOLE = 1 << 20;
 
     auto try_cfg = [&](int lpp, int B2, PlanePlan& out) -> bool {
         if (C % (2 * lpp) || lpp < cpl) return false;
-        if (force_lpp && lpp != force_lpp) return false;
-        if (force_b2 && (B2 == WHOLE ? H : B2) != force_b2) return false;
         if (B2 != WHOLE && B2 >= H) return false;           // same thing as the whole-plane candidate
         PlaneArgs a{};
         size_t bytes = 0;
@@ -845,17 +797,17 @@ PlanePlan plan_plane(int N, int C, int H, int W, int level, int k, int dtype)
         if (bytes > LDS_CU) return false;
         a.nblk = C / (2 * lpp);
         out.ok = true; out.lpp = lpp; out.lds_bytes = bytes; out.args = a;
-        out.nt = force_nt ? force_nt : pick_threads(a, lpp, cpl);
+        out.nt = pick_threads(a, lpp, cpl);
         if (out.nt < 64 || out.nt > PL_NT || out.nt % 64 || out.nt % lpp) out.nt = 256;
         if (!a.single && band_stage_items(a, lpp, cpl) > out.nt * PL_IPB) return false;   // FIFO slot too small
         return true;
     };
 
-    // Measured on MI355X (tools/sweep_plane.py, profiles/archive/r01b_plane_knob_sweep_*): planes up to 16x16 run best
+    // Measured on MI355X (profiles/archive/r01b_plane_knob_sweep_*): planes up to 16x16 run best
     // whole (x read once, no band loop) with the widest channel block that still lets two workgroups share a
     // CU; larger planes run banded with the widest block that fits and the tallest band that fits with it.
     PlanePlan p{};
-    const bool small = (long long)H * W <= 256 || force_b2 == H;
+    const bool small = (long long)H * W <= 256;
     if (small) {
         for (int lpp : lpps)
             if (try_cfg(lpp, WHOLE, p) && p.lds_bytes <= LDS_CU / 2) return p;
@@ -879,11 +831,6 @@ static hipError_t launch_plane_t(const void* x, void* y, const float* wpack, con
     PlaneArgs a = p.args;
     a.has_bias = bpack != nullptr;
     a.mode = mode;
-#ifdef RCX_STAMPS
-    a.ablate = env_int(rcx::opt::PLANE_ABLATE, 0);
-#else
-    a.ablate = 0;
-#endif
     const int groups = (a.N + 7) / 8;
     const unsigned grid = (unsigned)(groups * 8 * a.nblk);
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(p.nt), p.lds_bytes, s, (const TIO*)x, (TIO*)y, wpack, bpack, a);
@@ -913,14 +860,6 @@ int plane_describe(int N, int C, int H, int W, int level, int k, int dtype, char
     return snprintf(buf, len, "plane(cb=%d,%s,nt=%d,lds=%zu)", 2 * p.lpp,
                     p.args.single ? "whole-plane" : (p.args.B2 == 8 ? "band8" : (p.args.B2 == 4 ? "band4" : "band2")), p.nt, p.lds_bytes);
 }
-
-#ifdef RCX_STAMPS
-hipError_t set_stamp_buffer(void* p)
-{
-    unsigned long long* q = (unsigned long long*)p;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &q, sizeof(q));
-}
-#endif
 
 hipError_t plane_recconv(const void* x, void* y, const float* wpack, const float* bpack,
                          int N, int C, int H, int W, int level, int k, int mode, int dtype, hipStream_t s)

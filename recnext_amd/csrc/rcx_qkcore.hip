@@ -21,7 +21,6 @@
 // rcx_linear_attention_pe_fwd (their bar is 1e-3).
 #include "rcx_common.h"
 #include "rcx_launch.h"
-#include "rcx_opts.h"
 #include "rcx_cpl14_pieces.h"          // the packed-FMA row pieces of the channel-per-lane kernels: the whole unit's final conv (round 5)
 
 namespace rcx {
@@ -790,7 +789,7 @@ k_recattn_out(const float* __restrict__ d, const bf16_t* __restrict__ wqk, const
 
 // 16-bit-activation callers only (the operands of the products are bf16): heads a power of two up to 16, head dimension as heads_ok() below,
 // 16-byte-aligned d.  ONE launch when the plane has at most 64 tokens and its image (+ halo) fits the CU's LDS (at most 8 heads above 32 tokens);
-// else two launches and a workspace (at most 8 heads).  RCX_ATTN_FUSED=0: off, RCX_ATTN_FUSED=short: the one-launch form only (A/B).
+// else two launches and a workspace (at most 8 heads).
 static bool pow2_heads(int heads) { return heads > 0 && heads <= 16 && !(heads & (heads - 1)); }
 // head dimension 32, or (round 5) 4 .. 28 in steps of 4 with an even number of heads (a q / k half is whole heads): RecNeXt-A0 / A1 / A2's 20 / 24 / 28.
 // Inside the kernels a head is 32 wide either way (padded): LDS sizes and tile counts follow 32 heads, memory follows C.
@@ -808,11 +807,9 @@ static bool qkc_short(int Hp, int Wp, int C, int heads)
 }
 bool recattn_qkcore_applicable(int B, int Hp, int Wp, int C, int heads)
 {
-    const char* v = rcx::opt::value(rcx::opt::ATTN_FUSED);
-    if (v && *v == '0') return false;
     if (!(B > 0 && Hp > 0 && Wp > 0 && heads_ok(C, heads))) return false;
     if (qkc_short(Hp, Wp, 32 * heads, heads)) return true;
-    if ((v && *v == 's') || heads > 8) return false;
+    if (heads > 8) return false;
     if ((size_t)Hp * Wp * C * 4 >= (size_t)1 << 31 || B > 65535) return false;
     const qkc::LongGeo g = qkc::long_geo(B, Hp, Wp, 32 * heads, heads);
     return g.lds_out <= 160 * 1024 && g.G <= 65535;
@@ -914,11 +911,8 @@ static hipError_t launch_unit(const void* x, const float* wdn, const float* bdn,
                    : launch_unit_p<NT, KS, XW, TX, true>(x, wdn, bdn, wqk, bqk, wpe, bpe, wcv, bcv, y, B, D, s);
 }
 
-// RCX_ATTN_FUSED=twostep: the unit stays conv + attention | final conv (A/B)
 bool recattn2d_unit_applicable(int B, int H, int W, int C, int heads, int x_dt, int mode)
 {
-    const char* v = rcx::opt::value(rcx::opt::ATTN_FUSED);
-    if (v && *v == 't') return false;
     if (mode != 1 || !recattn_down_qkcore_applicable(B, H, W, C, heads, x_dt)) return false;      // (16 heads, 7 x 7 only: two heads per wave -- 16 waves of 128 registers do not hold the final conv)
     const int wo = (W + 1) / 2;
     return qkc::short_lds_bytes(wo * wo <= 32 ? 1 : 2, wo, 32 * heads, true) <= 160 * 1024;
@@ -947,11 +941,8 @@ hipError_t recattn2d_unit(const void* x, const float* wdn, const float* bdn, con
 }
 
 // RecAttn2d's stride-2 conv + coarse level in one launch: the 14 x 14 plane with 1 .. 8 heads, the 7 x 7 plane with 1 .. 16; 16-bit x.
-// RCX_ATTN_FUSED=nodown: off (A/B)
 bool recattn_down_qkcore_applicable(int B, int H, int W, int C, int heads, int x_dt)
 {
-    const char* v = rcx::opt::value(rcx::opt::ATTN_FUSED);
-    if (v && (*v == '0' || *v == 'n')) return false;
     if (!(B > 0 && heads_ok(C, heads) && (x_dt == 1 || x_dt == 2))) return false;
     if (!((H == 14 && W == 14 && heads <= 8) || (H == 7 && W == 7))) return false;
     const int wo = (W + 1) / 2;

@@ -202,7 +202,7 @@ void k_upadd_lanes(const TX* __restrict__ x, const TC* __restrict__ coarse, TX* 
                     sfor<5>([&](auto U) RCX_INL {
                         constexpr int u = decltype(U)::value;
                         constexpr int idx = i + 2 - u + 2;
-                        if constexpr (RCX_PK_FMA && sizeof(TX) == 2) {           // two columns per v_pk_fma_f32 (rcx_lanes.h, conv5_s1)
+                        if constexpr (sizeof(TX) == 2) {           // two columns per v_pk_fma_f32 (rcx_lanes.h, conv5_s1)
 #pragma unroll
                             for (int q = 0; q < B0 / 2; ++q) {
                                 f32x2 acc = u == 0 ? f32x2{bias, bias} : f32x2{L[idx][2 * q], L[idx][2 * q + 1]};
@@ -452,8 +452,7 @@ struct StepPlan {
 static StepPlan plan_step(int N, int C, int H, int W, int min_bytes_per_channel)
 {
     StepPlan p{};
-    const char* off = rcx::opt::value(rcx::opt::LANES);
-    if (off && *off == '0') return p;
+    if (rcx::opt::hand_kernels_off()) return p;
     if (H != W) return p;
     int lpc;
     if (W == 56 || W == 128 || W == 64 || W == 32) lpc = 16;

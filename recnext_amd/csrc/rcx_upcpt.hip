@@ -718,12 +718,7 @@ static hipError_t launch_down7(const void* x, void* y, const float* w, const flo
     return hipGetLastError();
 }
 
-static inline bool enabled()
-{
-    const char* v = rcx::opt::value(rcx::opt::UPADD_CPT);
-    const char* l = rcx::opt::value(rcx::opt::LANES);
-    return !(v && *v == '0') && !(l && *l == '0');
-}
+static inline bool enabled() { return !rcx::opt::off(rcx::opt::UPADD_CPT) && !rcx::opt::hand_kernels_off(); }
 
 template <int MODE, typename TIO, typename TC>
 static hipError_t launch(const void* x, const void* coarse, void* y, const float* w, const float* b, int N, int C, int H, int W, hipStream_t s)

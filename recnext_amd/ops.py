@@ -365,13 +365,10 @@ def linear_attention_core(qpre, kpre, v, pe, heads):
     return out
 
 
-FUSE_PE = __import__("os").environ.get("RCX_ATTN_FUSE_PE", "1") != "0"      # A/B switch, read at import
-
-
 def linear_attention_core_fuses_pe(c, heads):
     """Whether linear_attention_core_pe has a kernel for this head size (a multiple of four, at most 64)."""
     d = c // heads
-    return c % heads == 0 and d % 4 == 0 and d <= 64 and FUSE_PE
+    return c % heads == 0 and d % 4 == 0 and d <= 64
 
 
 def linear_attention_core_pe(qpre, kpre, v, w_pe_kkc, b_pe, heads):
@@ -392,7 +389,7 @@ def linear_attention_core_pe(qpre, kpre, v, w_pe_kkc, b_pe, heads):
         rc = _lib.load().rcx_linear_attention_pe_fwd(qpre.data_ptr(), kpre.data_ptr(), v.data_ptr(), w_pe_kkc.data_ptr(),
                                                      b_pe.data_ptr() if b_pe is not None else None, out.data_ptr(),
                                                      b, h, w, c, heads, _dt(v), _stream(v.device))
-    if rc == _lib.ERR_UNSUPPORTED:       # (RCX_ATTN_SCALAR=1 pins the kernel without this form): the caller runs the two steps
+    if rc == _lib.ERR_UNSUPPORTED:       # the matrix-core kernel has no such form: the caller runs the two steps
         return None
     _lib.check(rc, "rcx_linear_attention_pe_fwd")
     return out
