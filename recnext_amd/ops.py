@@ -73,6 +73,25 @@ def _empty_nhwc(n, c, h, w, dtype, device):
     return torch.empty((n, h, w, c), dtype=dtype, device=device).permute(0, 3, 1, 2)
 
 
+def _check_bwd_args(fn, x, shapes=(), packs=(), others=()):
+    """Extent checks of a backward entry, run before anything is allocated or launched: the C entry points see raw pointers only, so a tensor
+    smaller than the extents derived from x would be read out of range on the device.  shapes: (name, tensor, expected shape | None = only x's
+    N and C as its first two extents); packs: (name, tensor, element count) of float32 weight packs; others: (name, tensor | None) that must only
+    share x's device.  Raises ValueError naming the argument."""
+    if x.dim() != 4:
+        raise ValueError(f"{fn}: x must be 4-D (N,C,H,W), got shape {tuple(x.shape)}")
+    for name, t, want in shapes:
+        got = tuple(t.shape)
+        if (want is None and (t.dim() != 4 or got[:2] != tuple(x.shape[:2]))) or (want is not None and got != tuple(want)):
+            raise ValueError(f"{fn}: {name} has shape {got}, expected " + (f"(N, C) = {tuple(x.shape[:2])} in front of 2-D extents" if want is None else f"{tuple(want)}"))
+    for name, t, numel in packs:
+        if t.dtype != torch.float32 or t.numel() != numel:
+            raise ValueError(f"{fn}: {name} must be a float32 pack of {numel} elements, got {t.numel()} of {t.dtype}")
+    for name, t in [(n, t) for n, t, _ in shapes] + [(n, t) for n, t, _ in packs] + list(others):
+        if t is not None and t.device != x.device:
+            raise ValueError(f"{fn}: {name} is on {t.device}, x on {x.device}")
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -275,8 +294,15 @@ def dwconv2d_mult2(x, w_kkc, bias=None, k=7, stride=2):
     return y
 
 
+def _conv_out_shape(x, mult, k, stride):
+    n, c, h, w = x.shape
+    p = k // 2
+    return (n, c * mult, (h + 2 * p - k) // stride + 1, (w + 2 * p - k) // stride + 1)
+
+
 def dwconv2d_backward(x, gy, w_kkc, k, stride, need_input_grad=True, need_bias=False):
     """Backward of dwconv2d: -> (gx like x | None, gw (k,k,C) float32, gb (C) float32 | None). Deterministic."""
+    _check_bwd_args("dwconv2d_backward", x, shapes=[("gy", gy, _conv_out_shape(x, 1, k, stride))], packs=[("w_kkc", w_kkc, k * k * x.shape[1])])
     x = _nhwc(x)
     n, c, h, w = x.shape
     gy = _nhwc(gy.to(torch.float32), "grad_output")
@@ -298,6 +324,7 @@ def dwconv2d_backward(x, gy, w_kkc, k, stride, need_input_grad=True, need_bias=F
 def upadd_dwconv_backward(x, coarse, gy, w_kkc, k=5, mode="nearest", need_input_grad=True, need_coarse_grad=True, need_bias=False):
     """Backward of upadd_dwconv with a coarse plane (rcx_upadd_dwconv_bwd; model/recattn.py:67): -> (gx like x | None, gcoarse float32 like coarse | None,
     gw (k,k,C) float32, gb (C) float32 | None).  coarse must be float32; gy float32 or (where the library takes it) x's own 16-bit dtype.  Deterministic."""
+    _check_bwd_args("upadd_dwconv_backward", x, shapes=[("coarse", coarse, None), ("gy", gy, x.shape)], packs=[("w_kkc", w_kkc, k * k * x.shape[1])])
     x = _nhwc(x)
     coarse = _nhwc(coarse, "coarse")
     if coarse.dtype != torch.float32:
@@ -325,6 +352,7 @@ def upadd_dwconv_backward(x, coarse, gy, w_kkc, k=5, mode="nearest", need_input_
 
 def dwconv2d_mult2_backward(x, gy, w_kkc, k, need_input_grad=True, need_bias=False):
     """Backward of dwconv2d_mult2 (stride 2): -> (gx like x | None, gw (k,k,2C) float32, gb (2C) float32 | None)."""
+    _check_bwd_args("dwconv2d_mult2_backward", x, shapes=[("gy", gy, _conv_out_shape(x, 2, k, 2))], packs=[("w_kkc", w_kkc, k * k * 2 * x.shape[1])])
     x = _nhwc(x)
     n, c, h, w = x.shape
     gy = _nhwc(gy.to(torch.float32), "grad_output")
@@ -677,9 +705,16 @@ def recconv2d_backward(x, gy, wpack, saved, level, k, mode="bilinear", need_bias
     gradients straight into them (no packed gradient, no unpack launch, no dtype copy) and (gx, None, None) is returned.
     gy may be float32 or, where the library reads it as it is (rcx_recconv2d_bwd_gy_dtype: the 56x56 / level 4 and 28x28 / level 3 blocks), x's own
     16-bit dtype; anything else is converted to float32 here."""
-    x = _nhwc(x)
+    _check_bwd_args("recconv2d_backward", x, shapes=[("gy", gy, x.shape)],
+                    packs=[("wpack", wpack, (level + 2) * k * k * x.shape[1])] + ([("wflip", wflip, (level + 2) * k * k * x.shape[1])] if wflip is not None else []),
+                    others=[("saved", saved)])
     n, c, h, w = x.shape
     lib = _lib.load()
+    need = lib.rcx_recconv2d_train_saved_bytes(n, c, h, w, level, k)
+    if saved.numel() * saved.element_size() < need:
+        raise ValueError(f"recconv2d_backward: saved holds {saved.numel() * saved.element_size()} bytes, this problem's forward saves {need} "
+                         "(recconv2d_forward_train)")
+    x = _nhwc(x)
     want = lib.rcx_recconv2d_bwd_gy_dtype(n, c, h, w, level, k, _dt(x))
     gy = _nhwc(gy if (gy.dtype == torch.float32 or (_DT.get(gy.dtype) == want and gy.dtype == x.dtype)) else gy.to(torch.float32), "grad_output")
     if wflip is None:

@@ -1,5 +1,6 @@
 """GPU: randomised parity sweep of the fused schedules (tools/fuzz_lanes.py) with a fixed seed: every plane size of the
-register-resident families, channel counts that select every workgroup width, odd batch sizes, launch-knob overrides."""
+register-resident families, channel counts that select every workgroup width, odd batch sizes; and the fused backward schedules against the
+per-step one."""
 import os
 import sys
 
