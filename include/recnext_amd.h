@@ -117,12 +117,18 @@ int rcx_launch_events_pending(void);
  *                             Needs C % 4 == 0.  Deterministic (no atomics).
  *   rcx_recconv2d_bwd_gy_dtype  the element type rcx_recconv2d_bwd wants gy in for this problem: `dtype` where a 16-bit gy is read as it is,
  *                             else RCX_DTYPE_F32.
+ *   rcx_recconv2d_bwd_plan    the schedule rcx_recconv2d_bwd would use for this problem (same arguments as rcx_recconv2d_bwd_gy_dtype):
+ *                             "one(k_recconv_bwd_cpl7)", "one(k_recconv_bwd_cpl14)" / "one(k_recconv_bwd_cpl14,split)" (two waves per plane),
+ *                             "tiled(levels=2)+one(...)" / "tiled(levels=1)+one(...)" (the tiled fine levels, then the 14x14 block), "steps+one(...)"
+ *                             (one launch per ladder step down to a 14x14 tail), "steps", "generic" (RCX_FORCE_GENERIC=1) or "invalid";
+ *                             thread-local storage, valid until the next call on this thread.
  */
 size_t rcx_recconv2d_train_saved_bytes(int N, int C, int H, int W, int level, int k);
 size_t rcx_recconv2d_bwd_workspace_bytes(int N, int C, int H, int W, int level, int k);
 int rcx_recconv2d_fwd_train(const void* x, void* y, const float* wpack, const float* bpack, void* saved, size_t saved_bytes,
                             int N, int C, int H, int W, int level, int k, int mode, int dtype, void* stream);
 int rcx_recconv2d_bwd_gy_dtype(int N, int C, int H, int W, int level, int k, int dtype);
+const char* rcx_recconv2d_bwd_plan(int N, int C, int H, int W, int level, int k, int dtype);
 int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* wpack, const float* wpack_flipped, const void* saved,
                       void* gx, float* gwpack, float* gbpack, void* const* gw_out, void* const* gb_out, int grad_dtype,
                       void* workspace, size_t workspace_bytes,

@@ -21,9 +21,9 @@ int fail(int code, const char* fmt, ...)
     return code;
 }
 
-int hip_fail(hipError_t e, const char* what)
+int hip_fail(hipError_t e, const char* what, const char* prefix = "")
 {
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
+    snprintf(g_err, sizeof(g_err), "%s%s: %s", prefix, what, hipGetErrorString(e));
     return (int)e;
 }
 
@@ -185,6 +185,33 @@ hipError_t step_upadd(const void* x, const void* coarse, void* y, const float* w
     case STEP_CONV5_LANES: return rcx::conv5_lanes(x, y, w, b, N, C, H, W, x_dt, s);
     default: return rcx::generic_upadd_dwconv(x, coarse, y, w, b, N, C, H, W, Hc, Wc, k, mode, x_dt, c_dt, out_dt, s);
     }
+}
+
+// The per-step schedule, one launch per ladder step on the best single-step kernel each plane has: the down ladder F_l = down(F_{l-1}), F_0 = x
+// (model/recnext.py:27-29), the up recursion C_l = conv_j(F_l + resize(C_{l+1})) coarsest first (:31-33), the final conv (:34).  F_l and C_l
+// (l >= 1) are float32 planes of h[l] x w[l] at base + f_off[l] / base + c_off[l]; `prefix` starts the error messages.
+int recconv2d_steps(const void* x, void* y, const float* wpack, const float* bpack, char* base, const size_t* f_off, const size_t* c_off,
+                    const int* h, const int* w, int N, int C, int level, int k, int mode, int dtype, hipStream_t s, const char* prefix)
+{
+    const size_t wsz = (size_t)k * k * C;
+    auto W_ = [&](int i) { return wpack + (size_t)i * wsz; };                       // 0 = down, 1+j = convs[j]
+    auto B_ = [&](int i) { return bpack ? bpack + (size_t)i * C : nullptr; };
+    auto F_ = [&](int l) { return (float*)(base + f_off[l]); };
+    auto C_ = [&](int l) { return (float*)(base + c_off[l]); };
+    hipError_t e;
+    for (int l = 1; l <= level; ++l) {
+        e = step_dwconv(l == 1 ? x : (const void*)F_(l - 1), F_(l), W_(0), B_(0), N, C, h[l - 1], w[l - 1], k, 2,
+                        l == 1 ? dtype : RCX_DTYPE_F32, RCX_DTYPE_F32, s);
+        if (e != hipSuccess) return hip_fail(e, "down ladder", prefix);
+    }
+    for (int l = level, j = 0; l >= 1; --l, ++j) {
+        e = step_upadd(F_(l), l == level ? nullptr : C_(l + 1), C_(l), W_(1 + j), B_(1 + j), N, C, h[l], w[l],
+                       l == level ? 0 : h[l + 1], l == level ? 0 : w[l + 1], k, mode, RCX_DTYPE_F32, RCX_DTYPE_F32, RCX_DTYPE_F32, s);
+        if (e != hipSuccess) return hip_fail(e, "up recursion", prefix);
+    }
+    e = step_upadd(x, level >= 1 ? C_(1) : nullptr, y, W_(1 + level), B_(1 + level), N, C, h[0], w[0],
+                   level >= 1 ? h[1] : 0, level >= 1 ? w[1] : 0, k, mode, dtype, RCX_DTYPE_F32, dtype, s);
+    return e == hipSuccess ? 0 : hip_fail(e, "final conv", prefix);
 }
 
 }  // namespace
@@ -372,40 +399,10 @@ static int recconv2d_fwd_impl(const void* x, void* y, const float* wpack, const 
     const Ladder L = make_ladder(N, C, H, W, level, k);
     if (L.total > 0 && (!workspace || workspace_bytes < L.total))
         return fail(RCX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", L.total, workspace_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t wsz = (size_t)k * k * C;
-    auto W_ = [&](int i) { return wpack + (size_t)i * wsz; };                       // 0 = down, 1+j = convs[j]
-    auto B_ = [&](int i) { return bpack ? bpack + (size_t)i * C : nullptr; };
-    char* ws = (char*)workspace;
-    auto F_ = [&](int l) { return (float*)(ws + L.f_off[l]); };
-    auto Cb = [&](int l) { return (float*)(ws + L.c_off[(l + 1) & 1]); };           // C_1 -> buf 0, C_2 -> buf 1, ...
-    hipError_t e;
-    // down ladder, shared weight (model/recnext.py:27-29); F_l kept in float32
-    for (int l = 1; l <= level; ++l) {
-        const void* src = l == 1 ? x : (const void*)F_(l - 1);
-        e = step_dwconv(src, F_(l), W_(0), B_(0), N, C, L.h[l - 1], L.w[l - 1], k, 2,          // the best single-step kernel each plane has
-                        l == 1 ? dtype : RCX_DTYPE_F32, RCX_DTYPE_F32, s);
-        if (e != hipSuccess) return hip_fail(e, "down ladder");
-    }
-    // up recursion, coarsest first (model/recnext.py:31-33): C_l = conv_j(F_l + resize(C_{l+1}))
-    for (int l = level, j = 0; l >= 1; --l, ++j) {
-        const float* coarse = l == level ? nullptr : Cb(l + 1);
-        e = step_upadd(F_(l), coarse, Cb(l), W_(1 + j), B_(1 + j), N, C, L.h[l], L.w[l],
-                       l == level ? 0 : L.h[l + 1], l == level ? 0 : L.w[l + 1], k, mode,
-                       RCX_DTYPE_F32, RCX_DTYPE_F32, RCX_DTYPE_F32, s);
-        if (e != hipSuccess) return hip_fail(e, "up recursion");
-    }
-    // final conv (model/recnext.py:34)
-    e = step_upadd(x, level >= 1 ? Cb(1) : nullptr, y, W_(1 + level), B_(1 + level), N, C, H, W,
-                   level >= 1 ? L.h[1] : 0, level >= 1 ? L.w[1] : 0, k, mode,
-                   dtype, RCX_DTYPE_F32, dtype, s);
-    if (e != hipSuccess) return hip_fail(e, "final conv");
-    return 0;
+    size_t c_off[RCX_MAX_LEVEL + 1];
+    for (int l = 1; l <= level; ++l) c_off[l] = L.c_off[(l + 1) & 1];               // C_1 -> buf 0, C_2 -> buf 1, ...
+    return recconv2d_steps(x, y, wpack, bpack, (char*)workspace, L.f_off, c_off, L.h, L.w, N, C, level, k, mode, dtype, (hipStream_t)stream, "");
 }
-
-// ---- matrix-core schedules: 16-bit activations whose taps may be rounded to the same type ----
-namespace {
-}  // namespace
 
 // ---- training: forward that keeps the fp32 pyramid, and the backward pass (rcx_bwd.hip) ----
 namespace {
@@ -444,6 +441,142 @@ TrainLadder make_train_ladder(int N, int C, int H, int W, int level, int k)
     return L;
 }
 
+// The training forward's schedule: the blocks of RecNeXt at 224x224 run their inference kernel, which then also leaves the pyramid behind (one
+// launch instead of 2 * level + 1); everything else, and everything under RCX_TRAIN_FUSED=0, the per-step schedule
+enum TrainFwdSchedule { TRAIN_TILED, TRAIN_CPL14, TRAIN_CPL7, TRAIN_STEPS };
+
+TrainFwdSchedule train_fwd_schedule(int N, int C, int H, int W, int level, int k, int mode, int dtype)
+{
+    if (rcx::opt::off(rcx::opt::TRAIN_FUSED) || rcx::opt::hand_kernels_off()) return TRAIN_STEPS;
+    if (rcx::cpt_train_applicable(N, C, H, W, level, k, mode == RCX_MODE_NEAREST ? 1 : 0, dtype)) return TRAIN_TILED;
+    if (rcx::cpl14_applicable(N, C, H, W, level, k, dtype)) return TRAIN_CPL14;
+    return rcx::cpl7b_applicable(N, C, H, W, level, k, dtype) ? TRAIN_CPL7 : TRAIN_STEPS;
+}
+
+// The backward schedule of a RecConv2d block (the workspace size depends on the shape alone).  The 14x14 tail: a block deeper than level 2 whose
+// level m = level - 2 plane is 14x14 ends in exactly the 14x14 / level 2 block, whose whole backward is one launch.
+//   BWD_ONE    the 14x14 / level 2 and 7x7 / level 1 blocks: the whole backward in one launch (rcx_cplbwd.hip; RCX_BWD_FUSED=0: off)
+//   BWD_TILED  the 56x56 / level 4 and 28x28 / level 3 blocks: the m fine levels on the tiled adjoint kernels (rcx_cptbwd.hip), then the tail
+//   BWD_STEPS  one launch per ladder step, down to the tail where there is one
+enum BwdKind { BWD_ONE, BWD_TILED, BWD_STEPS };
+struct BwdSchedule { BwdKind kind; int m; bool split; };      // m: the tail's level (0: none); split: the 14x14 launch runs two waves per plane
+
+BwdSchedule bwd_schedule(const TrainLadder& L, int N, int C, int level, int k, int dtype)
+{
+    if (level >= 1 && rcx::cplbwd_applicable(N, C, L.h[0], L.w[0], level, k, dtype)) return {BWD_ONE, 0, L.h[0] == 14 && rcx::cplbwd_split(N, C)};
+    const int m = level >= 3 && L.h[level - 2] == 14 && L.w[level - 2] == 14 && rcx::cplbwd_applicable(N, C, 14, 14, 2, k, RCX_DTYPE_F32) ? level - 2 : 0;
+    bool tiled = m > 0;       // ... and every plane above the tail 56x56 or 28x28
+    for (int l = 0; l < m; ++l)
+        tiled = tiled && rcx::bwd_cpt_applicable(N, C, L.h[l], L.w[l], k) && L.h[l + 1] * 2 == L.h[l] && L.w[l + 1] * 2 == L.w[l];
+    return {tiled ? BWD_TILED : BWD_STEPS, m, m > 0 && rcx::cplbwd_split(N, C)};
+}
+
+// One rcx_recconv2d_bwd call and the weight-gradient jobs its partial buffers join (job 0 = the shared down conv, job 1 + j = convs[j])
+struct BwdRun {
+    const TrainLadder& L;
+    const void *x, *gy;
+    void* gx;
+    const float *wpack, *wflip;
+    const char* saved;
+    char* ws;
+    int gy_dt, N, C, level, k, mode, dtype;
+    hipStream_t s;
+    rcx::WgradJobs J;
+    int slot;
+    const float* Wd(int i) const { return wpack + (size_t)i * k * k * C; }       // 0 = down, 1 + j = convs[j]
+    const float* Wf(int i) const { return wflip + (size_t)i * k * k * C; }
+    const float* F(int l) const { return (const float*)(saved + L.f_off[l]); }
+    const float* Cs(int l) const { return (const float*)(saved + L.c_off[l]); }
+    float* G(int l) const { return (float*)(ws + L.g_off[l]); }
+    float* next_part() { return (float*)(ws + L.part_off + (size_t)slot++ * L.part_bytes); }
+    void add(int job, const float* p, int rows) { J.part[job][J.nslots[job]] = p; J.rows[job][J.nslots[job]] = rows; ++J.nslots[job]; }
+};
+
+#define RCX_TRY(call, what) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, what); } while (0)
+
+// the one-launch backward of the whole block (m = 0) or of its tail (x = F_m, g = dL/dC_m, gx = G_m): a partial row per image for jobs 0 .. level + 1
+hipError_t one_launch(BwdRun& B, const void* x, const void* g, int g_dt, void* gx, int m, int H, int level, int dtype)
+{
+    float* parts[RCX_MAX_LEVEL + 2];
+    for (int j = 0; j < level + 2; ++j) { parts[j] = B.next_part(); B.add(j, parts[j], B.N); }
+    return rcx::cplbwd_recconv(x, g, B.wpack, B.wflip, B.saved, B.L.f_off + m, B.L.c_off + m, gx, parts, B.N, B.C, H, level,
+                               B.mode == RCX_MODE_NEAREST ? 1 : 0, dtype, B.s, g_dt);
+}
+
+// BWD_TILED.  Top-down: gW_j from (a_l, C_{l+1}, g_l) and gC_{l+1} = R^T K^ g_l; the tail returns G_m; bottom-up: gW_d from (a_l, G_{l+1}) and
+// G_l = K^ g_l + D^T G_{l+1} (G_0 = gx).  g_0 = gy in its own type, g_l = gC_l float32 (parked in the full-resolution slot G(0) the per-step
+// schedule keeps gT_0 in: no gT plane exists here).
+int bwd_tiled(BwdRun& B, int m)
+{
+    const TrainLadder& L = B.L;
+    const int N = B.N, C = B.C, md = B.mode == RCX_MODE_NEAREST ? 1 : 0;
+    float* gcl[RCX_MAX_LEVEL + 1] = {};
+    size_t off = 0;
+    for (int l = 1; l <= m; ++l) { gcl[l] = (float*)(B.ws + L.g_off[0] + off); off += align256(sizeof(float) * (size_t)N * C * L.h[l] * L.w[l]); }
+    auto g_of = [&](int l) { return l == 0 ? B.gy : (const void*)gcl[l]; };
+    auto gdt_of = [&](int l) { return l == 0 ? B.gy_dt : RCX_DTYPE_F32; };
+    auto a_of = [&](int l) { return l == 0 ? B.x : (const void*)B.F(l); };
+    auto adt_of = [&](int l) { return l == 0 ? B.dtype : RCX_DTYPE_F32; };
+    int rows = 0;
+    // (Round 6 measured the four weight-gradient kernels on a second stream, forked and joined by events inside the call -- nothing but the final
+    // reduction waits for them, and the chain's middle runs on a fraction of the chip: the event hand-offs cost more than the overlap returns,
+    // 342 vs 301 us at 128 x 64 x 56 x 56, 301 vs 220 us at 256 x 128 x 28 x 28, equal at 256 x 64 x 56 x 56; profiles/r06_backward_side_stream.txt.)
+    for (int l = 0; l < m; ++l) {
+        const int j = B.level - l;                              // convs[j] is level l's conv
+        float* p = B.next_part();
+        RCX_TRY(rcx::bwd_wgrad_k_cpt(a_of(l), adt_of(l), B.Cs(l + 1), g_of(l), gdt_of(l), p, N, C, L.h[l], md, B.s, &rows), "bwd: conv weight grad");
+        B.add(1 + j, p, rows);
+        RCX_TRY(rcx::bwd_gc_cpt(g_of(l), gdt_of(l), gcl[l + 1], B.Wf(1 + j), N, C, L.h[l], md, B.s), "bwd: gradient handed down");
+    }
+    RCX_TRY(one_launch(B, B.F(m), gcl[m], RCX_DTYPE_F32, B.G(m), m, 14, 2, RCX_DTYPE_F32), "bwd: fused nested block");
+    for (int l = m - 1; l >= 0; --l) {
+        float* p = B.next_part();
+        RCX_TRY(rcx::bwd_wgrad_d_cpt(a_of(l), adt_of(l), B.G(l + 1), p, N, C, L.h[l], B.s, &rows), "bwd: down weight grad");
+        B.add(0, p, rows);
+        RCX_TRY(rcx::bwd_gx_cpt(g_of(l), gdt_of(l), B.G(l + 1), l == 0 ? B.gx : (void*)B.G(l), l == 0 ? B.dtype : RCX_DTYPE_F32, B.Wf(1 + B.level - l),
+                                B.Wd(0), N, C, L.h[l], B.s), "bwd: gradient handed up");
+    }
+    return 0;
+}
+
+// BWD_STEPS: the per-step forward read backwards, float32 throughout, down to the tail (m > 0)
+int bwd_steps(BwdRun& B, int m)
+{
+    const TrainLadder& L = B.L;
+    const int N = B.N, C = B.C, H = L.h[0], W = L.w[0], level = B.level, k = B.k, mode = B.mode, dtype = B.dtype;
+    float* gC = (float*)(B.ws + L.gc_off);
+    const float* gyf = (const float*)B.gy;
+    int rows = 0;
+    // final conv (model/recnext.py:34): gT_0 = K_L^T gy (gx itself with no ladder) ; gW_L = <x + R(C_1), gy>
+    RCX_TRY(step_dwconv(gyf, level == 0 ? B.gx : (void*)B.G(0), B.Wf(1 + level), nullptr, N, C, H, W, k, 1, RCX_DTYPE_F32,
+                        level == 0 ? dtype : RCX_DTYPE_F32, B.s), "bwd: final conv input grad");
+    float* p = B.next_part();
+    RCX_TRY(rcx::bwd_wgrad(B.x, dtype, level >= 1 ? B.Cs(1) : nullptr, gyf, p, B.J.gw[1 + level], B.J.gb[1 + level], N, C, H, W,
+                           level >= 1 ? L.h[1] : 0, level >= 1 ? L.w[1] : 0, H, W, k, 1, mode, 0, B.s, &rows), "bwd: final conv weight grad");
+    B.add(1 + level, p, rows);
+    // up recursion (:31-33), finest level first in the backward direction
+    for (int l = 1; l <= level; ++l) {
+        const int j = level - l;
+        RCX_TRY(rcx::bwd_resize(B.G(l - 1), gC, N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], mode, B.s), "bwd: resize adjoint");
+        if (l == m) { RCX_TRY(one_launch(B, B.F(m), gC, RCX_DTYPE_F32, B.G(m), m, 14, 2, RCX_DTYPE_F32), "bwd: fused nested block"); break; }
+        RCX_TRY(step_dwconv(gC, B.G(l), B.Wf(1 + j), nullptr, N, C, L.h[l], L.w[l], k, 1, RCX_DTYPE_F32, RCX_DTYPE_F32, B.s), "bwd: conv input grad");
+        p = B.next_part();
+        RCX_TRY(rcx::bwd_wgrad(B.F(l), RCX_DTYPE_F32, l < level ? B.Cs(l + 1) : nullptr, gC, p, B.J.gw[1 + j], B.J.gb[1 + j], N, C, L.h[l], L.w[l],
+                               l < level ? L.h[l + 1] : 0, l < level ? L.w[l + 1] : 0, L.h[l], L.w[l], k, 1, mode, 0, B.s, &rows), "bwd: conv weight grad");
+        B.add(1 + j, p, rows);
+    }
+    // down ladder (:27-29), coarsest first: the shared weight accumulates over all levels
+    for (int l = m ? m : level; l >= 1; --l) {
+        p = B.next_part();
+        RCX_TRY(rcx::bwd_wgrad(l == 1 ? B.x : (const void*)B.F(l - 1), l == 1 ? dtype : RCX_DTYPE_F32, nullptr, B.G(l), p, B.J.gw[0], B.J.gb[0],
+                               N, C, L.h[l - 1], L.w[l - 1], 0, 0, L.h[l], L.w[l], k, 2, mode, 0, B.s, &rows), "bwd: down weight grad");
+        B.add(0, p, rows);
+        RCX_TRY(rcx::bwd_down_input(B.G(l - 1), B.G(l), l == 1 ? B.gx : (void*)B.G(l - 1), l == 1 ? dtype : RCX_DTYPE_F32, B.Wd(0),
+                                    N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], k, B.s), "bwd: down input grad");
+    }
+    return 0;
+}
+
 }  // namespace
 
 size_t rcx_recconv2d_train_saved_bytes(int N, int C, int H, int W, int level, int k)
@@ -469,74 +602,35 @@ int rcx_recconv2d_fwd_train(const void* x, void* y, const float* wpack, const fl
     if (L.saved_total > 0 && (!saved || saved_bytes < L.saved_total))
         return fail(RCX_ERR_WORKSPACE, "saved-activation buffer too small: need %zu bytes, got %zu", L.saved_total, saved_bytes);
     hipStream_t s = (hipStream_t)stream;
-    // the blocks of RecNeXt at 224x224 (channel-per-lane kernels): the inference kernel itself leaves the pyramid behind --
-    // one launch instead of 2 * level + 1 (RCX_TRAIN_FUSED=0: the per-step schedule, for A/B runs)
-    {
-        const bool fused_ok = !rcx::opt::off(rcx::opt::TRAIN_FUSED) && !rcx::opt::hand_kernels_off();
-        const int md = mode == RCX_MODE_NEAREST ? 1 : 0;
-        if (fused_ok && rcx::cpt_train_applicable(N, C, H, W, level, k, md, dtype)) {
-            hipError_t fe = rcx::cpt_recconv(x, y, wpack, bpack, N, C, H, level, md, dtype, s, (float*)saved, L.f_off, L.c_off);
-            return fe == hipSuccess ? 0 : hip_fail(fe, "train fwd: fused tiled block");
-        }
-        if (fused_ok && rcx::cpl14_applicable(N, C, H, W, level, k, dtype)) {
-            hipError_t fe = rcx::cpl14_recconv(x, y, wpack, bpack, N, C, md, dtype, s, (float*)saved, L.f_off, L.c_off);
-            return fe == hipSuccess ? 0 : hip_fail(fe, "train fwd: fused 14x14 block");
-        }
-        if (fused_ok && rcx::cpl7b_applicable(N, C, H, W, level, k, dtype)) {
-            hipError_t fe = rcx::cpl7b_recconv(x, y, wpack, bpack, N, C, md, dtype, s, (float*)saved, L.f_off, L.c_off);
-            return fe == hipSuccess ? 0 : hip_fail(fe, "train fwd: fused 7x7 block");
-        }
-    }
-    const size_t wsz = (size_t)k * k * C;
-    auto W_ = [&](int i) { return wpack + (size_t)i * wsz; };
-    auto B_ = [&](int i) { return bpack ? bpack + (size_t)i * C : nullptr; };
-    char* ws = (char*)saved;
-    auto F_ = [&](int l) { return (float*)(ws + L.f_off[l]); };
-    auto C_ = [&](int l) { return (float*)(ws + L.c_off[l]); };
-    hipError_t e;
-    for (int l = 1; l <= level; ++l) {
-        e = step_dwconv(l == 1 ? x : (const void*)F_(l - 1), F_(l), W_(0), B_(0), N, C, L.h[l - 1], L.w[l - 1], k, 2,
-                        l == 1 ? dtype : RCX_DTYPE_F32, RCX_DTYPE_F32, s);
-        if (e != hipSuccess) return hip_fail(e, "train fwd: down ladder");
-    }
-    for (int l = level, j = 0; l >= 1; --l, ++j) {
-        e = step_upadd(F_(l), l == level ? nullptr : C_(l + 1), C_(l), W_(1 + j), B_(1 + j), N, C, L.h[l], L.w[l],
-                       l == level ? 0 : L.h[l + 1], l == level ? 0 : L.w[l + 1], k, mode,
-                       RCX_DTYPE_F32, RCX_DTYPE_F32, RCX_DTYPE_F32, s);
-        if (e != hipSuccess) return hip_fail(e, "train fwd: up recursion");
-    }
-    e = step_upadd(x, level >= 1 ? C_(1) : nullptr, y, W_(1 + level), B_(1 + level), N, C, H, W,
-                   level >= 1 ? L.h[1] : 0, level >= 1 ? L.w[1] : 0, k, mode, dtype, RCX_DTYPE_F32, dtype, s);
-    return e == hipSuccess ? 0 : hip_fail(e, "train fwd: final conv");
-}
-
-// A block deeper than level 2 whose level (level - 2) plane is 14x14 -- the 28x28 / level 3 and 56x56 / level 4 blocks of RecNeXt at 224x224 --
-// ends in exactly the 14x14 / level 2 block (input F_m, output C_m, convs[0..2], the shared down conv), whose whole backward is one fused launch:
-// m = level - 2, or 0 where there is no such tail
-static int bwd_tail14(const TrainLadder& L, int N, int C, int level, int k)
-{
-    if (level < 3) return 0;
-    const int m = level - 2;
-    return L.h[m] == 14 && L.w[m] == 14 && !rcx::opt::hand_kernels_off() && rcx::cplbwd_applicable(N, C, 14, 14, 2, k, RCX_DTYPE_F32) ? m : 0;
-}
-
-// the fine levels above the 14 x 14 tail run on the tiled adjoint kernels (rcx_cptbwd.hip) when every one of their planes is 56 x 56 or 28 x 28:
-// the number of such levels (2: the 56 x 56 / level 4 block, 1: 28 x 28 / level 3), 0 = the per-step schedule
-static int bwd_cpt_levels(const TrainLadder& L, int N, int C, int level, int k)
-{
-    const int m = bwd_tail14(L, N, C, level, k);
-    for (int l = 0; l < m; ++l)
-        if (!rcx::bwd_cpt_applicable(N, C, L.h[l], L.w[l], k) || L.h[l + 1] * 2 != L.h[l] || L.w[l + 1] * 2 != L.w[l]) return 0;
-    return m;
+    const int md = mode == RCX_MODE_NEAREST ? 1 : 0;
+    const TrainFwdSchedule sch = train_fwd_schedule(N, C, H, W, level, k, mode, dtype);
+    if (sch == TRAIN_STEPS) return recconv2d_steps(x, y, wpack, bpack, (char*)saved, L.f_off, L.c_off, L.h, L.w, N, C, level, k, mode, dtype, s, "train fwd: ");
+    const hipError_t e = sch == TRAIN_TILED ? rcx::cpt_recconv(x, y, wpack, bpack, N, C, H, level, md, dtype, s, (float*)saved, L.f_off, L.c_off)
+                       : sch == TRAIN_CPL14 ? rcx::cpl14_recconv(x, y, wpack, bpack, N, C, md, dtype, s, (float*)saved, L.f_off, L.c_off)
+                                            : rcx::cpl7b_recconv(x, y, wpack, bpack, N, C, md, dtype, s, (float*)saved, L.f_off, L.c_off);
+    static const char* const what[] = {"train fwd: fused tiled block", "train fwd: fused 14x14 block", "train fwd: fused 7x7 block"};
+    return e == hipSuccess ? 0 : hip_fail(e, what[sch]);
 }
 
 int rcx_recconv2d_bwd_gy_dtype(int N, int C, int H, int W, int level, int k, int dtype)
 {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || level < 0 || level > RCX_MAX_LEVEL || k <= 0 || (k & 1) == 0 || !known_dtype(dtype)) return RCX_DTYPE_F32;
-    // bfloat16 only: with float16 rows on both sides the tiled weight-gradient kernel does not fit its register budget (rcx_cptbwd_kernels.h)
+    // bfloat16 (float16 rows on both sides overflow the tiled weight-gradient kernel's registers), where the one-launch or tiled backward reads it
     if (dtype != RCX_DTYPE_BF16 || C % 4) return RCX_DTYPE_F32;
-    if (level >= 1 && !rcx::opt::hand_kernels_off() && rcx::cplbwd_applicable(N, C, H, W, level, k, dtype)) return dtype;      // the one-launch 14 x 14 / 7 x 7 backward
-    return bwd_cpt_levels(make_train_ladder(N, C, H, W, level, k), N, C, level, k) > 0 ? dtype : RCX_DTYPE_F32;
+    return bwd_schedule(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype).kind != BWD_STEPS ? dtype : RCX_DTYPE_F32;
+}
+
+const char* rcx_recconv2d_bwd_plan(int N, int C, int H, int W, int level, int k, int dtype)
+{
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || level < 0 || level > RCX_MAX_LEVEL || k <= 0 || (k & 1) == 0 || !known_dtype(dtype)) return "invalid";
+    if (rcx::opt::hand_kernels_off()) return "generic";
+    static thread_local char desc[64];
+    const BwdSchedule b = bwd_schedule(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype);
+    const char* one14 = b.split ? "one(k_recconv_bwd_cpl14,split)" : "one(k_recconv_bwd_cpl14)";
+    if (b.kind == BWD_ONE) return H == 14 ? one14 : "one(k_recconv_bwd_cpl7)";
+    if (b.kind == BWD_TILED) snprintf(desc, sizeof(desc), "tiled(levels=%d)+%s", b.m, one14);
+    else if (b.m) snprintf(desc, sizeof(desc), "steps+%s", one14);
+    return b.kind == BWD_STEPS && !b.m ? "steps" : desc;
 }
 
 int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* wpack, const float* wpack_flipped, const void* saved,
@@ -554,138 +648,38 @@ int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* 
     if (level >= 1 && !saved) return fail(RCX_ERR_BAD_ARG, "null saved-activation buffer");
     if (!workspace || workspace_bytes < L.bwd_total)
         return fail(RCX_ERR_WORKSPACE, "backward workspace too small: need %zu bytes, got %zu", L.bwd_total, workspace_bytes);
-    const int mcpt = bwd_cpt_levels(L, N, C, level, k);
-    const bool whole = level >= 1 && !rcx::opt::hand_kernels_off() && rcx::cplbwd_applicable(N, C, H, W, level, k, dtype);
-    if (gy_dtype != RCX_DTYPE_F32 && !((mcpt > 0 || whole) && gy_dtype == dtype && dtype == RCX_DTYPE_BF16))
+    const BwdSchedule sch = bwd_schedule(L, N, C, level, k, dtype);
+    if (gy_dtype != RCX_DTYPE_F32 && !(sch.kind != BWD_STEPS && gy_dtype == dtype && dtype == RCX_DTYPE_BF16))
         return fail(RCX_ERR_UNSUPPORTED, "gy of dtype %d: this problem takes float32 (rcx_recconv2d_bwd_gy_dtype)", gy_dtype);
     if (gw_out)
         for (int i = 0; i < level + 2; ++i)
             if (!gw_out[i]) return fail(RCX_ERR_BAD_ARG, "null gw_out[%d]", i);
     hipStream_t s = (hipStream_t)stream;
-    const size_t wsz = (size_t)k * k * C;
-    auto W_ = [&](int i) { return wpack + (size_t)i * wsz; };
-    auto Wf = [&](int i) { return wpack_flipped + (size_t)i * wsz; };
+    BwdRun B{L};
+    B.x = x; B.gy = gy; B.wpack = wpack; B.wflip = wpack_flipped; B.saved = (const char*)saved; B.ws = (char*)workspace; B.gx = gx;
+    B.gy_dt = gy_dtype; B.N = N; B.C = C; B.level = level; B.k = k; B.mode = mode; B.dtype = dtype; B.s = s;
     // where the final reduction leaves conv i's gradients: the packed float32 rows, or the parameters' own tensors
-    auto GW = [&](int i) { return gw_out ? (float*)gw_out[i] : gwpack + (size_t)i * wsz; };
-    auto GB = [&](int i) { return gw_out ? (gb_out ? (float*)gb_out[i] : nullptr) : (gbpack ? gbpack + (size_t)i * C : nullptr); };
-    const char* sv = (const char*)saved;
-    auto F_ = [&](int l) { return (const float*)(sv + L.f_off[l]); };
-    auto C_ = [&](int l) { return (const float*)(sv + L.c_off[l]); };
-    char* ws = (char*)workspace;
-    auto G_ = [&](int l) { return (float*)(ws + L.g_off[l]); };
-    float* gC = (float*)(ws + L.gc_off);
-    int slot = 0;
-    auto PART = [&](int i) { return (float*)(ws + L.part_off + (size_t)i * L.part_bytes); };
-    rcx::WgradJobs J{};
-    J.kk = k * k; J.C = C;
-    J.param_layout = gw_out ? 1 : 0;
-    J.param_dt = grad_dtype;
-    // job 0 = the shared down conv (its partial buffers are appended as the ladder is walked), job 1 + j = convs[j]
-    J.njobs = level + 2;
-    J.gw[0] = GW(0); J.gb[0] = GB(0); J.nslots[0] = 0;
-    for (int i = 0; i <= level; ++i) { J.gw[1 + i] = GW(1 + i); J.gb[1 + i] = GB(1 + i); J.nslots[1 + i] = 0; }
-    auto add_slot = [&](int job, const float* p, int rows) { J.part[job][J.nslots[job]] = p; J.rows[job][J.nslots[job]] = rows; ++J.nslots[job]; };
-    int rows = 0;
-    hipError_t e;
-#define RCX_TRY(call, what) do { e = (call); if (e != hipSuccess) return hip_fail(e, what); } while (0)
-    // the blocks whose planes fit one lane: the whole backward in one launch + the batch reduction (RCX_BWD_FUSED=0: per-step schedule)
-    if (whole) {
-        float* parts[RCX_MAX_LEVEL + 2];
-        for (int j = 0; j < level + 2; ++j) { parts[j] = PART(j); add_slot(j, PART(j), N); }
-        RCX_TRY(rcx::cplbwd_recconv(x, gy, wpack, wpack_flipped, saved, L.f_off, L.c_off, gx, parts, N, C, H, level,
-                                    mode == RCX_MODE_NEAREST ? 1 : 0, dtype, s, gy_dtype), "bwd: fused block");
-        RCX_TRY(rcx::bwd_wgrad_reduce_jobs(J, s), "bwd: weight-gradient reduction");
-        return 0;
+    rcx::WgradJobs& J = B.J;
+    J.njobs = level + 2; J.kk = k * k; J.C = C; J.param_layout = gw_out ? 1 : 0; J.param_dt = grad_dtype;
+    for (int i = 0; i < level + 2; ++i) {
+        J.gw[i] = gw_out ? (float*)gw_out[i] : gwpack + (size_t)i * k * k * C;
+        J.gb[i] = gw_out ? (gb_out ? (float*)gb_out[i] : nullptr) : (gbpack ? gbpack + (size_t)i * C : nullptr);
     }
-    // The 56x56 / level 4 and 28x28 / level 3 blocks (RecNeXt at 224x224): the fine levels on the tiled adjoint kernels, the 14x14 / level 2 tail as
-    // its one launch.  Top-down: gW_j from (a_l, C_{l+1}, g_l) and gC_{l+1} = R^T K^ g_l; the tail returns G_m; bottom-up: gW_d from (a_l, G_{l+1})
-    // and G_l = K^ g_l + D^T G_{l+1} (G_0 = gx).  g_0 = gy in its own type, g_l = gC_l float32 (parked in the full-resolution slot G_(0) the per-step
-    // schedule keeps gT_0 in: no gT plane exists here).
-    if (mcpt > 0) {
-        const int m = mcpt, md = mode == RCX_MODE_NEAREST ? 1 : 0;
-        float* gcl[RCX_MAX_LEVEL + 1] = {};
-        {
-            size_t off = 0;
-            for (int l = 1; l <= m; ++l) { gcl[l] = (float*)(ws + L.g_off[0] + off); off += align256(sizeof(float) * (size_t)N * C * L.h[l] * L.w[l]); }
-        }
-        auto g_of = [&](int l) { return l == 0 ? gy : (const void*)gcl[l]; };
-        auto gdt_of = [&](int l) { return l == 0 ? gy_dtype : RCX_DTYPE_F32; };
-        auto a_of = [&](int l) { return l == 0 ? x : (const void*)F_(l); };
-        auto adt_of = [&](int l) { return l == 0 ? dtype : RCX_DTYPE_F32; };
-        // (Round 6 measured the four weight-gradient kernels on a second stream, forked and joined by events inside the call -- nothing but the final
-        // reduction waits for them, and the chain's middle runs on a fraction of the chip: the event hand-offs cost more than the overlap returns,
-        // 342 vs 301 us at 128 x 64 x 56 x 56, 301 vs 220 us at 256 x 128 x 28 x 28, equal at 256 x 64 x 56 x 56; profiles/r06_backward_side_stream.txt.)
-        for (int l = 0; l < m; ++l) {
-            const int j = level - l;                              // convs[j] is level l's conv
-            RCX_TRY(rcx::bwd_wgrad_k_cpt(a_of(l), adt_of(l), C_(l + 1), g_of(l), gdt_of(l), PART(slot), N, C, L.h[l], md, s, &rows), "bwd: conv weight grad");
-            add_slot(1 + j, PART(slot++), rows);
-            RCX_TRY(rcx::bwd_gc_cpt(g_of(l), gdt_of(l), gcl[l + 1], Wf(1 + j), N, C, L.h[l], md, s), "bwd: gradient handed down");
-        }
-        {
-            float* parts[4];
-            for (int q = 0; q < 4; ++q) parts[q] = PART(slot++);
-            RCX_TRY(rcx::cplbwd_recconv(F_(m), gcl[m], wpack, wpack_flipped, saved, L.f_off + m, L.c_off + m, G_(m), parts, N, C, 14, 2, md,
-                                        RCX_DTYPE_F32, s), "bwd: fused nested block");
-            for (int q = 0; q < 4; ++q) add_slot(q, parts[q], N);
-        }
-        for (int l = m - 1; l >= 0; --l) {
-            RCX_TRY(rcx::bwd_wgrad_d_cpt(a_of(l), adt_of(l), G_(l + 1), PART(slot), N, C, L.h[l], s, &rows), "bwd: down weight grad");
-            add_slot(0, PART(slot++), rows);
-            RCX_TRY(rcx::bwd_gx_cpt(g_of(l), gdt_of(l), G_(l + 1), l == 0 ? gx : (void*)G_(l), l == 0 ? dtype : RCX_DTYPE_F32, Wf(1 + level - l), W_(0),
-                                    N, C, L.h[l], s), "bwd: gradient handed up");
-        }
-        RCX_TRY(rcx::bwd_wgrad_reduce_jobs(J, s), "bwd: weight-gradient reduction");
-        return 0;
-    }
-    const float* gyf = (const float*)gy;                          // the per-step schedule reads float32
-    // final conv (model/recnext.py:34): gT_0 = K_L^T gy ; gW_L = <x + R(C_1), gy>
-    if (level == 0) RCX_TRY(step_dwconv(gyf, gx, Wf(1), nullptr, N, C, H, W, k, 1, RCX_DTYPE_F32, dtype, s), "bwd: final conv input grad");
-    else RCX_TRY(step_dwconv(gyf, G_(0), Wf(1 + level), nullptr, N, C, H, W, k, 1, RCX_DTYPE_F32, RCX_DTYPE_F32, s), "bwd: final conv input grad");
-    RCX_TRY(rcx::bwd_wgrad(x, dtype, level >= 1 ? C_(1) : nullptr, gyf, PART(slot), GW(1 + level), GB(1 + level), N, C, H, W,
-                           level >= 1 ? L.h[1] : 0, level >= 1 ? L.w[1] : 0, H, W, k, 1, mode, 0, s, &rows), "bwd: final conv weight grad");
-    add_slot(1 + level, PART(slot++), rows);
-    // the 14x14 / level 2 tail (bwd_tail14) as its one launch, the levels above it on the per-step kernels
-    const int m = bwd_tail14(L, N, C, level, k);
-    // up recursion (:31-33), finest level first in the backward direction
-    for (int l = 1; l <= level; ++l) {
-        const int j = level - l;
-        RCX_TRY(rcx::bwd_resize(G_(l - 1), gC, N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], mode, s), "bwd: resize adjoint");
-        if (m && l == m) {
-            float* parts[4];
-            for (int q = 0; q < 4; ++q) parts[q] = PART(slot++);
-            RCX_TRY(rcx::cplbwd_recconv(F_(m), gC, wpack, wpack_flipped, saved, L.f_off + m, L.c_off + m, G_(m), parts, N, C, 14, 2,
-                                        mode == RCX_MODE_NEAREST ? 1 : 0, RCX_DTYPE_F32, s), "bwd: fused nested block");
-            for (int q = 0; q < 4; ++q) add_slot(q, parts[q], N);
-            break;
-        }
-        RCX_TRY(step_dwconv(gC, G_(l), Wf(1 + j), nullptr, N, C, L.h[l], L.w[l], k, 1, RCX_DTYPE_F32, RCX_DTYPE_F32, s), "bwd: conv input grad");
-        RCX_TRY(rcx::bwd_wgrad(F_(l), RCX_DTYPE_F32, l < level ? C_(l + 1) : nullptr, gC, PART(slot), GW(1 + j), GB(1 + j), N, C, L.h[l], L.w[l],
-                               l < level ? L.h[l + 1] : 0, l < level ? L.w[l + 1] : 0, L.h[l], L.w[l], k, 1, mode, 0, s, &rows), "bwd: conv weight grad");
-        add_slot(1 + j, PART(slot++), rows);
-    }
-    // down ladder (:27-29), coarsest first: the shared weight accumulates over all levels
-    for (int l = m ? m : level; l >= 1; --l) {
-        RCX_TRY(rcx::bwd_wgrad(l == 1 ? x : (const void*)F_(l - 1), l == 1 ? dtype : RCX_DTYPE_F32, nullptr, G_(l), PART(slot), GW(0), GB(0),
-                               N, C, L.h[l - 1], L.w[l - 1], 0, 0, L.h[l], L.w[l], k, 2, mode, 0, s, &rows), "bwd: down weight grad");
-        add_slot(0, PART(slot++), rows);
-        RCX_TRY(rcx::bwd_down_input(G_(l - 1), G_(l), l == 1 ? gx : (void*)G_(l - 1), l == 1 ? dtype : RCX_DTYPE_F32, W_(0),
-                                    N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], k, s), "bwd: down input grad");
-    }
-    // every weight gradient of the block in one reduction launch (job 0 sums the down conv's levels, coarsest first); with no ladder
-    // job 0 has no buffer and writes zeros -- replaced by the memset below
-    if (level == 0) { J.njobs = 1; J.gw[0] = GW(1); J.gb[0] = GB(1); J.nslots[0] = J.nslots[1]; J.part[0][0] = J.part[1][0]; J.rows[0][0] = J.rows[1][0]; }
+    if (sch.kind == BWD_ONE) RCX_TRY(one_launch(B, x, gy, gy_dtype, gx, 0, H, level, dtype), "bwd: fused block");
+    else if (int rc = sch.kind == BWD_TILED ? bwd_tiled(B, sch.m) : bwd_steps(B, sch.m)) return rc;
+    // every weight gradient of the block in one reduction launch (job 0 sums the down conv's levels, coarsest first).  With no ladder the shared
+    // down weight is unused: conv 0 is reduced alone, and the down gradient zeroed.
+    float* const gw0 = J.gw[0], * const gb0 = J.gb[0];
+    if (level == 0) { J.njobs = 1; J.gw[0] = J.gw[1]; J.gb[0] = J.gb[1]; J.nslots[0] = J.nslots[1]; J.part[0][0] = J.part[1][0]; J.rows[0][0] = J.rows[1][0]; }
     RCX_TRY(rcx::bwd_wgrad_reduce_jobs(J, s), "bwd: weight-gradient reduction");
-#undef RCX_TRY
-    if (level == 0) {   // no ladder: the shared down weight is unused, its gradient is zero
-        const size_t esz = gw_out ? (grad_dtype == RCX_DTYPE_F32 ? 4 : 2) : 4;
-        float* gw0 = gw_out ? (float*)gw_out[0] : gwpack;
-        float* gb0 = gw_out ? (gb_out ? (float*)gb_out[0] : nullptr) : gbpack;
-        e = hipMemsetAsync(gw0, 0, esz * wsz, s);
-        if (e == hipSuccess && gb0) e = hipMemsetAsync(gb0, 0, esz * C, s);
-        if (e != hipSuccess) return hip_fail(e, "bwd: zero down grad");
-    }
-    return 0;
+    if (level >= 1) return 0;
+    const size_t esz = gw_out && grad_dtype != RCX_DTYPE_F32 ? 2 : 4;
+    hipError_t e = hipMemsetAsync(gw0, 0, esz * k * k * C, s);
+    if (e == hipSuccess && gb0) e = hipMemsetAsync(gb0, 0, esz * C, s);
+    return e == hipSuccess ? 0 : hip_fail(e, "bwd: zero down grad");
 }
+
+#undef RCX_TRY
 
 int rcx_dwconv2d_fwd(const void* x, void* y, const float* w_kkc, const float* bias,
                      int N, int C, int H, int W, int k, int stride, int in_dtype, int out_dtype, void* stream)
@@ -749,6 +743,47 @@ int rcx_upadd_dwconv_fwd(const void* x, const void* coarse, void* y, const float
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_upadd_dwconv_fwd");
 }
 
+// ---- backward of the depthwise convs of RecAttn2d and Downsample ----
+namespace {
+
+// the argument checks the three entries below share (check_common's counterpart); c_mult: the channel multiple their kernels need
+int check_dw_bwd(const char* who, bool have_ptrs, int N, int C, int H, int W, int dtype, int c_mult)
+{
+    if (!have_ptrs) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", who);
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(RCX_ERR_BAD_ARG, "non-positive extent N=%d C=%d H=%d W=%d", N, C, H, W);
+    if (!known_dtype(dtype)) return fail(RCX_ERR_BAD_ARG, "unknown dtype %d", dtype);
+    if (C % c_mult) return fail(RCX_ERR_UNSUPPORTED, "%s: the backward kernels need C %% %d == 0, got C=%d", who, c_mult, C);
+    return 0;
+}
+
+// gw / gb = the sum of the `rows` partial rows one tiled kernel left in `part`
+hipError_t reduce_one(const float* part, int rows, float* gw, float* gb, int k, int C, hipStream_t s)
+{
+    rcx::WgradJobs J{};
+    J.njobs = 1; J.kk = k * k; J.C = C;
+    J.nslots[0] = 1; J.part[0][0] = part; J.rows[0][0] = rows; J.gw[0] = gw; J.gb[0] = gb;
+    return rcx::bwd_wgrad_reduce_jobs(J, s);
+}
+
+// rcx_dwconv2d_bwd: the stride-2 conv5 on the 56 x 56 / 28 x 28 planes (RecAttn2d's `down` conv) takes the tiled adjoint kernels of
+// rcx_recconv2d_bwd (round 6) for its input gradient ...
+bool dw_bwd_tiled_gx(int N, int C, int H, int W, int k, int stride)
+{
+    return stride == 2 && !rcx::opt::hand_kernels_off() && rcx::bwd_cpt_applicable(N, C, H, W, k) && down_size(H, k) * 2 == H && down_size(W, k) * 2 == W;
+}
+
+// ... and for its weight gradient while the tiled kernel's N * H / 14 partial rows fit the workspace: rcx_dwconv2d_bwd_workspace_bytes takes no N
+// and holds 512 rows (wgrad_partial_bytes), so a larger batch reduces on the generic kernel
+bool dw_bwd_tiled_gw(int N, int C, int H, int W, int k, int stride) { return dw_bwd_tiled_gx(N, C, H, W, k, stride) && N * (H / 14) <= 512; }
+
+// backward of conv(x + resize(coarse)) (RecAttn2d's last line in a training step): the tiled adjoint kernels on the 56 x 56 / 28 x 28 planes
+bool upadd_bwd_tiled(int N, int C, int H, int W, int Hc, int Wc, int k)
+{
+    return !rcx::opt::hand_kernels_off() && rcx::bwd_cpt_applicable(N, C, H, W, k) && Hc * 2 == H && Wc * 2 == W;
+}
+
+}  // namespace
+
 size_t rcx_dwconv2d_bwd_workspace_bytes(int C, int k)
 {
     if (C <= 0 || k <= 0 || (k & 1) == 0) return 0;
@@ -759,12 +794,9 @@ int rcx_dwconv2d_bwd(const void* x, const float* gy, const float* w_kkc, const f
                      void* gx, float* gw, float* gb, void* workspace, size_t workspace_bytes,
                      int N, int C, int H, int W, int k, int stride, int x_dtype, void* stream)
 {
-    if (!x || !gy || !gw) return fail(RCX_ERR_BAD_ARG, "rcx_dwconv2d_bwd: null pointer");
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(RCX_ERR_BAD_ARG, "non-positive extent N=%d C=%d H=%d W=%d", N, C, H, W);
     if (k <= 0 || (k & 1) == 0) return fail(RCX_ERR_BAD_ARG, "kernel_size must be odd and positive, got %d", k);
-    if (!known_dtype(x_dtype)) return fail(RCX_ERR_BAD_ARG, "unknown dtype %d", x_dtype);
+    if (int rc = check_dw_bwd("rcx_dwconv2d_bwd", x && gy && gw, N, C, H, W, x_dtype, 4)) return rc;
     if (stride != 1 && stride != 2) return fail(RCX_ERR_UNSUPPORTED, "stride %d not supported (1 or 2)", stride);
-    if (C % 4) return fail(RCX_ERR_UNSUPPORTED, "the backward kernels need C %% 4 == 0, got C=%d", C);
     if (gx && (!w_kkc || !w_flipped_kkc)) return fail(RCX_ERR_BAD_ARG, "rcx_dwconv2d_bwd: weights are needed for the input gradient");
     const size_t need = rcx_dwconv2d_bwd_workspace_bytes(C, k);
     if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
@@ -772,40 +804,24 @@ int rcx_dwconv2d_bwd(const void* x, const float* gy, const float* w_kkc, const f
     const int p = k / 2, Ho = (H + 2 * p - k) / stride + 1, Wo = (W + 2 * p - k) / stride + 1;
     hipError_t e;
     if (gx) {
-        // the stride-2 conv5 on the 56 x 56 / 28 x 28 planes (RecAttn2d's `down` conv): the tiled adjoint kernels of rcx_recconv2d_bwd (round 6)
-        const bool tiled = stride == 2 && !rcx::opt::hand_kernels_off() && rcx::bwd_cpt_applicable(N, C, H, W, k) && Ho * 2 == H && Wo * 2 == W;
         if (stride == 1) e = step_dwconv(gy, gx, w_flipped_kkc, nullptr, N, C, H, W, k, 1, RCX_DTYPE_F32, x_dtype, s);
-        else if (tiled) e = rcx::bwd_dT_cpt(gy, gx, x_dtype, w_kkc, N, C, H, s);
+        else if (dw_bwd_tiled_gx(N, C, H, W, k, stride)) e = rcx::bwd_dT_cpt(gy, gx, x_dtype, w_kkc, N, C, H, s);
         else e = rcx::bwd_down_input(nullptr, gy, gx, x_dtype, w_kkc, N, C, H, W, Ho, Wo, k, s);
         if (e != hipSuccess) return hip_fail(e, "rcx_dwconv2d_bwd: input gradient");
     }
-    if (stride == 2 && !rcx::opt::hand_kernels_off() && rcx::bwd_cpt_applicable(N, C, H, W, k) && Ho * 2 == H && Wo * 2 == W && N * (H / 14) <= 512) {      // 512 partial rows: the workspace above
-        int rows = 0;
-        e = rcx::bwd_wgrad_d_cpt(x, x_dtype, gy, (float*)workspace, N, C, H, s, &rows);
-        if (e == hipSuccess) {
-            rcx::WgradJobs J{};
-            J.njobs = 1; J.kk = k * k; J.C = C;
-            J.nslots[0] = 1; J.part[0][0] = (const float*)workspace; J.rows[0][0] = rows; J.gw[0] = gw; J.gb[0] = gb;
-            e = rcx::bwd_wgrad_reduce_jobs(J, s);
-        }
-        return e == hipSuccess ? 0 : hip_fail(e, "rcx_dwconv2d_bwd: weight gradient");
-    }
-    e = rcx::bwd_wgrad(x, x_dtype, nullptr, gy, (float*)workspace, gw, gb, N, C, H, W, 0, 0, Ho, Wo, k, stride, 0, 0, s);
+    int rows = 0;
+    if (!dw_bwd_tiled_gw(N, C, H, W, k, stride))
+        e = rcx::bwd_wgrad(x, x_dtype, nullptr, gy, (float*)workspace, gw, gb, N, C, H, W, 0, 0, Ho, Wo, k, stride, 0, 0, s);
+    else if ((e = rcx::bwd_wgrad_d_cpt(x, x_dtype, gy, (float*)workspace, N, C, H, s, &rows)) == hipSuccess)
+        e = reduce_one((const float*)workspace, rows, gw, gb, k, C, s);
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_dwconv2d_bwd: weight gradient");
-}
-
-// ---- backward of conv(x + resize(coarse)) (RecAttn2d's last line in a training step) ----
-static bool upadd_bwd_tiled(int N, int C, int H, int W, int Hc, int Wc, int k)
-{
-    return !rcx::opt::hand_kernels_off() && rcx::bwd_cpt_applicable(N, C, H, W, k) && Hc * 2 == H && Wc * 2 == W;
 }
 
 size_t rcx_upadd_dwconv_bwd_workspace_bytes(int N, int C, int H, int W, int Hc, int Wc, int k)
 {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || k <= 0 || (k & 1) == 0) return 0;
-    const size_t part = align256(rcx::wgrad_partial_bytes(C, k));
     if (upadd_bwd_tiled(N, C, H, W, Hc, Wc, k)) return align256(sizeof(float) * (size_t)N * ((H + 13) / 14) * (size_t)(k * k + 1) * C);      // one partial row per (image, band)
-    return part + align256(sizeof(float) * (size_t)N * C * H * W);      // + the float32 gT the resize adjoint reads
+    return align256(rcx::wgrad_partial_bytes(C, k)) + align256(sizeof(float) * (size_t)N * C * H * W);      // + the float32 gT the resize adjoint reads
 }
 
 int rcx_upadd_dwconv_bwd_gy_dtype(int N, int C, int H, int W, int Hc, int Wc, int k, int dtype)
@@ -818,12 +834,11 @@ int rcx_upadd_dwconv_bwd(const void* x, const float* coarse, const void* gy, int
                          void* gx, float* gcoarse, float* gw, float* gb, void* workspace, size_t workspace_bytes,
                          int N, int C, int H, int W, int Hc, int Wc, int k, int mode, int dtype, void* stream)
 {
-    if (!x || !coarse || !gy || !gw || !w_flipped_kkc) return fail(RCX_ERR_BAD_ARG, "rcx_upadd_dwconv_bwd: null pointer");
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || Hc <= 0 || Wc <= 0) return fail(RCX_ERR_BAD_ARG, "non-positive extent N=%d C=%d H=%d W=%d Hc=%d Wc=%d", N, C, H, W, Hc, Wc);
+    if (Hc <= 0 || Wc <= 0) return fail(RCX_ERR_BAD_ARG, "non-positive coarse extent %dx%d", Hc, Wc);
     if (k <= 0 || (k & 1) == 0) return fail(RCX_ERR_BAD_ARG, "kernel_size must be odd and positive, got %d", k);
-    if (!known_dtype(dtype) || !known_dtype(gy_dtype)) return fail(RCX_ERR_BAD_ARG, "unknown dtype %d / %d", dtype, gy_dtype);
+    if (!known_dtype(gy_dtype)) return fail(RCX_ERR_BAD_ARG, "unknown dtype %d", gy_dtype);
     if (mode != RCX_MODE_BILINEAR && mode != RCX_MODE_NEAREST) return fail(RCX_ERR_BAD_ARG, "unknown mode %d", mode);
-    if (C % 4) return fail(RCX_ERR_UNSUPPORTED, "the backward kernels need C %% 4 == 0, got C=%d", C);
+    if (int rc = check_dw_bwd("rcx_upadd_dwconv_bwd", x && coarse && gy && gw && w_flipped_kkc, N, C, H, W, dtype, 4)) return rc;
     const size_t need = rcx_upadd_dwconv_bwd_workspace_bytes(N, C, H, W, Hc, Wc, k);
     if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     const bool tiled = upadd_bwd_tiled(N, C, H, W, Hc, Wc, k);
@@ -844,12 +859,7 @@ int rcx_upadd_dwconv_bwd(const void* x, const float* coarse, const void* gy, int
         }
         int rows = 0;
         e = rcx::bwd_wgrad_k_cpt(x, dtype, coarse, gy, gy_dtype, part, N, C, H, md, s, &rows);
-        if (e == hipSuccess) {
-            rcx::WgradJobs J{};
-            J.njobs = 1; J.kk = k * k; J.C = C;
-            J.nslots[0] = 1; J.part[0][0] = part; J.rows[0][0] = rows; J.gw[0] = gw; J.gb[0] = gb;
-            e = rcx::bwd_wgrad_reduce_jobs(J, s);
-        }
+        if (e == hipSuccess) e = reduce_one(part, rows, gw, gb, k, C, s);
         return e == hipSuccess ? 0 : hip_fail(e, "rcx_upadd_dwconv_bwd: weight gradient");
     }
     const float* gyf = (const float*)gy;
@@ -871,11 +881,8 @@ int rcx_upadd_dwconv_bwd(const void* x, const float* coarse, const void* gy, int
 int rcx_dwconv2d_mult2_bwd(const void* x, const float* gy, const float* w_kkc, void* gx, float* gw, float* gb,
                            void* workspace, size_t workspace_bytes, int N, int Cin, int H, int W, int k, int dtype, void* stream)
 {
-    if (!x || !gy || !gw) return fail(RCX_ERR_BAD_ARG, "rcx_dwconv2d_mult2_bwd: null pointer");
-    if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0) return fail(RCX_ERR_BAD_ARG, "non-positive extent N=%d C=%d H=%d W=%d", N, Cin, H, W);
-    if (!known_dtype(dtype)) return fail(RCX_ERR_BAD_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_dw_bwd("rcx_dwconv2d_mult2_bwd", x && gy && gw, N, Cin, H, W, dtype, 2)) return rc;
     if (k != 3 && k != 5 && k != 7) return fail(RCX_ERR_UNSUPPORTED, "kernel_size %d not supported by the multiplier-2 backward (3, 5, 7)", k);
-    if (Cin % 2) return fail(RCX_ERR_UNSUPPORTED, "the multiplier-2 backward needs an even channel count, got %d", Cin);
     if (gx && !w_kkc) return fail(RCX_ERR_BAD_ARG, "rcx_dwconv2d_mult2_bwd: weights are needed for the input gradient");
     const size_t need = rcx_dwconv2d_bwd_workspace_bytes(2 * Cin, k);
     if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);

@@ -571,6 +571,10 @@ k_wgrad_reduce(const float* __restrict__ partial, float* __restrict__ gw, float*
 }
 
 // ---------------- host side ----------------
+// f(T{}) with T the element type of dtype id dt: 1 bfloat16, 2 float16, else float32
+template <typename F>
+static void with_type(int dt, F&& f) { if (dt == 1) f(bf16_t{}); else if (dt == 2) f(f16_t{}); else f(float{}); }
+
 static unsigned grid_for(long long total)
 {
     long long b = (total + 255) / 256;
@@ -596,6 +600,14 @@ size_t wgrad_partial_bytes(int C, int k)
     return old > fast ? old : fast;
 }
 
+// gw / gb (+)= the sum of `rows` partial rows of (k * k + 1) * C, in row order
+static hipError_t wgrad_reduce8(const float* partial, float* gw, float* gb, int rows, int k, int C, int accumulate, hipStream_t s)
+{
+    const int kk = k * k, n = (kk + 1) * C;
+    hipLaunchKernelGGL(k_wgrad_reduce8, dim3((n + 31) / 32), dim3(32, 8), 0, s, partial, gw, gb, rows, kk, C, accumulate);
+    return hipGetLastError();
+}
+
 template <typename TA>
 static hipError_t wgrad_launch(const void* a, const float* coarse, const float* g, float* partial, float* gw, float* gb,
                                BwGeom q, int Ho, int Wo, int stride, int accumulate, hipStream_t s, int* rows_out)
@@ -614,9 +626,7 @@ static hipError_t wgrad_launch(const void* a, const float* coarse, const float* 
         hipError_t e5 = hipGetLastError();
         if (e5 != hipSuccess) return e5;
         if (rows_out) { *rows_out = gy; return hipSuccess; }          // the caller reduces all its partial buffers in one launch
-        const int kk = q.k * q.k, n5 = (kk + 1) * q.C;
-        hipLaunchKernelGGL(k_wgrad_reduce8, dim3((n5 + 31) / 32), dim3(32, 8), 0, s, partial, gw, gb, gy, kk, q.C, accumulate);
-        return hipGetLastError();
+        return wgrad_reduce8(partial, gw, gb, gy, q.k, q.C, accumulate, s);
     }
     const int cvecs = q.C / BW_V;
     dim3 block(32, WG_ROWS_Y), grid((cvecs + 31) / 32, WG_BLOCKS_Y);
@@ -636,27 +646,23 @@ hipError_t bwd_wgrad(const void* a, int a_dt, const float* coarse, const float* 
                      int* rows_out, int g_dt)
 {
     // the 56x56 / 28x28 convs over T = a + R(coarse): tiled channel-per-lane kernel (rcx_cplwgrad.hip), when the caller reduces itself
-    {
-        const bool t1 = Ho == H && Wo == W && wgrad_cpl_applicable(N, C, H, W, Hc, Wc, k, stride, coarse != nullptr);
-        const bool t2 = !t1 && wgrad2_cpl_applicable(N, C, H, W, Ho, Wo, k, stride, coarse != nullptr);
-        if (g_dt != 0 && !t1) return hipErrorInvalidValue;
-        if (t1 || t2) {
-            int rows = 0;
-            hipError_t e = t1 ? wgrad_cpl(a, a_dt, coarse, g, g_dt, partial, N, C, H, mode, s, &rows) : wgrad2_cpl(a, a_dt, g, partial, N, C, H, s, &rows);
-            if (e != hipSuccess) return e;
-            if (rows_out) { *rows_out = rows; return hipSuccess; }        // the caller reduces all its partial buffers in one launch
-            const int kk = k * k, n5 = (kk + 1) * C;
-            hipLaunchKernelGGL(k_wgrad_reduce8, dim3((n5 + 31) / 32), dim3(32, 8), 0, s, partial, gw, gb, rows, kk, C, accumulate);
-            return hipGetLastError();
-        }
+    const bool t1 = Ho == H && Wo == W && wgrad_cpl_applicable(N, C, H, W, Hc, Wc, k, stride, coarse != nullptr);
+    const bool t2 = !t1 && wgrad2_cpl_applicable(N, C, H, W, Ho, Wo, k, stride, coarse != nullptr);
+    if (g_dt != 0 && !t1) return hipErrorInvalidValue;
+    if (t1 || t2) {
+        int rows = 0;
+        hipError_t e = t1 ? wgrad_cpl(a, a_dt, coarse, g, g_dt, partial, N, C, H, mode, s, &rows) : wgrad2_cpl(a, a_dt, g, partial, N, C, H, s, &rows);
+        if (e != hipSuccess) return e;
+        if (rows_out) { *rows_out = rows; return hipSuccess; }        // the caller reduces all its partial buffers in one launch
+        return wgrad_reduce8(partial, gw, gb, rows, k, C, accumulate, s);
     }
     BwGeom q{};
     q.N = N; q.C = C; q.H = H; q.W = W; q.Hc = Hc; q.Wc = Wc; q.k = k; q.mode = mode;
     q.sy = Hc > 0 ? (float)Hc / (float)H : 0.f;
     q.sx = Wc > 0 ? (float)Wc / (float)W : 0.f;
-    if (a_dt == 1) return wgrad_launch<bf16_t>(a, coarse, g, partial, gw, gb, q, Ho, Wo, stride, accumulate, s, rows_out);
-    if (a_dt == 2) return wgrad_launch<f16_t>(a, coarse, g, partial, gw, gb, q, Ho, Wo, stride, accumulate, s, rows_out);
-    return wgrad_launch<float>(a, coarse, g, partial, gw, gb, q, Ho, Wo, stride, accumulate, s, rows_out);
+    hipError_t e = hipSuccess;
+    with_type(a_dt, [&](auto t) { e = wgrad_launch<decltype(t)>(a, coarse, g, partial, gw, gb, q, Ho, Wo, stride, accumulate, s, rows_out); });
+    return e;
 }
 
 hipError_t bwd_wgrad_reduce_jobs(const WgradJobs& J, hipStream_t s)
@@ -666,7 +672,18 @@ hipError_t bwd_wgrad_reduce_jobs(const WgradJobs& J, hipStream_t s)
     return hipGetLastError();
 }
 
-// Downsample conv (channel multiplier 2, stride 2): input gradient and weight/bias gradients; Cin % 2 == 0
+// Downsample conv (channel multiplier 2, stride 2): which kernel takes the input gradient, and which the weight gradient.  RecNeXt's three
+// Downsample convs at 224 x 224 take the tile kernels (rcx_cptbwd_kernels.h), the first two the tiled kernel (rcx_cplwgrad.hip) above 512 tile rows.
+enum Mult2Gx { M2GX_TILE, M2GX_K7, M2GX_ANY };
+enum Mult2Gw { M2GW_TILE, M2GW_CPL, M2GW_ROWS };
+
+static Mult2Gx pick_mult2_gx(int N, int Cin, int H, int W, int k) { return bwd_down7m2_cpt_applicable(N, Cin, H, W, k) ? M2GX_TILE : k == 7 ? M2GX_K7 : M2GX_ANY; }
+static Mult2Gw pick_mult2_gw(int N, int Cout, int H, int W, int k)
+{
+    return bwd_wgrad_dm_cpt_applicable(N, Cout, H, W, k) ? M2GW_TILE : wgrad2m_cpl_applicable(N, Cout, H, W, k) ? M2GW_CPL : M2GW_ROWS;
+}
+
+// input gradient and weight/bias gradients; Cin % 2 == 0
 hipError_t bwd_mult2(const void* x, int x_dt, const float* g, const float* w, void* gx, float* partial, float* gw, float* gb,
                      int N, int Cin, int H, int W, int k, hipStream_t s)
 {
@@ -674,54 +691,38 @@ hipError_t bwd_mult2(const void* x, int x_dt, const float* g, const float* w, vo
     const int p = k / 2, Ho = (H + 2 * p - k) / 2 + 1, Wo = (W + 2 * p - k) / 2 + 1;
     BwGeom q{};
     q.N = N; q.C = Cin; q.H = H; q.W = W; q.Hc = Ho; q.Wc = Wo; q.k = k;
+    hipError_t e = hipSuccess;
     if (gx) {
-        const unsigned grid = grid_for((long long)N * H * W * (Cin / 2));
-        if (bwd_down7m2_cpt_applicable(N, Cin, H, W, k)) {          // RecNeXt's three Downsample convs at 224 x 224: tile kernel (rcx_cptbwd_kernels.h)
-            hipError_t et = bwd_down7m2_cpt(g, gx, x_dt, w, N, Cin, H, s);
-            if (et != hipSuccess) return et;
-        } else
-        if (k == 7) {
-            if (x_dt == 1) hipLaunchKernelGGL((k_down_bwd_input_k<bf16_t, 7, 2>), dim3(grid), dim3(256), 0, s, (const float*)nullptr, g, (bf16_t*)gx, w, q);
-            else if (x_dt == 2) hipLaunchKernelGGL((k_down_bwd_input_k<f16_t, 7, 2>), dim3(grid), dim3(256), 0, s, (const float*)nullptr, g, (f16_t*)gx, w, q);
-            else hipLaunchKernelGGL((k_down_bwd_input_k<float, 7, 2>), dim3(grid), dim3(256), 0, s, (const float*)nullptr, g, (float*)gx, w, q);
-        } else
-        if (x_dt == 1) hipLaunchKernelGGL(k_down_bwd_input_mult2<bf16_t>, dim3(grid), dim3(256), 0, s, g, (bf16_t*)gx, w, q);
-        else if (x_dt == 2) hipLaunchKernelGGL(k_down_bwd_input_mult2<f16_t>, dim3(grid), dim3(256), 0, s, g, (f16_t*)gx, w, q);
-        else hipLaunchKernelGGL(k_down_bwd_input_mult2<float>, dim3(grid), dim3(256), 0, s, g, (float*)gx, w, q);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        const dim3 grid(grid_for((long long)N * H * W * (Cin / 2)));
+        const Mult2Gx kx = pick_mult2_gx(N, Cin, H, W, k);
+        if (kx == M2GX_TILE && (e = bwd_down7m2_cpt(g, gx, x_dt, w, N, Cin, H, s)) != hipSuccess) return e;
+        with_type(x_dt, [&](auto t) {
+            using T = decltype(t);
+            if (kx == M2GX_K7) hipLaunchKernelGGL((k_down_bwd_input_k<T, 7, 2>), grid, dim3(256), 0, s, (const float*)nullptr, g, (T*)gx, w, q);
+            if (kx == M2GX_ANY) hipLaunchKernelGGL(k_down_bwd_input_mult2<T>, grid, dim3(256), 0, s, g, (T*)gx, w, q);
+        });
+        if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     q.C = 2 * Cin;                                     // the weight-gradient kernel counts output channels
-    if (bwd_wgrad_dm_cpt_applicable(N, q.C, H, W, k)) {  // RecNeXt's three Downsample convs at 224 x 224: tile kernel (rcx_cptbwd_kernels.h)
-        int rows = 0;
-        hipError_t e3 = bwd_wgrad_dm_cpt(x, x_dt, g, partial, N, q.C, H, s, &rows);
-        if (e3 != hipSuccess) return e3;
-        const int kk3 = k * k, n53 = (kk3 + 1) * q.C;
-        hipLaunchKernelGGL(k_wgrad_reduce8, dim3((n53 + 31) / 32), dim3(32, 8), 0, s, partial, gw, gb, rows, kk3, q.C, 0);
-        return hipGetLastError();
-    }
-    if (wgrad2m_cpl_applicable(N, q.C, H, W, k)) {      // the first two Downsample convs of RecNeXt at 224x224: tiled kernel (rcx_cplwgrad.hip)
-        int rows = 0;
-        hipError_t e2 = wgrad2m_cpl(x, x_dt, g, partial, N, q.C, H, s, &rows);
-        if (e2 != hipSuccess) return e2;
-        const int kk2 = k * k, n52 = (kk2 + 1) * q.C;
-        hipLaunchKernelGGL(k_wgrad_reduce8, dim3((n52 + 31) / 32), dim3(32, 8), 0, s, partial, gw, gb, rows, kk2, q.C, 0);
-        return hipGetLastError();
-    }
-    int gy = wr_grid_y(q.C);
-    const int need = (N * Ho + WR_SLOTS - 1) / WR_SLOTS;
-    if (gy > need) gy = need < 1 ? 1 : need;
-    dim3 block(WR_LANES, WR_SLOTS), grid((q.C / 2 + WR_LANES - 1) / WR_LANES, gy);
-#define RCX_WGM(TA_, K_) hipLaunchKernelGGL((k_wgrad_rows<TA_, 2, false, K_, 2>), grid, block, 0, s, (const TA_*)x, (const float*)nullptr, g, partial, q, Ho, Wo)
-    if (x_dt == 1) { if (k == 3) RCX_WGM(bf16_t, 3); else if (k == 5) RCX_WGM(bf16_t, 5); else RCX_WGM(bf16_t, 7); }
-    else if (x_dt == 2) { if (k == 3) RCX_WGM(f16_t, 3); else if (k == 5) RCX_WGM(f16_t, 5); else RCX_WGM(f16_t, 7); }
-    else { if (k == 3) RCX_WGM(float, 3); else if (k == 5) RCX_WGM(float, 5); else RCX_WGM(float, 7); }
+    int rows = 0;
+    const Mult2Gw kw = pick_mult2_gw(N, q.C, H, W, k);
+    if (kw == M2GW_TILE) e = bwd_wgrad_dm_cpt(x, x_dt, g, partial, N, q.C, H, s, &rows);
+    else if (kw == M2GW_CPL) e = wgrad2m_cpl(x, x_dt, g, partial, N, q.C, H, s, &rows);
+    else {
+        rows = wr_grid_y(q.C);
+        const int need = (N * Ho + WR_SLOTS - 1) / WR_SLOTS;
+        if (rows > need) rows = need < 1 ? 1 : need;
+        dim3 block(WR_LANES, WR_SLOTS), grid((q.C / 2 + WR_LANES - 1) / WR_LANES, rows);
+        with_type(x_dt, [&](auto t) {
+            using T = decltype(t);
+#define RCX_WGM(K_) hipLaunchKernelGGL((k_wgrad_rows<T, 2, false, K_, 2>), grid, block, 0, s, (const T*)x, (const float*)nullptr, g, partial, q, Ho, Wo)
+            if (k == 3) RCX_WGM(3); else if (k == 5) RCX_WGM(5); else RCX_WGM(7);
 #undef RCX_WGM
-    hipError_t e = hipGetLastError();
+        });
+        e = hipGetLastError();
+    }
     if (e != hipSuccess) return e;
-    const int kk = k * k, n5 = (kk + 1) * q.C;
-    hipLaunchKernelGGL(k_wgrad_reduce8, dim3((n5 + 31) / 32), dim3(32, 8), 0, s, partial, gw, gb, gy, kk, q.C, 0);
-    return hipGetLastError();
+    return wgrad_reduce8(partial, gw, gb, rows, k, q.C, 0, s);
 }
 
 hipError_t bwd_down_input(const float* base, const float* g, void* out, int out_dt, const float* w,
@@ -729,16 +730,12 @@ hipError_t bwd_down_input(const float* base, const float* g, void* out, int out_
 {
     BwGeom q{};
     q.N = N; q.C = C; q.H = H; q.W = W; q.Hc = Hc; q.Wc = Wc; q.k = k;
-    const unsigned grid = grid_for((long long)N * H * W * (C / BW_V));
-    if (k == 5) {
-        if (out_dt == 1) hipLaunchKernelGGL((k_down_bwd_input_k<bf16_t, 5, 1>), dim3(grid), dim3(256), 0, s, base, g, (bf16_t*)out, w, q);
-        else if (out_dt == 2) hipLaunchKernelGGL((k_down_bwd_input_k<f16_t, 5, 1>), dim3(grid), dim3(256), 0, s, base, g, (f16_t*)out, w, q);
-        else hipLaunchKernelGGL((k_down_bwd_input_k<float, 5, 1>), dim3(grid), dim3(256), 0, s, base, g, (float*)out, w, q);
-        return hipGetLastError();
-    }
-    if (out_dt == 1) hipLaunchKernelGGL(k_down_bwd_input<bf16_t>, dim3(grid), dim3(256), 0, s, base, g, (bf16_t*)out, w, q);
-    else if (out_dt == 2) hipLaunchKernelGGL(k_down_bwd_input<f16_t>, dim3(grid), dim3(256), 0, s, base, g, (f16_t*)out, w, q);
-    else hipLaunchKernelGGL(k_down_bwd_input<float>, dim3(grid), dim3(256), 0, s, base, g, (float*)out, w, q);
+    const dim3 grid(grid_for((long long)N * H * W * (C / BW_V)));
+    with_type(out_dt, [&](auto t) {
+        using T = decltype(t);
+        if (k == 5) hipLaunchKernelGGL((k_down_bwd_input_k<T, 5, 1>), grid, dim3(256), 0, s, base, g, (T*)out, w, q);
+        else hipLaunchKernelGGL(k_down_bwd_input<T>, grid, dim3(256), 0, s, base, g, (T*)out, w, q);
+    });
     return hipGetLastError();
 }
 

@@ -377,35 +377,22 @@ void k_recconv_bwd_cpl14(BwdArgs A)
     store_wacc(A.part[0], n, C, c, wd);
 }
 
-template <int MODE, int CT, typename TIO, typename TGY = float>
-static hipError_t launch14(const BwdArgs& A, hipStream_t s)
+// the 14x14 (H = 14) or the 7x7 block's backward; a compile-time channel pitch for RecNeXt's stage (256 / 512 channels), else a run-time one
+template <int H, int MODE, int CT, typename TIO, typename TGY>
+static hipError_t launch(const BwdArgs& A, hipStream_t s)
 {
     const unsigned planes = (unsigned)(A.N * ((A.C + 63) / 64));
-    // two waves per plane while that still fits the chip's 1024 SIMDs in one round (and the split grid keeps whole XCD rounds)
     BwdArgs B = A;
-    B.split = planes * 2 <= 1024 && planes % 8 == 0;
-    hipLaunchKernelGGL((k_recconv_bwd_cpl14<MODE, CT, TIO, TGY>), dim3(B.split ? planes * 2 : planes), dim3(64), 0, s, B);
+    B.split = H == 14 && cplbwd_split(A.N, A.C);
+    if constexpr (H == 14) hipLaunchKernelGGL((k_recconv_bwd_cpl14<MODE, CT, TIO, TGY>), dim3(B.split ? planes * 2 : planes), dim3(64), 0, s, B);
+    else hipLaunchKernelGGL((k_recconv_bwd_cpl7<MODE, CT, TIO, TGY>), dim3(planes), dim3(64), 0, s, B);
     return hipGetLastError();
 }
-template <int MODE, typename TIO, typename TGY = float>
-static hipError_t launch14_c(const BwdArgs& A, hipStream_t s)
+template <int H, int MODE, typename TIO, typename TGY = float>
+static hipError_t launch_c(const BwdArgs& A, hipStream_t s)
 {
-    if (A.C == 256) return launch14<MODE, 256, TIO, TGY>(A, s);
-    return launch14<MODE, 0, TIO, TGY>(A, s);
-}
-
-template <int MODE, int CT, typename TIO, typename TGY = float>
-static hipError_t launch7(const BwdArgs& A, hipStream_t s)
-{
-    const unsigned grid = (unsigned)(A.N * ((A.C + 63) / 64));
-    hipLaunchKernelGGL((k_recconv_bwd_cpl7<MODE, CT, TIO, TGY>), dim3(grid), dim3(64), 0, s, A);
-    return hipGetLastError();
-}
-template <int MODE, typename TIO, typename TGY = float>
-static hipError_t launch7_c(const BwdArgs& A, hipStream_t s)
-{
-    if (A.C == 512) return launch7<MODE, 512, TIO, TGY>(A, s);
-    return launch7<MODE, 0, TIO, TGY>(A, s);
+    constexpr int CT = H == 14 ? 256 : 512;
+    return A.C == CT ? launch<H, MODE, CT, TIO, TGY>(A, s) : launch<H, MODE, 0, TIO, TGY>(A, s);
 }
 
 }  // namespace cplbwd
@@ -415,6 +402,13 @@ bool cplbwd_applicable(int N, int C, int H, int W, int level, int k, int dtype)
 {
     if (rcx::opt::off(rcx::opt::BWD_FUSED) || rcx::opt::hand_kernels_off() || N > 512) return false;
     return cpl7b_applicable(N, C, H, W, level, k, dtype) || cpl14_applicable(N, C, H, W, level, k, dtype);
+}
+
+// the 14x14 launch runs two waves per plane while that still fits the chip's 1024 SIMDs in one round (and the split grid keeps whole XCD rounds)
+bool cplbwd_split(int N, int C)
+{
+    const unsigned planes = (unsigned)(N * ((C + 63) / 64));
+    return planes * 2 <= 1024 && planes % 8 == 0;
 }
 
 // gy_dt: RCX_DTYPE_F32, or bfloat16 with a bfloat16 block (dL/dy as autograd hands it over under autocast: no float32 copy; round 6)
@@ -427,12 +421,11 @@ hipError_t cplbwd_recconv(const void* x, const void* gy, const float* wpack, con
     A.x = x; A.gy = gy; A.wpack = wpack; A.wflip = wflip; A.saved = (const char*)saved; A.gx = gx; A.N = N; A.C = C;
     for (int l = 1; l <= level; ++l) { A.f_off[l - 1] = f_off[l]; A.c_off[l - 1] = c_off[l]; }
     for (int j = 0; j < level + 2; ++j) A.part[j] = part[j];
-#define RCX_BW14(MD_) (gy_dt == 1 ? cplbwd::launch14_c<MD_, bf16_t, bf16_t>(A, s) : dtype == 1 ? cplbwd::launch14_c<MD_, bf16_t>(A, s) : dtype == 2 ? cplbwd::launch14_c<MD_, f16_t>(A, s) : cplbwd::launch14_c<MD_, float>(A, s))
-    if (H == 14) return mode == 1 ? RCX_BW14(1) : RCX_BW14(0);
-#undef RCX_BW14
-#define RCX_BW7(MD_) (gy_dt == 1 ? cplbwd::launch7_c<MD_, bf16_t, bf16_t>(A, s) : dtype == 1 ? cplbwd::launch7_c<MD_, bf16_t>(A, s) : dtype == 2 ? cplbwd::launch7_c<MD_, f16_t>(A, s) : cplbwd::launch7_c<MD_, float>(A, s))
-    return mode == 1 ? RCX_BW7(1) : RCX_BW7(0);
-#undef RCX_BW7
+#define RCX_BW(H_, MD_) (gy_dt == 1 ? cplbwd::launch_c<H_, MD_, bf16_t, bf16_t>(A, s) : dtype == 1 ? cplbwd::launch_c<H_, MD_, bf16_t>(A, s) \
+                                : dtype == 2 ? cplbwd::launch_c<H_, MD_, f16_t>(A, s) : cplbwd::launch_c<H_, MD_, float>(A, s))
+    if (H == 14) return mode == 1 ? RCX_BW(14, 1) : RCX_BW(14, 0);
+    return mode == 1 ? RCX_BW(7, 1) : RCX_BW(7, 0);
+#undef RCX_BW
 }
 
 }  // namespace rcx

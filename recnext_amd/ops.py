@@ -211,6 +211,11 @@ def recconv2d_plan(n, c, h, w, level, k, mode, dtype):
     return _lib.load().rcx_recconv2d_fwd_plan(n, c, h, w, level, k, _lib.MODES[mode], _DT[dtype]).decode()
 
 
+def recconv2d_bwd_plan(n, c, h, w, level, k, dtype):
+    """Which schedule recconv2d_backward would run for these extents and this type (rcx_recconv2d_bwd_plan)."""
+    return _lib.load().rcx_recconv2d_bwd_plan(n, c, h, w, level, k, _DT[dtype]).decode()
+
+
 def recconv2d_forward(x, wpack, bpack, level, k, mode="bilinear"):
     """RecConv2d.forward (model/recnext.py:24-34) on the HIP kernels. Returns a channels_last tensor like x."""
     x = _nhwc(x)

@@ -96,6 +96,31 @@ def test_abi_version_and_argument_errors_without_gpu():
     assert lib.rcx_dwconv2d_fwd(one, two, one, None, 1, 8, 7, 7, 5, 3, 0, 0, None) == -2                # stride 3
 
 
+def test_backward_plan_at_the_cut_overs():
+    """rcx_recconv2d_bwd_plan on both sides of each cut-over of the backward schedule (the cases tests/test_backward_f64_gpu.py runs)."""
+    lib = _lib.load()
+
+    def plan(n, c, h, level):
+        return lib.rcx_recconv2d_bwd_plan(n, c, h, h, level, 5, _lib.DTYPE_BF16)
+    assert plan(512, 8, 7, 1) == b"one(k_recconv_bwd_cpl7)"                  # one launch up to 512 images (one partial row each)
+    assert plan(513, 8, 7, 1) == b"steps"
+    assert plan(128, 256, 14, 2) == b"one(k_recconv_bwd_cpl14,split)"       # 512 planes: two waves each still fit 1024 SIMDs
+    assert plan(130, 256, 14, 2) == b"one(k_recconv_bwd_cpl14)"
+    assert plan(64, 64, 56, 4) == b"tiled(levels=2)+one(k_recconv_bwd_cpl14,split)"
+    assert plan(288, 128, 28, 3) == b"tiled(levels=1)+one(k_recconv_bwd_cpl14)"
+    assert plan(1, 16, 112, 5) == b"steps+one(k_recconv_bwd_cpl14)"         # 112 -> 56 -> 28 -> 14: the per-step levels end in the 14 x 14 tail
+    assert plan(1, 8, 40, 5) == b"steps"
+    assert lib.rcx_recconv2d_bwd_plan(2, 64, 56, 56, 9, 5, _lib.DTYPE_BF16) == b"invalid"
+    with rcx_env(RCX_BWD_FUSED="0"):
+        assert plan(128, 256, 14, 2) == b"steps"
+        assert plan(64, 64, 56, 4) == b"steps"                                # no 14 x 14 tail, so no tiled levels either
+        assert plan(1, 16, 112, 5) == b"steps"
+    with rcx_env(RCX_FORCE_GENERIC="1"):
+        assert plan(512, 8, 7, 1) == b"generic"
+        assert plan(64, 64, 56, 4) == b"generic"
+        assert plan(1, 8, 40, 5) == b"generic"
+
+
 def test_workspace_query():
     lib = _lib.load()
     assert lib.rcx_recconv2d_fwd_workspace_bytes(1, 8, 7, 7, 0, 5, 0) == 0 or True

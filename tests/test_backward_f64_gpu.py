@@ -5,7 +5,8 @@ K * 2**-24 times the sum of absolute products that feed the element).
 Schedules of rcx_recconv2d_bwd (rcx_api.hip): "one7" / "one14" the one-launch block backward (N <= 512; at 14 x 14 two waves per plane while
 2 * planes <= 1024 and planes % 8 == 0, planes = N * ceil(C / 64)), "tiled28" / "tiled56" the tiled adjoint kernels of the fine levels with the
 one-launch 14 x 14 block as their tail, "perstep" one launch per ladder step, "generic" the same under RCX_FORCE_GENERIC=1.  Each case checks
-that the library still routes it as named, through the dL/dy type it accepts (bfloat16 on the first four, float32 on the last two).
+that the library still routes it as named, through the plan query (rcx_recconv2d_bwd_plan) and through the dL/dy type it accepts (bfloat16 on
+the first four, float32 on the last two).
 """
 import itertools
 
@@ -43,6 +44,15 @@ LARGE = [
     ("tiled56", (160, 64, 56, 56, 4), "f32", "nearest"),
 ]
 FAST = ("one7", "one14split", "one14", "tiled28", "tiled56")
+
+
+def _plan(sched, n, c):
+    """The plan string of each schedule; the tiled ones end in their 14 x 14 tail, split by the rule above."""
+    planes = n * -(-c // 64)
+    tail = "one(k_recconv_bwd_cpl14,split)" if 2 * planes <= 1024 and planes % 8 == 0 else "one(k_recconv_bwd_cpl14)"
+    return {"one7": "one(k_recconv_bwd_cpl7)", "one14": "one(k_recconv_bwd_cpl14)", "one14split": "one(k_recconv_bwd_cpl14,split)",
+            "tiled28": "tiled(levels=1)+" + tail, "tiled56": "tiled(levels=2)+" + tail, "perstep": "steps", "generic": "generic"}[sched]
+
 
 RECCONV_CASES = [(s, shp, dt, mode, bias) for (s, shp), dt, mode, bias in
                  itertools.product(SMALL, ("f32", "bf16", "f16"), ("bilinear", "nearest"), (True, False))]
@@ -91,6 +101,7 @@ def test_recconv2d_backward_matches_float64(case, monkeypatch, ratios):
     bd = _rand(g, (c,), dt, dev, 0.1) if bias else None
     bc = [_rand(g, (c,), dt, dev, 0.1) for _ in range(level + 1)] if bias else None
 
+    assert ops.recconv2d_bwd_plan(n, c, h, w, level, K5, dt) == _plan(sched, n, c)
     gy_native = _lib.load().rcx_recconv2d_bwd_gy_dtype(n, c, h, w, level, K5, ops._DT[dt])
     if dt == torch.bfloat16:
         assert gy_native == (_lib.DTYPE_BF16 if sched in FAST else _lib.DTYPE_F32), "the case no longer reaches the schedule it is named after"
