@@ -135,6 +135,32 @@ int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* 
                       int N, int C, int H, int W, int level, int k, int mode, int dtype, void* stream);
 
 /*
+ * Input-only backward of the RecConv2d block (model/recnext.py:24-34) for a block whose parameters want no gradient (frozen, or folded for
+ * inference): gx = dL/dx alone.  The block is linear in x, so gx depends on gy and the taps only -- no x, no saved pyramid (the forward is
+ * the inference rcx_recconv2d_fwd), and no weight gradient is formed.
+ *   rcx_recconv2d_bwd_input   gy: N x H x W x C of `gy_dtype`: float32 always works; the block's own 16-bit `dtype` (bfloat16 or float16) where
+ *                             rcx_recconv2d_bwd_input_gy_dtype() returns it (the one-launch and tiled schedules);  gx: N x H x W x C of `dtype`,
+ *                             must not alias gy;  wpack / wpack_flipped as for rcx_recconv2d_bwd (bpack plays no part: the gradient of a bias
+ *                             term with respect to x is zero, so a folded block's pack works as it is);  workspace:
+ *                             rcx_recconv2d_bwd_input_workspace_bytes() bytes (0: may be NULL).  Needs C % 4 == 0.  Deterministic (no atomics).
+ *   rcx_recconv2d_bwd_input_workspace_bytes   0 for the 14x14 / level 2 and 7x7 / level 1 blocks; never more than
+ *                             rcx_recconv2d_bwd_workspace_bytes() for the same problem.
+ *   rcx_recconv2d_bwd_input_gy_dtype  the element type rcx_recconv2d_bwd_input wants gy in: `dtype` where a 16-bit gy is read as it is, else
+ *                             RCX_DTYPE_F32.
+ *   rcx_recconv2d_bwd_input_plan  the schedule rcx_recconv2d_bwd_input would use: "one(k_recconv_adj_cpl7)", "one(k_recconv_adj_cpl14)" (the whole
+ *                             adjoint in one launch, any batch), "tiled(levels=2)+one(k_recconv_adj_cpl14)" / "tiled(levels=1)+one(...)" (the tiled
+ *                             fine levels of the 56x56 / 28x28 blocks, then the 14x14 adjoint), "steps+one(...)" (one launch per ladder step down to a
+ *                             14x14 tail), "steps", "generic" (RCX_FORCE_GENERIC=1) or "invalid"; thread-local storage, valid until the next call
+ *                             on this thread.  RCX_BWD_FUSED=0 pins "steps", as for rcx_recconv2d_bwd.
+ */
+size_t rcx_recconv2d_bwd_input_workspace_bytes(int N, int C, int H, int W, int level, int k);
+int rcx_recconv2d_bwd_input_gy_dtype(int N, int C, int H, int W, int level, int k, int dtype);
+const char* rcx_recconv2d_bwd_input_plan(int N, int C, int H, int W, int level, int k, int dtype);
+int rcx_recconv2d_bwd_input(const void* gy, int gy_dtype, const float* wpack, const float* wpack_flipped, void* gx,
+                            void* workspace, size_t workspace_bytes,
+                            int N, int C, int H, int W, int level, int k, int mode, int dtype, void* stream);
+
+/*
  * Depthwise conv, zero padding k/2, stride 1 or 2 -- nn.Conv2d(groups=C) as used at
  * model/recnext.py:21-22 and by RecAttn2d's ConvNorm(dw k5 s2) after BN folding (model/recattn.py:61, :89-111).
  *   x: N x H x W x C (in_dtype);  y: N x Ho x Wo x C (out_dtype), Ho = (H + 2*(k/2) - k)/stride + 1.

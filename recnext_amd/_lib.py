@@ -42,6 +42,10 @@ SIGNATURES = {
     "rcx_upadd_dwconv_bwd_gy_dtype": (_i, [_i] * 8),
     "rcx_upadd_dwconv_bwd": (_i, [_vp, _vp, _vp, _i] + [_vp] * 7 + [_sz] + [_i] * 9 + [_vp]),
     "rcx_recconv2d_bwd": (_i, [_vp, _vp, _i] + [_vp] * 8 + [_i, _vp, _sz] + [_i] * 8 + [_vp]),
+    "rcx_recconv2d_bwd_input_workspace_bytes": (_sz, [_i] * 6),
+    "rcx_recconv2d_bwd_input_gy_dtype": (_i, [_i] * 7),
+    "rcx_recconv2d_bwd_input_plan": (ctypes.c_char_p, [_i] * 7),
+    "rcx_recconv2d_bwd_input": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz] + [_i] * 8 + [_vp]),
     "rcx_dwconv2d_fwd": (_i, [_vp, _vp, _vp, _vp] + [_i] * 8 + [_vp]),
     "rcx_dwconv2d_mult2_fwd": (_i, [_vp, _vp, _vp, _vp] + [_i] * 7 + [_vp]),
     "rcx_upadd_dwconv_fwd": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 11 + [_vp]),

@@ -471,6 +471,20 @@ BwdSchedule bwd_schedule(const TrainLadder& L, int N, int C, int level, int k, i
     return {tiled ? BWD_TILED : BWD_STEPS, m, m > 0 && rcx::cplbwd_split(N, C)};
 }
 
+// The input-only backward's schedule (rcx_recconv2d_bwd_input): the same kinds and cut-overs as bwd_schedule, on the input adjoint
+// (rcx_cpladj.hip) instead of the whole-block backward.  That kernel keeps no partial rows, so no batch limit; it runs one wave per plane.
+BwdKind bwd_input_schedule(const TrainLadder& L, int N, int C, int level, int k, int dtype, int* m_out)
+{
+    *m_out = 0;
+    if (level >= 1 && rcx::cpladj_applicable(N, C, L.h[0], L.w[0], level, k, dtype)) return BWD_ONE;
+    const int m = level >= 3 && L.h[level - 2] == 14 && L.w[level - 2] == 14 && rcx::cpladj_applicable(N, C, 14, 14, 2, k, RCX_DTYPE_F32) ? level - 2 : 0;
+    bool tiled = m > 0;
+    for (int l = 0; l < m; ++l)
+        tiled = tiled && rcx::bwd_cpt_applicable(N, C, L.h[l], L.w[l], k) && L.h[l + 1] * 2 == L.h[l] && L.w[l + 1] * 2 == L.w[l];
+    *m_out = m;
+    return tiled ? BWD_TILED : BWD_STEPS;
+}
+
 // One rcx_recconv2d_bwd call and the weight-gradient jobs its partial buffers join (job 0 = the shared down conv, job 1 + j = convs[j])
 struct BwdRun {
     const TrainLadder& L;
@@ -677,6 +691,137 @@ int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* 
     hipError_t e = hipMemsetAsync(gw0, 0, esz * k * k * C, s);
     if (e == hipSuccess && gb0) e = hipMemsetAsync(gb0, 0, esz * C, s);
     return e == hipSuccess ? 0 : hip_fail(e, "bwd: zero down grad");
+}
+
+// ---- the input-only backward: gx = A^T gy, from gy and the taps alone (the block is linear in x) ----
+namespace {
+
+// The workspace of an input-only backward: none for the one-launch blocks, else the float32 gradient planes of the training backward's
+// ladder (gT_0 .. gT_L and the resized-gradient plane) without its partial-sum buffers
+size_t bwd_input_workspace(const TrainLadder& L, BwdKind kind) { return kind == BWD_ONE ? 0 : L.part_off; }
+
+struct AdjRun {
+    const TrainLadder& L;
+    const void* gy;
+    void* gx;
+    const float *wpack, *wflip;
+    char* ws;
+    int gy_dt, N, C, level, k, mode, dtype;
+    hipStream_t s;
+    const float* Wd(int i) const { return wpack + (size_t)i * k * k * C; }
+    const float* Wf(int i) const { return wflip + (size_t)i * k * k * C; }
+    float* G(int l) const { return (float*)(ws + L.g_off[l]); }
+};
+
+// the 14x14 tail: g = dL/dC_m (float32) -> G_m (float32)
+hipError_t adj_tail(const AdjRun& R, const float* g, float* G)
+{
+    return rcx::cpladj_recconv(g, RCX_DTYPE_F32, R.wpack, R.wflip, G, RCX_DTYPE_F32, R.N, R.C, 14, R.mode == RCX_MODE_NEAREST ? 1 : 0, R.s);
+}
+
+// BWD_TILED without the weight gradients: gC_{l+1} = R^T K^ g_l top-down, the tail, then G_l = K^ g_l + D^T G_{l+1} bottom-up (as bwd_tiled)
+int adj_tiled(const AdjRun& R, int m)
+{
+    const TrainLadder& L = R.L;
+    const int N = R.N, C = R.C, md = R.mode == RCX_MODE_NEAREST ? 1 : 0;
+    float* gcl[RCX_MAX_LEVEL + 1] = {};
+    size_t off = 0;
+    for (int l = 1; l <= m; ++l) { gcl[l] = (float*)(R.ws + L.g_off[0] + off); off += align256(sizeof(float) * (size_t)N * C * L.h[l] * L.w[l]); }
+    auto g_of = [&](int l) { return l == 0 ? R.gy : (const void*)gcl[l]; };
+    auto gdt_of = [&](int l) { return l == 0 ? R.gy_dt : RCX_DTYPE_F32; };
+    for (int l = 0; l < m; ++l)
+        RCX_TRY(rcx::bwd_gc_cpt(g_of(l), gdt_of(l), gcl[l + 1], R.Wf(1 + R.level - l), N, C, L.h[l], md, R.s), "bwd input: gradient handed down");
+    RCX_TRY(adj_tail(R, gcl[m], R.G(m)), "bwd input: 14x14 tail");
+    for (int l = m - 1; l >= 0; --l)
+        RCX_TRY(rcx::bwd_gx_cpt(g_of(l), gdt_of(l), R.G(l + 1), l == 0 ? R.gx : (void*)R.G(l), l == 0 ? R.dtype : RCX_DTYPE_F32, R.Wf(1 + R.level - l),
+                                R.Wd(0), N, C, L.h[l], R.s), "bwd input: gradient handed up");
+    return 0;
+}
+
+// BWD_STEPS without the weight gradients: the per-step adjoint chain (as bwd_steps), float32 throughout, down to the tail (m > 0)
+int adj_steps(const AdjRun& R, int m)
+{
+    const TrainLadder& L = R.L;
+    const int N = R.N, C = R.C, H = L.h[0], W = L.w[0], level = R.level, k = R.k, mode = R.mode, dtype = R.dtype;
+    float* gC = (float*)(R.ws + L.gc_off);
+    // gT_0 = K_L^T gy (gx itself with no ladder)
+    RCX_TRY(step_dwconv(R.gy, level == 0 ? R.gx : (void*)R.G(0), R.Wf(1 + level), nullptr, N, C, H, W, k, 1, RCX_DTYPE_F32,
+                        level == 0 ? dtype : RCX_DTYPE_F32, R.s), "bwd input: final conv");
+    for (int l = 1; l <= level; ++l) {
+        RCX_TRY(rcx::bwd_resize(R.G(l - 1), gC, N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], mode, R.s), "bwd input: resize adjoint");
+        if (l == m) { RCX_TRY(adj_tail(R, gC, R.G(m)), "bwd input: 14x14 tail"); break; }
+        RCX_TRY(step_dwconv(gC, R.G(l), R.Wf(1 + level - l), nullptr, N, C, L.h[l], L.w[l], k, 1, RCX_DTYPE_F32, RCX_DTYPE_F32, R.s), "bwd input: conv");
+    }
+    for (int l = m ? m : level; l >= 1; --l)
+        RCX_TRY(rcx::bwd_down_input(R.G(l - 1), R.G(l), l == 1 ? R.gx : (void*)R.G(l - 1), l == 1 ? dtype : RCX_DTYPE_F32, R.Wd(0),
+                                    N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], k, R.s), "bwd input: down conv");
+    return 0;
+}
+
+bool bwd_input_extents_ok(int N, int C, int H, int W, int level, int k, int dtype)
+{
+    return N > 0 && C > 0 && H > 0 && W > 0 && level >= 0 && level <= RCX_MAX_LEVEL && k > 0 && (k & 1) && known_dtype(dtype);
+}
+
+}  // namespace
+
+size_t rcx_recconv2d_bwd_input_workspace_bytes(int N, int C, int H, int W, int level, int k)
+{
+    if (!bwd_input_extents_ok(N, C, H, W, level, k, RCX_DTYPE_F32)) return 0;
+    const TrainLadder L = make_train_ladder(N, C, H, W, level, k);
+    int m;
+    // the one-launch kernels take every dtype the fused forward does, so the float32 schedule decides for all three
+    return bwd_input_workspace(L, bwd_input_schedule(L, N, C, level, k, RCX_DTYPE_F32, &m));
+}
+
+int rcx_recconv2d_bwd_input_gy_dtype(int N, int C, int H, int W, int level, int k, int dtype)
+{
+    if (!bwd_input_extents_ok(N, C, H, W, level, k, dtype) || dtype == RCX_DTYPE_F32 || C % 4) return RCX_DTYPE_F32;
+    // the block's own 16-bit type where the one-launch or tiled kernels read gy (bfloat16 and float16 alike: no weight-gradient kernel runs)
+    int m;
+    return bwd_input_schedule(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype, &m) != BWD_STEPS ? dtype : RCX_DTYPE_F32;
+}
+
+const char* rcx_recconv2d_bwd_input_plan(int N, int C, int H, int W, int level, int k, int dtype)
+{
+    if (!bwd_input_extents_ok(N, C, H, W, level, k, dtype)) return "invalid";
+    if (rcx::opt::hand_kernels_off()) return "generic";
+    static thread_local char desc[64];
+    int m;
+    const BwdKind kind = bwd_input_schedule(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype, &m);
+    if (kind == BWD_ONE) return H == 14 ? "one(k_recconv_adj_cpl14)" : "one(k_recconv_adj_cpl7)";
+    if (kind == BWD_TILED) snprintf(desc, sizeof(desc), "tiled(levels=%d)+one(k_recconv_adj_cpl14)", m);
+    else if (m) snprintf(desc, sizeof(desc), "steps+one(k_recconv_adj_cpl14)");
+    return kind == BWD_STEPS && !m ? "steps" : desc;
+}
+
+int rcx_recconv2d_bwd_input(const void* gy, int gy_dtype, const float* wpack, const float* wpack_flipped, void* gx,
+                            void* workspace, size_t workspace_bytes,
+                            int N, int C, int H, int W, int level, int k, int mode, int dtype, void* stream)
+{
+    if (int rc = check_common(gy, gx, N, C, H, W, k, dtype)) return rc;
+    if (!wpack || !wpack_flipped) return fail(RCX_ERR_BAD_ARG, "null weight pack");
+    if (gy == gx) return fail(RCX_ERR_BAD_ARG, "gx must not alias gy");
+    if (!known_dtype(gy_dtype)) return fail(RCX_ERR_BAD_ARG, "unknown gy dtype %d", gy_dtype);
+    if (level < 0 || level > RCX_MAX_LEVEL) return fail(RCX_ERR_BAD_ARG, "level %d outside [0,%d]", level, RCX_MAX_LEVEL);
+    if (mode != RCX_MODE_BILINEAR && mode != RCX_MODE_NEAREST) return fail(RCX_ERR_BAD_ARG, "unknown mode %d", mode);
+    if (C % 4) return fail(RCX_ERR_UNSUPPORTED, "the backward kernels need C %% 4 == 0, got C=%d", C);
+    const TrainLadder L = make_train_ladder(N, C, H, W, level, k);
+    int m;
+    const BwdKind kind = bwd_input_schedule(L, N, C, level, k, dtype, &m);
+    const size_t need = bwd_input_workspace(L, kind);
+    if (need && (!workspace || workspace_bytes < need))
+        return fail(RCX_ERR_WORKSPACE, "input-backward workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (gy_dtype != RCX_DTYPE_F32 && !(kind != BWD_STEPS && gy_dtype == dtype))
+        return fail(RCX_ERR_UNSUPPORTED, "gy of dtype %d: this problem takes float32 (rcx_recconv2d_bwd_input_gy_dtype)", gy_dtype);
+    AdjRun R{L};
+    R.gy = gy; R.gx = gx; R.wpack = wpack; R.wflip = wpack_flipped; R.ws = (char*)workspace;
+    R.gy_dt = gy_dtype; R.N = N; R.C = C; R.level = level; R.k = k; R.mode = mode; R.dtype = dtype; R.s = (hipStream_t)stream;
+    if (kind == BWD_ONE) {
+        RCX_TRY(rcx::cpladj_recconv(gy, gy_dtype, wpack, wpack_flipped, gx, dtype, N, C, H, mode == RCX_MODE_NEAREST ? 1 : 0, R.s), "bwd input: fused block");
+        return 0;
+    }
+    return kind == BWD_TILED ? adj_tiled(R, m) : adj_steps(R, m);
 }
 
 #undef RCX_TRY

@@ -108,6 +108,12 @@ hipError_t cplbwd_recconv(const void* x, const void* gy, const float* wpack, con
                           const size_t* f_off, const size_t* c_off, void* gx, float* const* part,
                           int N, int C, int H, int level, int mode, int dtype, hipStream_t s, int gy_dt = 0);      // gy_dt: 0 float32 | 1 bfloat16 (with dtype 1)
 
+// channel-per-lane input adjoint of the same two blocks (rcx_cpladj.hip): gx alone, from gy and the taps (no x, no saved pyramid, no partial
+// rows).  gy_dt: 0 float32, or the block's 16-bit type (= gx_dt); gx_dt: the block's type, or 0 for the float32 14x14 tail of a larger block
+bool cpladj_applicable(int N, int C, int H, int W, int level, int k, int dtype);
+hipError_t cpladj_recconv(const void* gy, int gy_dt, const float* wpack, const float* wflip, void* gx, int gx_dt, int N, int C, int H, int mode,
+                          hipStream_t s);
+
 // tiled channel-per-lane weight gradient of a stride-1 5x5 conv over T = a + R(coarse) on the 56x56 / 28x28 planes (rcx_cplwgrad.hip):
 // one partial row of (25 + 1) * C sums per (image, 14-row band)
 bool wgrad_cpl_applicable(int N, int C, int H, int W, int Hc, int Wc, int k, int stride, bool has_coarse);

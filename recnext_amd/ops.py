@@ -216,6 +216,11 @@ def recconv2d_bwd_plan(n, c, h, w, level, k, dtype):
     return _lib.load().rcx_recconv2d_bwd_plan(n, c, h, w, level, k, _DT[dtype]).decode()
 
 
+def recconv2d_bwd_input_plan(n, c, h, w, level, k, dtype):
+    """Which schedule recconv2d_input_backward would run for these extents and this type (rcx_recconv2d_bwd_input_plan)."""
+    return _lib.load().rcx_recconv2d_bwd_input_plan(n, c, h, w, level, k, _DT[dtype]).decode()
+
+
 def recconv2d_forward(x, wpack, bpack, level, k, mode="bilinear"):
     """RecConv2d.forward (model/recnext.py:24-34) on the HIP kernels. Returns a channels_last tensor like x."""
     x = _nhwc(x)
@@ -749,3 +754,32 @@ def recconv2d_backward(x, gy, wpack, saved, level, k, mode="bilinear", need_bias
                                    ws.data_ptr(), nbytes, n, c, h, w, level, k, _lib.MODES[mode], _dt(x), _stream(x.device))
     _lib.check(rc, "rcx_recconv2d_bwd")
     return gx, gw, gb
+
+
+def recconv2d_input_backward(gy, wpack, wflip, level, k, mode="bilinear", dtype=None):
+    """-> gx = dL/dx of RecConv2d (channels_last, `dtype`, default gy's dtype) for a block whose parameters want no gradient
+    (rcx_recconv2d_bwd_input).  The block is linear in x: gx needs neither x nor a saved pyramid, only dL/dy and the two packs of
+    pack_recconv_params(with_flipped=True); no weight gradient is formed.  Deterministic.
+    gy may be float32 or, where the library reads it as it is (rcx_recconv2d_bwd_input_gy_dtype: the one-launch and tiled schedules), the
+    block's own 16-bit dtype; anything else is converted to float32 here."""
+    dtype = gy.dtype if dtype is None else dtype
+    if dtype not in _DT:
+        raise TypeError(f"recconv2d_input_backward: dtype must be float32, bfloat16 or float16, got {dtype}")
+    if mode not in _lib.MODES:
+        raise ValueError(f"mode must be 'bilinear' or 'nearest', got {mode!r}")
+    numel = (level + 2) * k * k * gy.shape[1] if gy.dim() == 4 else 0
+    _check_bwd_args("recconv2d_input_backward", gy, packs=[("wpack", wpack, numel), ("wflip", wflip, numel)])
+    _require_gpu(gy, "grad_output")
+    n, c, h, w = gy.shape
+    lib = _lib.load()
+    want = lib.rcx_recconv2d_bwd_input_gy_dtype(n, c, h, w, level, k, _DT[dtype])
+    gy = _nhwc(gy if (gy.dtype == torch.float32 or (gy.dtype == dtype and _DT[gy.dtype] == want)) else gy.to(torch.float32), "grad_output")
+    gx = _empty_nhwc(n, c, h, w, dtype, gy.device)
+    nbytes = lib.rcx_recconv2d_bwd_input_workspace_bytes(n, c, h, w, level, k)    # 0 for the one-launch blocks: nothing to allocate
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device) if nbytes else None
+    with _on(gy.device):
+        rc = lib.rcx_recconv2d_bwd_input(gy.data_ptr(), _dt(gy), wpack.data_ptr(), wflip.data_ptr(), gx.data_ptr(),
+                                         ws.data_ptr() if ws is not None else None, nbytes, n, c, h, w, level, k, _lib.MODES[mode], _dt(gx),
+                                         _stream(gy.device))
+    _lib.check(rc, "rcx_recconv2d_bwd_input")
+    return gx

@@ -98,6 +98,7 @@ class RecConv2d(nn.Module):
                     bpack = torch.zeros((self.level + 2, c), dtype=torch.float32, device=wpack.device)
                 sc = self.fold_scale.to(wpack.device)
                 wpack[-1].view(k * k, c).mul_(sc)                    # tap-major (k*k, C): scale each channel's taps
+                self._wflip[-1].view(k * k, c).mul_(sc)              # ... and the flipped taps the input-only backward reads
                 bpack[-1].mul_(sc).add_(self.fold_shift.to(wpack.device))
             self._pack = (wpack, bpack)
             self._pack_key = key
@@ -105,20 +106,27 @@ class RecConv2d(nn.Module):
 
     def forward(self, x):
         # Schedule choice.  Autograd needs the per-level schedule (it keeps the float32 pyramid for the backward), so ANY call
-        # with grad mode on and something that requires grad takes it -- including a model in eval() called outside
+        # with grad mode on and a parameter that requires grad takes it -- including a model in eval() called outside
         # torch.no_grad(), which is legal (the block has no train/eval distinction) but several times slower than the fused
-        # inference kernels: warn once so that a forgotten no_grad() does not pass for a slow kernel.
+        # inference kernels: warn once so that a forgotten no_grad() does not pass for a slow kernel.  A call that wants dL/dx alone
+        # (frozen or folded parameters) runs the inference launch and the input-only backward: the block is linear in x.
         plist = self._plist() if torch.is_grad_enabled() else ()
-        if plist and (x.requires_grad or any(p.requires_grad for p in plist)):
+        if plist and any(p.requires_grad for p in plist):
             if self.fold_scale is not None:
                 raise RuntimeError("this RecConv2d carries a folded output affine (fold_token_mixer_norms / fold_output_affine), an "
-                                   "inference-only transform: wrap the call in torch.no_grad() (or torch.inference_mode())")
+                                   "inference-only transform: its parameters cannot be trained.  Wrap the call in torch.no_grad() (or "
+                                   "torch.inference_mode()), or freeze the parameters (requires_grad_(False)) to get input gradients")
             if self.in_channels % 4:
                 raise NotImplementedError(f"the HIP backward of RecConv2d needs a channel count that is a multiple of 4, got "
                                           f"{self.in_channels}; run inference under torch.no_grad()")
             if not self.training and not x.requires_grad:
                 _warn_eval_with_grad()
             return _RecConv2dFn.apply(x, self, *plist)
+        if plist and x.requires_grad:
+            if self.in_channels % 4:
+                raise NotImplementedError(f"the HIP backward of RecConv2d needs a channel count that is a multiple of 4, got "
+                                          f"{self.in_channels}; run inference under torch.no_grad()")
+            return _RecConv2dInputFn.apply(x, self)
         wpack, bpack = self.packed_params()
         return ops.recconv2d_forward(x, wpack, bpack, self.level, self.kernel_size, self.mode)
 
@@ -190,3 +198,25 @@ class _RecConv2dFn(torch.autograd.Function):
         grads = [g.as_strided(g.shape, ps) if g.stride() != ps and all(n == 1 or a == b for n, a, b in zip(g.shape, g.stride(), ps)) else g
                  for g, ps in zip(grads, ctx.param_strides)]
         return (gx if ctx.needs_input_grad[0] else None, None, *grads)
+
+
+class _RecConv2dInputFn(torch.autograd.Function):
+    """Autograd wrapper for a block whose parameters want no gradient (frozen, or folded by fold_output_affine): dL/dx only.
+
+    The forward is the inference launch (the same call the no-grad path makes, so y is bit-identical to it).  The block is linear in x,
+    so the backward (rcx_recconv2d_bwd_input) needs the weight packs alone: no activation is saved and no weight gradient is formed.
+    """
+
+    @staticmethod
+    def forward(ctx, x, module):
+        wpack, bpack = module.packed_params()
+        y = ops.recconv2d_forward(x, wpack, bpack, module.level, module.kernel_size, module.mode)
+        ctx.save_for_backward(wpack, module._wflip)
+        ctx.level, ctx.k, ctx.mode, ctx.x_dtype = module.level, module.kernel_size, module.mode, x.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        wpack, wflip = ctx.saved_tensors
+        gx = ops.recconv2d_input_backward(grad_out, wpack, wflip, ctx.level, ctx.k, ctx.mode, ctx.x_dtype)
+        return gx, None

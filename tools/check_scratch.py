@@ -2,7 +2,8 @@
 """Build gate (recnext_amd/csrc/Makefile): list every kernel of the given hipcc -S listings with its register and scratch figures and fail
 when a kernel the DEFAULT dispatch reaches has a private segment (registers spilled to memory).  Default dispatch = the inference
 instantiations for bf16 / float32 activations of the fused kernels (k_recconv_cpt without TRAIN, k_recconv_cpl14, k_recconv_cpl7b) and the
-tiled step kernels (k_upadd_cpt, k_down5_cpt, k_down7m2_cpt); the training-forward and float16 instantiations are reported only.
+tiled step kernels (k_upadd_cpt, k_down5_cpt, k_down7m2_cpt), and every instantiation of the input adjoint (k_recconv_adj_cpl14,
+k_recconv_adj_cpl7); the training-forward and float16 instantiations are reported only.
 usage: check_scratch.py file.s [file.s ...]"""
 import re
 import subprocess
@@ -53,6 +54,8 @@ for (path, r), name in zip(rows, names):
         gated = m.group(6) == "false" and not fp16
     elif re.match(r"(cpl14::k_recconv_cpl14|cpl14::k_recconv_cpl7b|cpl14::k_upadd_cpl14|cpl14::k_upadd_cpl7|cpl14::k_down5_cpl7|upcpt::k_upadd_cpt|upcpt::k_down5_cpt|upcpt::k_down7m2_cpt)<", short):
         gated = not fp16
+    elif re.match(r"cpladj::k_recconv_adj_cpl(14|7)<", short):
+        gated = True                                       # the input adjoint: every instantiation, float16 included, is default dispatch
     flag = ""
     if priv:
         flag = "  <-- SCRATCH" + (" (gated)" if gated else " (reported only)")
