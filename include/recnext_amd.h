@@ -258,7 +258,8 @@ int rcx_linear_attention_pe_fwd(const void* qpre, const void* kpre, const void* 
  *   bqk    : (2C) float32 biases; w_pe_kkc / b_pe: as rcx_linear_attention_pe_fwd (b_pe may be NULL);  out: B x (H W) x C float32;
  *   workspace: rcx_recattn_qkcore_workspace_bytes(...) bytes (0 bytes / may be NULL when one launch does it).  Every pointer 16-byte aligned.
  * 1, 2, 4, 8 or 16 heads of dimension C / heads = 32, or of 4, 8 .. 28 when heads is even (a head is padded to 32 inside the kernels; memory stays
- * compact: RecNeXt-A0 / A1 / A2's 20 / 24 / 28).  Planes of at most 64 tokens whose image fits the CU's LDS: ONE launch, a workgroup
+ * compact: RecNeXt-A0 / A1 / A2's 20 / 24 / 28), or 2, 4 or 8 heads of 36, 40 .. 64 (round 8: RecNeXt-A5's 40; a head is two 32-channel tiles in
+ * registers, the LDS images keep the true width C -- where that image does not fit, e.g. 8 heads of 64 on 7 x 7, the plane takes two launches).  Planes of at most 64 tokens whose image fits the CU's LDS: ONE launch, a workgroup
  * per image, a wave per head (16 heads: at most 32 tokens; RecNeXt-A's stages 2 and 3 at 224 x 224).  Other planes: TWO launches (the k^T v partial
  * sums of every image go through the workspace, summed in a fixed order: deterministic), at most 8 heads.  rcx_recattn_qkcore_launches() tells which
  * (0: no kernel for the shape -> the call returns RCX_ERR_UNSUPPORTED).  The products run on the matrix cores with bf16 operands and float32
@@ -274,7 +275,8 @@ int rcx_recattn_qkcore_fwd(const float* d, const void* wqk_bf16, const float* bq
  * The same preceded by RecAttn2d's stride-2 depthwise 5x5 ConvNorm (model/recattn.py:12 / :61, BatchNorm folded) in the same launch: x -> d stays in
  * LDS, d never exists in memory.  x: B x H x W x C bf16 / f16 NHWC; w_down_kkc (5,5,C) / b_down (C, may be NULL) float32 as rcx_dwconv2d_fwd takes
  * them; the rest as rcx_recattn_qkcore_fwd; out: B x ceil(H/2) x ceil(W/2) x C float32.  Planes 14 x 14 (1 .. 8 heads) and 7 x 7 (1 .. 16 heads) only --
- * RecNeXt-A's stages 2 and 3 at 224 x 224 -- rcx_recattn_down_qkcore_supported() says (1 / 0); else RCX_ERR_UNSUPPORTED.
+ * RecNeXt-A's stages 2 and 3 at 224 x 224 --, head dimensions as rcx_recattn_qkcore_fwd (36 .. 64: 2, 4 or 8 heads, the coarse plane's image within the
+ * LDS); rcx_recattn_down_qkcore_supported() says (1 / 0); else RCX_ERR_UNSUPPORTED.
  */
 int rcx_recattn_down_qkcore_supported(int B, int H, int W, int C, int heads, int x_dtype);
 int rcx_recattn_down_qkcore_fwd(const void* x, const float* w_down_kkc, const float* b_down, const void* wqk_bf16, const float* bqk,
@@ -284,7 +286,8 @@ int rcx_recattn_down_qkcore_fwd(const void* x, const float* w_down_kkc, const fl
  * RecAttn2d.forward whole (model/recattn.py:54-67 in eval mode, BatchNorms folded): y = ConvNorm_k5(x + interpolate(LinearAttention(ConvNorm_k5s2(x)),
  * size = x's, mode = nearest)) in ONE launch -- a workgroup per image, x's plane read twice (the stride-2 conv, the final conv), d and the attention
  * output only ever in LDS.  x, y: B x H x W x C bf16 / f16 NHWC; w_down_kkc / b_down, w_conv_kkc / b_conv: (5,5,C) / (C) float32 packs (biases may be
- * NULL); wqk / bqk / w_pe_kkc / b_pe as rcx_recattn_qkcore_fwd.  Planes 14 x 14 and 7 x 7, 1 .. 8 heads of 32 channels, RCX_MODE_NEAREST;
+ * NULL); wqk / bqk / w_pe_kkc / b_pe as rcx_recattn_qkcore_fwd.  Planes 14 x 14 and 7 x 7, 1 .. 8 heads of 32 channels (or 4 .. 28; never above 32:
+ * the attention output's image would not fit the LDS beside d's), RCX_MODE_NEAREST;
  * rcx_recattn2d_fwd_supported() says (1 / 0); else RCX_ERR_UNSUPPORTED -- the caller then chains the entry points above and rcx_upadd_dwconv_fwd.
  */
 int rcx_recattn2d_fwd_supported(int B, int H, int W, int C, int heads, int mode, int dtype);

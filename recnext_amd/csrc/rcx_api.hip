@@ -1085,7 +1085,8 @@ int rcx_recattn_qkcore_fwd(const float* d, const void* wqk_bf16, const float* bq
         return fail(RCX_ERR_BAD_ARG, "rcx_recattn_qkcore_fwd: d, wqk, bqk, w_pe_kkc, b_pe and out must be 16-byte aligned");
     if (!rcx::recattn_qkcore_applicable(B, H, W, C, heads))
         return fail(RCX_ERR_UNSUPPORTED, "rcx_recattn_qkcore_fwd: head dimension %d, %d heads, %d tokens, C=%d: the matrix-core form takes 32-wide heads, 1, 2, 4, 8 or "
-                                         "16 of them; 16 only on planes of at most 32 tokens (rcx_recattn_qkcore_launches; use the projection GEMMs + "
+                                         "16 of them (16 only on planes of at most 32 tokens), heads of 4 .. 28 channels in fours (an even count), or of 36 .. 64 "
+                                         "in fours (2, 4 or 8 heads), where the LDS holds the plane (rcx_recattn_qkcore_launches; use the projection GEMMs + "
                                          "rcx_linear_attention_pe_fwd)", C / heads, heads, H * W, C);
     const size_t need = rcx::recattn_qkcore_workspace_bytes(B, H, W, C, heads);
     if (need && (!workspace || workspace_bytes < need || ((size_t)workspace & 15)))
@@ -1111,7 +1112,8 @@ int rcx_recattn_down_qkcore_fwd(const void* x, const float* w_down_kkc, const fl
         return fail(RCX_ERR_BAD_ARG, "rcx_recattn_down_qkcore_fwd: wqk, bqk, w_pe_kkc, b_pe and out must be 16-byte aligned");
     if (!rcx::recattn_down_qkcore_applicable(B, H, W, C, heads, x_dtype))
         return fail(RCX_ERR_UNSUPPORTED, "rcx_recattn_down_qkcore_fwd: %d x %d plane, %d heads of %d, dtype %d: the one-launch form takes the 14 x 14 plane (1 .. 8 heads) "
-                                         "and the 7 x 7 plane (1 .. 16 heads) of bf16 / f16 activations, 32-wide heads (use rcx_dwconv2d_fwd + rcx_recattn_qkcore_fwd)",
+                                         "and the 7 x 7 plane (1 .. 16 heads) of bf16 / f16 activations, heads of 4 .. 32 channels, or 2, 4 or 8 heads of 36 .. 64 in fours "
+                                         "whose image fits the LDS (use rcx_dwconv2d_fwd + rcx_recattn_qkcore_fwd)",
                     H, W, heads, C / heads, x_dtype);
     hipError_t e = rcx::recattn_down_qkcore(x, w_down_kkc, b_down, wqk_bf16, bqk, w_pe_kkc, b_pe, out, B, H, C, heads, x_dtype, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_recattn_down_qkcore_fwd");
@@ -1136,7 +1138,7 @@ int rcx_recattn2d_fwd(const void* x, void* y, const float* w_down_kkc, const flo
         return fail(RCX_ERR_BAD_ARG, "rcx_recattn2d_fwd: wqk, bqk, w_pe_kkc and b_pe must be 16-byte aligned");
     if (!rcx::recattn2d_unit_applicable(B, H, W, C, heads, dtype, mode == RCX_MODE_NEAREST ? 1 : 0))
         return fail(RCX_ERR_UNSUPPORTED, "rcx_recattn2d_fwd: %d x %d plane, %d heads of %d, mode %d, dtype %d: the one-launch unit takes the 14 x 14 (1 .. 8 heads) and 7 x 7 (1 .. 16 heads) planes of bf16 / f16 "
-                                         "activations, heads of 32 or 4 .. 28 channels, nearest resize (use rcx_recattn_down_qkcore_fwd / rcx_dwconv2d_fwd + rcx_recattn_qkcore_fwd, then "
+                                         "activations, heads of 32 or 4 .. 28 channels (not above 32), nearest resize (use rcx_recattn_down_qkcore_fwd / rcx_dwconv2d_fwd + rcx_recattn_qkcore_fwd, then "
                                          "rcx_upadd_dwconv_fwd)", H, W, heads, C / heads, mode, dtype);
     hipError_t e = rcx::recattn2d_unit(x, w_down_kkc, b_down, wqk_bf16, bqk, w_pe_kkc, b_pe, w_conv_kkc, b_conv, y, B, H, C, heads, dtype, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_recattn2d_fwd");

@@ -591,16 +591,22 @@ static inline size_t short_lds_bytes(int NT, int Wp, int C, bool full = false)
 
 constexpr int TILE_TOK = 32;
 constexpr int PART_FLOATS = 17 * 64;       // per (image, range, head): 16 accumulator registers + the column-sum partial of each lane
+constexpr int PART_W = (4 * 16 + 2) * 64;  // the same for a WIDE head (36 .. 64 channels, below): the 2 x 2 kv tiles + the column-sum partial of each channel tile
+// a wide head's LDS after the rows of d: [9][C] pe taps, [C] pe bias, [64 heads] q biases (-100 past D), [64 heads] kbar
+static inline size_t small_floats_w(int C, int heads) { return 10 * (size_t)C + 128 * (size_t)heads; }
 
+// wide = heads of 36 .. 64 channels (k_recattn_kv_w / k_recattn_out_w): C is then the true channel count, 8 waves in both kernels
 struct LongGeo { int ntiles, tpg, G, rows, waves, S; size_t lds_out; int tpgA, GA, SA; size_t lds_kv, ws_bytes; };
-static inline LongGeo long_geo(int B, int Hp, int Wp, int C, int heads)
+static inline LongGeo long_geo(int B, int Hp, int Wp, int C, int heads, bool wide = false)
 {
     LongGeo g{};
     const int n = Hp * Wp;
+    const size_t small = wide ? small_floats_w(C, heads) : 12 * (size_t)C;
+    const int part = wide ? PART_W : PART_FLOATS;
     g.ntiles = (n + TILE_TOK - 1) / TILE_TOK;
     // second kernel: ranges whose rows (+ halo) take at most half a CU's LDS
     const int halo = 2 * Wp + 2;
-    int tpg = ((int)((80 * 1024 - 48 * (size_t)C) / (4 * (size_t)(C + DPAD))) - halo - 1) / TILE_TOK;
+    int tpg = ((int)((80 * 1024 - 4 * small) / (4 * (size_t)(C + DPAD))) - halo - 1) / TILE_TOK;
     if (tpg < 1) tpg = 1;
     if (tpg > g.ntiles) tpg = g.ntiles;
     g.G = (g.ntiles + tpg - 1) / tpg;
@@ -609,14 +615,15 @@ static inline LongGeo long_geo(int B, int Hp, int Wp, int C, int heads)
     g.rows = g.tpg * TILE_TOK + halo;
     g.waves = 8;
     g.S = g.waves / heads;
-    g.lds_out = sizeof(float) * ((size_t)(g.rows + 1) * (C + DPAD) + 12 * (size_t)C);      // rows of d, 9 + 1 rows of pe taps / bias, the q biases, kbar
-    // first kernel: 16 waves, as few ranges per image as keeps a wave's serial tiles short (every range's partial is read by every workgroup of the second)
-    g.SA = 16 / heads;
+    g.lds_out = sizeof(float) * ((size_t)(g.rows + 1) * (C + DPAD) + small);      // rows of d, 9 + 1 rows of pe taps / bias, the q biases, kbar
+    // first kernel: 16 waves (wide: 8), as few ranges per image as keeps a wave's serial tiles short (every range's partial is read by every workgroup of the second)
+    const int wavesA = wide ? 8 : 16;
+    g.SA = wavesA / heads;
     g.GA = (g.ntiles + 63) / 64;
     g.tpgA = (g.ntiles + g.GA - 1) / g.GA;
     g.GA = (g.ntiles + g.tpgA - 1) / g.tpgA;
-    g.lds_kv = sizeof(float) * 16 * (size_t)PART_FLOATS;
-    g.ws_bytes = sizeof(float) * (size_t)B * g.GA * heads * PART_FLOATS;
+    g.lds_kv = sizeof(float) * wavesA * (size_t)part;
+    g.ws_bytes = sizeof(float) * (size_t)B * g.GA * heads * part;
     return g;
 }
 
@@ -785,46 +792,560 @@ k_recattn_out(const float* __restrict__ d, const bf16_t* __restrict__ wqk, const
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// WIDE heads: head dimension 36 .. 64 in steps of 4, 2 / 4 / 8 heads (round 8: RecNeXt-A5, 40 channels per head).  A head no longer fits one 32 x 32
+// tile: inside the matrix products it is 64 wide, TWO channel tiles (c = 32 a + r, a = 0, 1), and kv = k^T v is 2 x 2 tiles of v_mfma_f32_32x32x16_bf16
+// (64 accumulator registers) held by the head's one wave.  The padding is in REGISTERS only -- the weights of a padded channel read 0 (buffer loads past
+// the pack), its q / k bias is -100 (elu1 -> 0: it neither projects nor normalises), its v is 0 -- while every LDS image keeps the TRUE width:
+// d / x rows of C + DPAD floats (C = D heads; the DPAD columns are zeros), the pe taps and bias C wide, only the q biases and kbar 64 per head.
+// 8 heads of 40 on the 7 x 7 plane: 121 872 B of LDS, where 64-wide images would take 191 760.  The projections sum over the half's C / 2 compact inputs
+// in ceil(C / 32) k-steps (a run-time loop, the next step's fragments requested before the current step's products); inputs past C / 2 meet zero weights.
+// The same data flow as the 32-wide kernels above otherwise: k with the channel on the lane, q^T with the token on the lane, out^T = kv^T q^T.
+
+// the 8 bf16 weights of output row `row` (Kg compact inputs per row), inputs i .. i + 7 of its half: a padding row or inputs past the half read 0
+// (two 8-byte requests: a row of C / 2 bf16 is 8-byte aligned only)
+__device__ __forceinline__ bf16x8 wfrag_w(__amdgpu_buffer_rsrc_t wsrc, int row, bool rvalid, int i, int Kg)
+{
+    const int base = (row * Kg + i) * 2;
+    const u32x2q lo = __builtin_bit_cast(u32x2q, __builtin_amdgcn_raw_buffer_load_b64(wsrc, rvalid && i < Kg ? base : -16, 0, 0));
+    const u32x2q hi = __builtin_bit_cast(u32x2q, __builtin_amdgcn_raw_buffer_load_b64(wsrc, rvalid && i + 4 < Kg ? base + 8 : -16, 0, 0));
+    return __builtin_bit_cast(bf16x8, u32x4q{lo.x, lo.y, hi.x, hi.y});
+}
+
+// LDS after the rows of d: small_floats_w
+__device__ __forceinline__ void stage_small_w(float* Lw, const float* __restrict__ wpe, const float* __restrict__ bpe, const float* __restrict__ bqk,
+                                              int C, int D, int heads, int nthr)
+{
+    float4* L4 = reinterpret_cast<float4*>(Lw);
+    const float4* w4 = reinterpret_cast<const float4*>(wpe);
+    for (int i = threadIdx.x; i < 9 * C / 4; i += nthr) L4[i] = w4[i];
+    for (int i = threadIdx.x; i < C / 4; i += nthr) L4[9 * C / 4 + i] = bpe ? reinterpret_cast<const float4*>(bpe)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = threadIdx.x; i < 64 * heads; i += nthr) {
+        const int hd = i >> 6, c = i & 63;
+        Lw[10 * C + i] = c < D ? bqk[hd * D + c] : QK_PAD_BIAS;
+    }
+}
+
+// the DPAD columns of rows 0 .. rows of a staged image (the k half's last k-step reads into them: finite values times zero weights) and row `rows`: zeros
+__device__ __forceinline__ void zero_pad_w(float* Ld, int rows, int C, int DROW, int nthr)
+{
+    for (int i = threadIdx.x; i <= rows; i += nthr) *reinterpret_cast<float4*>(Ld + (size_t)i * DROW + C) = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = threadIdx.x; i < C / 4; i += nthr) reinterpret_cast<float4*>(Ld + (size_t)rows * DROW)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// k v^T of one 32-token tile of a wide head into the 2 x 2 kv tiles: ak[a] = k pre-activation (channel 32 a + r on the lane, tokens in the registers),
+// vv[b][i] = v of channel 32 b + r at the token of register i (0 for a padding channel)
+__device__ __forceinline__ void kv_tile_w(f32x16 (&kv)[2][2], float (&ksum)[2], const f32x16 (&ak)[2], const float (&vv)[2][16], const float (&bk)[2], int tt, int n, int h)
+{
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+        bf16x8 fa[2], fb[2];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = 8 * s2 + j, t = 32 * tt + acc_row(i, h);
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                const float kk = t < n ? elu1(ak[a][i] + bk[a]) : 0.f;
+                ksum[a] += kk;
+                fa[a][j] = (__bf16)kk;
+                fb[a][j] = (__bf16)vv[a][i];
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) kv[a][bb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[a], fb[bb], kv[a][bb], 0, 0, 0);
+    }
+}
+
+// q^T of one 32-token tile (lane = token t, rows c1 = 32 a + acc_row(i, h) in the registers) from the LDS row of t: NS k-steps over the q half's Kg inputs
+__device__ __forceinline__ void q_tile_w(f32x16 (&aq)[2], __amdgpu_buffer_rsrc_t wsrc, const float* drow, int r0, bool v0, bool v1, int h, int Kg, int NS)
+{
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) aq[a][i] = 0.f;
+    bf16x8 w0 = wfrag_w(wsrc, r0, v0, 8 * h, Kg), w1 = wfrag_w(wsrc, r0 + 32, v1, 8 * h, Kg);
+    f32x4q x0 = *reinterpret_cast<const f32x4q*>(drow + 8 * h), x1 = *reinterpret_cast<const f32x4q*>(drow + 8 * h + 4);
+    for (int s = 0; s < NS; ++s) {
+        const bf16x8 c0 = w0, c1 = w1, fb = to_bf16x8(x0, x1);
+        const int i = 16 * (s + 1) + 8 * h;                          // the next step (past the half: zero weights; the LDS row goes on into the k half)
+        w0 = wfrag_w(wsrc, r0, v0, i, Kg);
+        w1 = wfrag_w(wsrc, r0 + 32, v1, i, Kg);
+        if (s + 1 < NS) { x0 = *reinterpret_cast<const f32x4q*>(drow + i); x1 = *reinterpret_cast<const f32x4q*>(drow + i + 4); }
+        aq[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c0, fb, aq[0], 0, 0, 0);
+        aq[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c1, fb, aq[1], 0, 0, 0);
+    }
+}
+
+// kv (the 2 x 2 tiles, already / n) as bf16 A operands: kvb[a][b][s] = registers 8 s .. 8 s + 7 of tile (a, b)
+__device__ __forceinline__ void kv_operands_w(bf16x8 (&kvb)[2][2][2], const f32x16 (&kv)[2][2], float inv_n)
+{
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { kvb[a][bb][0][j] = (__bf16)(kv[a][bb][j] * inv_n); kvb[a][bb][1][j] = (__bf16)(kv[a][bb][8 + j] * inv_n); }
+}
+
+// the end of a 32-token tile of a wide head: bias + activation, the normaliser over the 64 (padded) c1, out^T = kv^T q^T as 2 x 2 products, pe and the
+// 16-byte stores of the channels that exist.  Every pointer is at the head's first channel: drow / zrow = LDS rows (token t / zeros) of DROW floats,
+// Lw = the pe taps ([9][C] then the bias), Lbq / Lkb = the head's 64 q biases / kbar, outp = the image's output
+__device__ __forceinline__ void out_epilogue_w(const f32x16 (&aq)[2], const bf16x8 (&kvb)[2][2][2], const float* Lbq, const float* Lkb, const float* drow,
+                                               const float* zrow, const float* Lw, int t, int n, int Wp, int h, float* outp, int C, int DROW, int D)
+{
+    float dpart = 0.f;
+    bf16x8 q[2][2];
+    int hop = 4 * h;                               // opaque, as in out_epilogue
+    asm volatile("" : "+v"(hop));
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c1 = 32 * a + acc_row(i, 0) + hop;
+            const float qq = elu1(aq[a][i] + Lbq[c1]);
+            dpart = fmaf(qq, Lkb[c1], dpart);
+            q[a][i >> 3][i & 7] = (__bf16)qq;
+        }
+    const float dn = dpart + __shfl_xor(dpart, 32) + 1e-6f;
+    f32x16 o[2];
+#pragma unroll
+    for (int bb = 0; bb < 2; ++bb) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[bb][i] = 0.f;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {                                     // out^T[c2][t] = sum_c1 kv[c1][c2] q^T[c1][t]
+            o[bb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kvb[a][bb][0], q[a][0], o[bb], 0, 0, 0);
+            o[bb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kvb[a][bb][1], q[a][1], o[bb], 0, 0, 0);
+        }
+    }
+    if (t < n) {
+        const float rdn = 1.f / dn;
+        const int y = t / Wp, x = t - y * Wp;
+        const float* nb[9];
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const bool wrap = (dx < 0 && x == 0) || (dx > 0 && x == Wp - 1);
+                nb[(dy + 1) * 3 + dx + 1] = wrap ? zrow : drow + (dy * Wp + dx) * DROW;
+            }
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const int c = 32 * bb + 8 * gq + 4 * h;                  // the lane's channels c .. c + 3 (D % 4 == 0: all of them exist or none)
+                if (c < D) {
+                    f32x4q pe = *reinterpret_cast<const f32x4q*>(Lw + 9 * C + c);
+#pragma unroll
+                    for (int j = 0; j < 9; ++j)
+                        pe = __builtin_elementwise_fma(*reinterpret_cast<const f32x4q*>(Lw + j * C + c), *reinterpret_cast<const f32x4q*>(nb[j] + c), pe);
+                    const f32x4q ov = {o[bb][4 * gq + 0], o[bb][4 * gq + 1], o[bb][4 * gq + 2], o[bb][4 * gq + 3]};
+                    *reinterpret_cast<f32x4q*>(outp + (size_t)t * C + c) = __builtin_elementwise_fma(ov, f32x4q{rdn, rdn, rdn, rdn}, pe);
+                }
+            }
+    }
+}
+
+// SHORT sequences (at most 64 tokens), one launch: a workgroup = one image, a wave = one head, as k_recattn_short.  XW > 0: d = conv5 stride 2 (x) + bias
+// from the image's XW x XW plane of 16-bit x, one lane per channel forming every output row (the 32-wide form's two lanes per channel assume 32-wide heads).
+template <int NT, int KS, int XW = 0, typename TX = bf16_t>
+__global__ void __launch_bounds__(64 * KS)
+k_recattn_short_w(const float* __restrict__ d, const bf16_t* __restrict__ wqk, const float* __restrict__ bqk, const float* __restrict__ wpe,
+                  const float* __restrict__ bpe, float* __restrict__ out, int Hp, int Wp,
+                  const TX* __restrict__ x, const float* __restrict__ wdn, const float* __restrict__ bdn, int D)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds_sw[];
+    constexpr int NTHR = 64 * KS;
+    const int hd = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int b = blockIdx.x, n = Hp * Wp, rows = NT * 32 + 2 * Wp + 2, R0 = -Wp - 1;
+    const int C = KS * D, Kg = C / 2, DROW = C + DPAD, NS = (Kg + 15) / 16;
+    float* const Ld = lds_sw;                                 // [rows + 1][DROW]: tokens R0 .. of the image (zeros outside it), then a row of zeros
+    float* const Lw = Ld + (size_t)(rows + 1) * DROW;
+    if constexpr (XW == 0) {
+        const __amdgpu_buffer_rsrc_t dsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(d + (size_t)b * n * C), 0, n * C * 4, 0x00020000);
+        stage_rows<NT == 2 ? 12 : 6>(Ld, dsrc, R0, rows, C, 32, KS, DROW, NTHR);      // (D = 32: the compact layout as it stands)
+        zero_pad_w(Ld, rows, C, DROW, NTHR);
+    } else {
+        constexpr int WO = (XW + 1) / 2;
+        const int DROW4 = DROW / 4, tok0 = Wp + 1, tok1 = Wp + 1 + n;
+        float4* L4 = reinterpret_cast<float4*>(lds_sw);
+        for (int i = threadIdx.x; i < (rows + 1) * DROW4; i += NTHR) {          // rows that are not tokens and the DPAD column: zeros
+            const int row = i / DROW4;
+            if (row < tok0 || row >= tok1 || i - row * DROW4 == DROW4 - 1) L4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        for (int c = threadIdx.x; c < C; c += NTHR) {
+            const TX* xc = x + (size_t)b * XW * XW * C + c;
+            float wt[25];
+#pragma unroll
+            for (int j = 0; j < 25; ++j) wt[j] = wdn[j * C + c];
+            const float bias = bdn ? bdn[c] : 0.f;
+            float a[WO][WO];
+#pragma unroll
+            for (int o = 0; o < WO; ++o)
+#pragma unroll
+                for (int j = 0; j < WO; ++j) a[o][j] = bias;
+#pragma unroll
+            for (int y = 0; y < XW; ++y) {
+                float xr[XW];
+#pragma unroll
+                for (int xx = 0; xx < XW; ++xx) xr[xx] = elem_to_f32(xc[(size_t)(y * XW + xx) * C]);
+#pragma unroll
+                for (int o = 0; o < WO; ++o) {
+                    const int dy = y - 2 * o + 2;
+                    if (dy >= 0 && dy < 5) {
+#pragma unroll
+                        for (int j = 0; j < WO; ++j)
+#pragma unroll
+                            for (int dx = 0; dx < 5; ++dx) {
+                                const int xx = 2 * j - 2 + dx;
+                                if (xx >= 0 && xx < XW) a[o][j] = fmaf(wt[dy * 5 + dx], xr[xx], a[o][j]);
+                            }
+                    }
+                }
+            }
+#pragma unroll
+            for (int o = 0; o < WO; ++o)
+#pragma unroll
+                for (int j = 0; j < WO; ++j) Ld[(size_t)(Wp + 1 + o * Wp + j) * DROW + c] = a[o][j];
+        }
+    }
+    stage_small_w(Lw, wpe, bpe, bqk, C, D, KS, NTHR);
+    __syncthreads();
+
+    const __amdgpu_buffer_rsrc_t wsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wqk, 0, 2 * C * Kg * 2, 0x00020000);
+    const int r0 = hd * D + r;                                // the lane's channel of tile 0 (tile 1: + 32)
+    const bool v0 = r < D, v1 = r + 32 < D;
+    const float bk[2] = {v0 ? bqk[C + r0] : QK_PAD_BIAS, v1 ? bqk[C + r0 + 32] : QK_PAD_BIAS};
+    // ---- 1. k (lane = channel), kv
+    f32x16 acc[NT][2];
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[tt][a][i] = 0.f;
+    {
+        bf16x8 w0 = wfrag_w(wsrc, C + r0, v0, 8 * h, Kg), w1 = wfrag_w(wsrc, C + r0 + 32, v1, 8 * h, Kg);
+        f32x4q xf[NT][2];
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt) {
+            const float* pa = Ld + (size_t)(32 * tt + r - R0) * DROW + Kg + 8 * h;
+            xf[tt][0] = *reinterpret_cast<const f32x4q*>(pa); xf[tt][1] = *reinterpret_cast<const f32x4q*>(pa + 4);
+        }
+        for (int s = 0; s < NS; ++s) {
+            const bf16x8 c0 = w0, c1 = w1;
+            bf16x8 fa[NT];
+#pragma unroll
+            for (int tt = 0; tt < NT; ++tt) fa[tt] = to_bf16x8(xf[tt][0], xf[tt][1]);
+            const int i = 16 * (s + 1) + 8 * h;
+            w0 = wfrag_w(wsrc, C + r0, v0, i, Kg);
+            w1 = wfrag_w(wsrc, C + r0 + 32, v1, i, Kg);
+            if (s + 1 < NS) {
+#pragma unroll
+                for (int tt = 0; tt < NT; ++tt) {
+                    const float* pa = Ld + (size_t)(32 * tt + r - R0) * DROW + Kg + i;
+                    xf[tt][0] = *reinterpret_cast<const f32x4q*>(pa); xf[tt][1] = *reinterpret_cast<const f32x4q*>(pa + 4);
+                }
+            }
+#pragma unroll
+            for (int tt = 0; tt < NT; ++tt) {
+                acc[tt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tt], c0, acc[tt][0], 0, 0, 0);
+                acc[tt][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tt], c1, acc[tt][1], 0, 0, 0);
+            }
+        }
+    }
+    f32x16 kv[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) kv[a][bb][i] = 0.f;
+    float ksum[2] = {0.f, 0.f};
+    const float* const Lv = Ld + hd * D + r;                  // v of the lane's channel (tile 1: + 32; a padding channel reads a neighbour and is zeroed)
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt) {
+        float vv[2][16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float* pv = Lv + (size_t)(32 * tt + acc_row(i, h) - R0) * DROW;
+            vv[0][i] = v0 ? pv[0] : 0.f;
+            vv[1][i] = v1 ? pv[32] : 0.f;
+        }
+        kv_tile_w(kv, ksum, acc[tt], vv, bk, tt, n, h);
+    }
+    const float inv_n = 1.f / (float)n;
+    float* const Lbq = Lw + 10 * C + hd * 64;
+    float* const Lkb = Lw + 10 * C + 64 * KS + hd * 64;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const float kbar = (ksum[a] + __shfl_xor(ksum[a], 32)) * inv_n;
+        if (h == 0) Lkb[32 * a + r] = kbar;
+    }
+    bf16x8 kvb[2][2][2];
+    kv_operands_w(kvb, kv, inv_n);
+    wave_sync();
+    // ---- 2. q^T tiles (lane = token), epilogue
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt) {
+        const int t = 32 * tt + r;
+        const float* drow = Ld + (size_t)(t - R0) * DROW;
+        f32x16 aq[2];
+        q_tile_w(aq, wsrc, drow, r0, v0, v1, h, Kg, NS);
+        out_epilogue_w(aq, kvb, Lbq, Lkb, drow + hd * D, Ld + (size_t)rows * DROW + hd * D, Lw + hd * D, t, n, Wp, h,
+                       out + (size_t)b * n * C + hd * D, C, DROW, D);
+    }
+}
+
+static inline size_t short_lds_bytes_w(int NT, int Wp, int C, int heads)
+{
+    return sizeof(float) * ((size_t)(NT * 32 + 2 * Wp + 3) * (C + DPAD) + small_floats_w(C, heads));
+}
+
+// LONG sequences, two launches as k_recattn_kv / k_recattn_out, 8 waves a workgroup (the 2 x 2 kv tiles, the k tile pair and v take ~150 registers: 16 waves
+// would leave 128).  k_recattn_kv_w: a wave = (head, split), partials of PART_W floats per (image, range, head) summed in split order in LDS.
+template <int KS>
+__global__ void __launch_bounds__(512)
+k_recattn_kv_w(const float* __restrict__ d, const bf16_t* __restrict__ wqk, const float* __restrict__ bqk, float* __restrict__ part,
+               int n, int D, int S, int tpg, int ntiles)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds_kvw[];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int hd = wv % KS, sp = wv / KS;
+    const int g = blockIdx.x, b = blockIdx.y, G = gridDim.x;
+    const int C = KS * D, Kg = C / 2, NS = (Kg + 15) / 16;
+    const __amdgpu_buffer_rsrc_t dsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(d + (size_t)b * n * C), 0, n * C * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wqk, 0, 2 * C * Kg * 2, 0x00020000);
+    const int r0 = hd * D + r;
+    const bool v0 = r < D, v1 = r + 32 < D;
+    const float bk[2] = {v0 ? bqk[C + r0] : QK_PAD_BIAS, v1 ? bqk[C + r0 + 32] : QK_PAD_BIAS};
+    const unsigned vl0 = v0 ? 4u * (4 * h * C + r0) : 0x80000000u, vl1 = v1 ? 4u * (4 * h * C + r0 + 32) : 0x80000000u;   // v (padding: past the buffer, 0)
+    f32x16 kv[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) kv[a][bb][i] = 0.f;
+    float ksum[2] = {0.f, 0.f};
+    const int t_end = min((g + 1) * tpg, ntiles);
+    for (int tt = g * tpg + sp; tt < t_end; tt += S) {
+        float vv[2][16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const unsigned row = (unsigned)((32 * tt + acc_row(i, 0)) * C) * 4u;
+            vv[0][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dsrc, (int)(row + vl0), 0, 0));
+            vv[1][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dsrc, (int)(row + vl1), 0, 0));
+        }
+        f32x16 ak[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) ak[a][i] = 0.f;
+        // token 32 tt + r, inputs Kg + 16 s + 8 h .. + 7 (past the half: the next token's row or past the buffer, times zero weights)
+        const unsigned trow = (unsigned)((32 * tt + r) * C + Kg + 8 * h) * 4u;
+        bf16x8 w0 = wfrag_w(wsrc, C + r0, v0, 8 * h, Kg), w1 = wfrag_w(wsrc, C + r0 + 32, v1, 8 * h, Kg);
+        f32x4q x0 = __builtin_bit_cast(f32x4q, __builtin_amdgcn_raw_buffer_load_b128(dsrc, (int)trow, 0, 0));
+        f32x4q x1 = __builtin_bit_cast(f32x4q, __builtin_amdgcn_raw_buffer_load_b128(dsrc, (int)(trow + 16u), 0, 0));
+        for (int s = 0; s < NS; ++s) {
+            const bf16x8 c0 = w0, c1 = w1, fa = to_bf16x8(x0, x1);
+            const int i = 16 * (s + 1) + 8 * h;
+            w0 = wfrag_w(wsrc, C + r0, v0, i, Kg);
+            w1 = wfrag_w(wsrc, C + r0 + 32, v1, i, Kg);
+            x0 = __builtin_bit_cast(f32x4q, __builtin_amdgcn_raw_buffer_load_b128(dsrc, (int)(trow + 64u * (s + 1)), 0, 0));
+            x1 = __builtin_bit_cast(f32x4q, __builtin_amdgcn_raw_buffer_load_b128(dsrc, (int)(trow + 64u * (s + 1) + 16u), 0, 0));
+            ak[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, c0, ak[0], 0, 0, 0);
+            ak[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, c1, ak[1], 0, 0, 0);
+        }
+        kv_tile_w(kv, ksum, ak, vv, bk, tt, n, h);
+    }
+    float* mine = lds_kvw + (size_t)wv * PART_W;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) mine[((2 * a + bb) * 16 + i) * 64 + lane] = kv[a][bb][i];
+        mine[(64 + a) * 64 + lane] = ksum[a];
+    }
+    __syncthreads();
+    if (sp == 0) {
+        float* dst = part + (((size_t)b * G + g) * KS + hd) * PART_W;
+        for (int i = 0; i < PART_W / 64; ++i) {
+            float a = 0.f;
+            for (int q = 0; q < S; ++q) a += lds_kvw[(size_t)(q * KS + hd) * PART_W + i * 64 + lane];
+            dst[i * 64 + lane] = a;
+        }
+    }
+}
+
+// k_recattn_out_w: stages the range's rows of d (+ halo) at the true width, sums the GA partials of the wave's head, q^T per tile, the shared epilogue
+template <int KS>
+__global__ void __launch_bounds__(512)
+k_recattn_out_w(const float* __restrict__ d, const bf16_t* __restrict__ wqk, const float* __restrict__ bqk, const float* __restrict__ wpe,
+                const float* __restrict__ bpe, const float* __restrict__ part, float* __restrict__ out,
+                int Hp, int Wp, int D, int S, int tpg, int ntiles, int rows, int GA)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds_ow[];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int hd = wv % KS, sp = wv / KS;
+    const int g = blockIdx.x, b = blockIdx.y, n = Hp * Wp;
+    const int C = KS * D, Kg = C / 2, DROW = C + DPAD, NS = (Kg + 15) / 16;
+    const int T0 = g * tpg * TILE_TOK, R0 = T0 - Wp - 1;
+    float* const Ld = lds_ow;
+    float* const Lw = Ld + (size_t)(rows + 1) * DROW;
+    float* const Lbq = Lw + 10 * C + hd * 64;
+    float* const Lkb = Lw + 10 * C + 64 * KS + hd * 64;
+    const __amdgpu_buffer_rsrc_t dsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(d + (size_t)b * n * C), 0, n * C * 4, 0x00020000);
+    stage_rows(Ld, dsrc, R0, rows, C, 32, KS, DROW, 512);
+    __builtin_amdgcn_sched_barrier(0);
+    zero_pad_w(Ld, rows, C, DROW, 512);
+    stage_small_w(Lw, wpe, bpe, bqk, C, D, KS, 512);
+    bf16x8 kvb[2][2][2];
+    {
+        f32x16 kvs[2][2];
+        float ks[2] = {0.f, 0.f};
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) kvs[a][bb][i] = 0.f;
+        for (int q = 0; q < GA; ++q) {
+            const float* src = part + (((size_t)b * GA + q) * KS + hd) * PART_W;
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+#pragma unroll
+                for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) kvs[a][bb][i] += src[((2 * a + bb) * 16 + i) * 64 + lane];
+                ks[a] += src[(64 + a) * 64 + lane];
+            }
+        }
+        const float inv_n = 1.f / (float)n;
+        kv_operands_w(kvb, kvs, inv_n);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const float kbar = (ks[a] + __shfl_xor(ks[a], 32)) * inv_n;
+            if (sp == 0 && h == 0) Lkb[32 * a + r] = kbar;
+        }
+    }
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t wsrc = __builtin_amdgcn_make_buffer_rsrc((void*)wqk, 0, 2 * C * Kg * 2, 0x00020000);
+    const int r0 = hd * D + r;
+    const bool v0 = r < D, v1 = r + 32 < D;
+    const int t_end = min((g + 1) * tpg, ntiles);
+    for (int tt = g * tpg + sp; tt < t_end; tt += S) {
+        const int t = 32 * tt + r;
+        const float* drow = Ld + (size_t)(t - R0) * DROW;
+        f32x16 aq[2];
+        q_tile_w(aq, wsrc, drow, r0, v0, v1, h, Kg, NS);
+        out_epilogue_w(aq, kvb, Lbq, Lkb, drow + hd * D, Ld + (size_t)rows * DROW + hd * D, Lw + hd * D, t, n, Wp, h,
+                       out + (size_t)b * n * C + hd * D, C, DROW, D);
+    }
+}
+
 }  // namespace qkc
 
 // 16-bit-activation callers only (the operands of the products are bf16): heads a power of two up to 16, head dimension as heads_ok() below,
 // 16-byte-aligned d.  ONE launch when the plane has at most 64 tokens and its image (+ halo) fits the CU's LDS (at most 8 heads above 32 tokens);
 // else two launches and a workspace (at most 8 heads).
 static bool pow2_heads(int heads) { return heads > 0 && heads <= 16 && !(heads & (heads - 1)); }
-// head dimension 32, or (round 5) 4 .. 28 in steps of 4 with an even number of heads (a q / k half is whole heads): RecNeXt-A0 / A1 / A2's 20 / 24 / 28.
-// Inside the kernels a head is 32 wide either way (padded): LDS sizes and tile counts follow 32 heads, memory follows C.
+// head dimension 32, or (round 5) 4 .. 28 in steps of 4 with an even number of heads (a q / k half is whole heads): RecNeXt-A0 / A1 / A2's 20 / 24 / 28;
+// inside those kernels a head is 32 wide either way (padded): LDS sizes and tile counts follow 32 heads, memory follows C.  Or (round 8, wide_heads)
+// 36 .. 64 in steps of 4 with 2, 4 or 8 heads: RecNeXt-A5's 40, on the _w kernels, whose LDS images keep the true width C.
+static bool wide_heads(int C, int heads)
+{
+    if (C % heads) return false;
+    const int D = C / heads;
+    return D > 32 && D <= 64 && D % 4 == 0 && (heads == 2 || heads == 4 || heads == 8);
+}
 static bool heads_ok(int C, int heads)
 {
     if (!pow2_heads(heads) || C % heads) return false;
     const int D = C / heads;
-    return D == 32 || (D >= 4 && D < 32 && D % 4 == 0 && heads % 2 == 0);
+    return D == 32 || (D >= 4 && D < 32 && D % 4 == 0 && heads % 2 == 0) || wide_heads(C, heads);
 }
+// the one-launch form: C = the channels in memory
 static bool qkc_short(int Hp, int Wp, int C, int heads)
 {
-    const int n = Hp * Wp;
+    const int n = Hp * Wp, NT = n <= 32 ? 1 : 2;
     if (n > 64 || (n > 32 && heads > 8)) return false;
-    return qkc::short_lds_bytes(n <= 32 ? 1 : 2, Wp, C) <= 160 * 1024;
+    return (wide_heads(C, heads) ? qkc::short_lds_bytes_w(NT, Wp, C, heads) : qkc::short_lds_bytes(NT, Wp, 32 * heads)) <= 160 * 1024;
+}
+static qkc::LongGeo qkc_long_geo(int B, int Hp, int Wp, int C, int heads)
+{
+    return wide_heads(C, heads) ? qkc::long_geo(B, Hp, Wp, C, heads, true) : qkc::long_geo(B, Hp, Wp, 32 * heads, heads);
 }
 bool recattn_qkcore_applicable(int B, int Hp, int Wp, int C, int heads)
 {
     if (!(B > 0 && Hp > 0 && Wp > 0 && heads_ok(C, heads))) return false;
-    if (qkc_short(Hp, Wp, 32 * heads, heads)) return true;
+    if (qkc_short(Hp, Wp, C, heads)) return true;
     if (heads > 8) return false;
     if ((size_t)Hp * Wp * C * 4 >= (size_t)1 << 31 || B > 65535) return false;
-    const qkc::LongGeo g = qkc::long_geo(B, Hp, Wp, 32 * heads, heads);
-    return g.lds_out <= 160 * 1024 && g.G <= 65535;
+    const qkc::LongGeo g = qkc_long_geo(B, Hp, Wp, C, heads);
+    return g.lds_out <= 160 * 1024 && g.lds_kv <= 160 * 1024 && g.G <= 65535;
 }
 
 int recattn_qkcore_launches(int B, int Hp, int Wp, int C, int heads)
 {
     if (!recattn_qkcore_applicable(B, Hp, Wp, C, heads)) return 0;
-    return qkc_short(Hp, Wp, 32 * heads, heads) ? 1 : 2;
+    return qkc_short(Hp, Wp, C, heads) ? 1 : 2;
 }
 
 size_t recattn_qkcore_workspace_bytes(int B, int Hp, int Wp, int C, int heads)
 {
-    if (!recattn_qkcore_applicable(B, Hp, Wp, C, heads) || qkc_short(Hp, Wp, 32 * heads, heads)) return 0;
-    return qkc::long_geo(B, Hp, Wp, 32 * heads, heads).ws_bytes;
+    if (!recattn_qkcore_applicable(B, Hp, Wp, C, heads) || qkc_short(Hp, Wp, C, heads)) return 0;
+    return qkc_long_geo(B, Hp, Wp, C, heads).ws_bytes;
+}
+
+// wide heads (36 .. 64 channels): C = the true channel count throughout
+template <int KS>
+static hipError_t launch_long_w(const float* d, const bf16_t* wqk, const float* bqk, const float* wpe, const float* bpe, float* out, float* ws,
+                                int B, int Hp, int Wp, int C, hipStream_t s)
+{
+    const int D = C / KS;
+    const qkc::LongGeo g = qkc::long_geo(B, Hp, Wp, C, KS, true);
+    {
+        auto kfn = qkc::k_recattn_kv_w<KS>;
+        RCX_SET_LDS_ONCE(kfn, g.lds_kv);
+        hipLaunchKernelGGL(kfn, dim3((unsigned)g.GA, (unsigned)B), dim3(512), g.lds_kv, s, d, wqk, bqk, ws, Hp * Wp, D, g.SA, g.tpgA, g.ntiles);
+    }
+    {
+        auto kfn = qkc::k_recattn_out_w<KS>;
+        RCX_SET_LDS_ONCE(kfn, g.lds_out);
+        hipLaunchKernelGGL(kfn, dim3((unsigned)g.G, (unsigned)B), dim3(512), g.lds_out, s, d, wqk, bqk, wpe, bpe, ws, out, Hp, Wp, D, g.S, g.tpg, g.ntiles, g.rows, g.GA);
+    }
+    return hipGetLastError();
+}
+template <int NT, int KS, int XW = 0, typename TX = bf16_t>
+static hipError_t launch_short_w(const float* d, const void* x, const float* wdn, const float* bdn, const bf16_t* wqk, const float* bqk, const float* wpe,
+                                 const float* bpe, float* out, int B, int Hp, int Wp, int C, hipStream_t s)
+{
+    const size_t lds = qkc::short_lds_bytes_w(NT, Wp, C, KS);
+    auto kfn = qkc::k_recattn_short_w<NT, KS, XW, TX>;
+    RCX_SET_LDS_ONCE(kfn, lds);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)B), dim3(64 * KS), lds, s, d, wqk, bqk, wpe, bpe, out, Hp, Wp, (const TX*)x, wdn, bdn, C / KS);
+    return hipGetLastError();
+}
+template <int KS>
+static hipError_t recattn_qkcore_w(const float* d, const bf16_t* w, const float* bqk, const float* wpe, const float* bpe, float* out, float* ws,
+                                   int B, int Hp, int Wp, int C, hipStream_t s)
+{
+    if (!qkc_short(Hp, Wp, C, KS)) return launch_long_w<KS>(d, w, bqk, wpe, bpe, out, ws, B, Hp, Wp, C, s);
+    return Hp * Wp <= 32 ? launch_short_w<1, KS>(d, nullptr, nullptr, nullptr, w, bqk, wpe, bpe, out, B, Hp, Wp, C, s)
+                         : launch_short_w<2, KS>(d, nullptr, nullptr, nullptr, w, bqk, wpe, bpe, out, B, Hp, Wp, C, s);
+}
+template <int KS>
+static hipError_t recattn_down_qkcore_w(const void* x, const float* wdn, const float* bdn, const bf16_t* w, const float* bqk, const float* wpe, const float* bpe,
+                                        float* out, int B, int H, int C, int x_dt, hipStream_t s)
+{
+    if (H == 14) return x_dt == 1 ? launch_short_w<2, KS, 14, bf16_t>(nullptr, x, wdn, bdn, w, bqk, wpe, bpe, out, B, 7, 7, C, s)
+                                  : launch_short_w<2, KS, 14, f16_t>(nullptr, x, wdn, bdn, w, bqk, wpe, bpe, out, B, 7, 7, C, s);
+    return x_dt == 1 ? launch_short_w<1, KS, 7, bf16_t>(nullptr, x, wdn, bdn, w, bqk, wpe, bpe, out, B, 4, 4, C, s)
+                     : launch_short_w<1, KS, 7, f16_t>(nullptr, x, wdn, bdn, w, bqk, wpe, bpe, out, B, 4, 4, C, s);
 }
 
 // PAD = the head dimension is below 32 (D = C / heads at run time); the D == 32 instantiations keep every offset and mask a compile-time constant
@@ -913,7 +1434,7 @@ static hipError_t launch_unit(const void* x, const float* wdn, const float* bdn,
 
 bool recattn2d_unit_applicable(int B, int H, int W, int C, int heads, int x_dt, int mode)
 {
-    if (mode != 1 || !recattn_down_qkcore_applicable(B, H, W, C, heads, x_dt)) return false;      // (16 heads, 7 x 7 only: two heads per wave -- 16 waves of 128 registers do not hold the final conv)
+    if (mode != 1 || wide_heads(C, heads) || !recattn_down_qkcore_applicable(B, H, W, C, heads, x_dt)) return false;      // (heads above 32 channels: the full image alone does not fit; 16 heads, 7 x 7 only: two heads per wave -- 16 waves of 128 registers do not hold the final conv)
     const int wo = (W + 1) / 2;
     return qkc::short_lds_bytes(wo * wo <= 32 ? 1 : 2, wo, 32 * heads, true) <= 160 * 1024;
 }
@@ -940,19 +1461,27 @@ hipError_t recattn2d_unit(const void* x, const float* wdn, const float* bdn, con
 #undef RCX_UX
 }
 
-// RecAttn2d's stride-2 conv + coarse level in one launch: the 14 x 14 plane with 1 .. 8 heads, the 7 x 7 plane with 1 .. 16; 16-bit x.
+// RecAttn2d's stride-2 conv + coarse level in one launch: the 14 x 14 plane with 1 .. 8 heads, the 7 x 7 plane with 1 .. 16 (wide heads: 2, 4, 8); 16-bit x.
 bool recattn_down_qkcore_applicable(int B, int H, int W, int C, int heads, int x_dt)
 {
     if (!(B > 0 && heads_ok(C, heads) && (x_dt == 1 || x_dt == 2))) return false;
     if (!((H == 14 && W == 14 && heads <= 8) || (H == 7 && W == 7))) return false;
     const int wo = (W + 1) / 2;
-    return qkc_short(wo, wo, 32 * heads, heads);
+    return qkc_short(wo, wo, C, heads);
 }
 
 hipError_t recattn_down_qkcore(const void* x, const float* wdn, const float* bdn, const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe,
                                float* out, int B, int H, int C, int heads, int x_dt, hipStream_t s)
 {
     const bf16_t* w = (const bf16_t*)wqk_bf16;
+    if (wide_heads(C, heads)) {
+        switch (heads) {
+            case 2: return recattn_down_qkcore_w<2>(x, wdn, bdn, w, bqk, wpe, bpe, out, B, H, C, x_dt, s);
+            case 4: return recattn_down_qkcore_w<4>(x, wdn, bdn, w, bqk, wpe, bpe, out, B, H, C, x_dt, s);
+            case 8: return recattn_down_qkcore_w<8>(x, wdn, bdn, w, bqk, wpe, bpe, out, B, H, C, x_dt, s);
+            default: return hipErrorInvalidConfiguration;
+        }
+    }
 #define RCX_DX(KS_)                                                                                                                            \
     (H == 14 ? (x_dt == 1 ? launch_short_x<2, KS_, 14, bf16_t>(x, wdn, bdn, w, bqk, wpe, bpe, out, B, C / heads, s)                                       \
                           : launch_short_x<2, KS_, 14, f16_t>(x, wdn, bdn, w, bqk, wpe, bpe, out, B, C / heads, s))                                       \
@@ -975,7 +1504,16 @@ hipError_t recattn_qkcore(const float* d, const void* wqk_bf16, const float* bqk
                           int B, int Hp, int Wp, int C, int heads, hipStream_t s)
 {
     const bf16_t* w = (const bf16_t*)wqk_bf16;
-    if (qkc_short(Hp, Wp, 32 * heads, heads)) {
+    if (wide_heads(C, heads)) {
+        float* ws = (float*)workspace;
+        switch (heads) {
+            case 2: return recattn_qkcore_w<2>(d, w, bqk, wpe, bpe, out, ws, B, Hp, Wp, C, s);
+            case 4: return recattn_qkcore_w<4>(d, w, bqk, wpe, bpe, out, ws, B, Hp, Wp, C, s);
+            case 8: return recattn_qkcore_w<8>(d, w, bqk, wpe, bpe, out, ws, B, Hp, Wp, C, s);
+            default: return hipErrorInvalidConfiguration;
+        }
+    }
+    if (qkc_short(Hp, Wp, C, heads)) {
         const bool one = Hp * Wp <= 32;
         switch (heads) {                  // = C / 32 = the k-steps of the projection (C / 2 inputs, 16 per step)
             case 1: return one ? launch_short<1, 1>(d, w, bqk, wpe, bpe, out, B, Hp, Wp, C / heads, s) : launch_short<2, 1>(d, w, bqk, wpe, bpe, out, B, Hp, Wp, C / heads, s);

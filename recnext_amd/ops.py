@@ -434,8 +434,8 @@ def linear_attention_core_pe(qpre, kpre, v, w_pe_kkc, b_pe, heads):
 
 
 def recattn_qkcore_supported(c, heads, h, w):
-    """Whether recattn_qkcore has a kernel for this coarse plane (rcx_recattn_qkcore_launches: 1/2/4/8/16 heads of 32 channels, or of 4 .. 28 in fours when heads is even; one launch for
-    planes of at most 64 tokens that fit the LDS, two launches otherwise)."""
+    """Whether recattn_qkcore has a kernel for this coarse plane (rcx_recattn_qkcore_launches: 1/2/4/8/16 heads of 32 channels, or of 4 .. 28 in fours when heads is even, or 2/4/8
+    heads of 36 .. 64 in fours (RecNeXt-A5's 40); one launch for planes of at most 64 tokens that fit the LDS, two launches otherwise)."""
     return _lib.load().rcx_recattn_qkcore_launches(1, h, w, c, heads) > 0
 
 
@@ -464,7 +464,7 @@ def recattn_qkcore(d, wqk_bf16, bqk, w_pe_kkc, b_pe, heads):
 
 def recattn_down_qkcore_supported(c, heads, h, w, x_dtype):
     """Whether RecAttn2d's stride-2 conv + coarse level run as ONE launch from x (rcx_recattn_down_qkcore_fwd: the 14 x 14 and 7 x 7 planes of 16-bit
-    activations, 32-wide heads)."""
+    activations; heads as recattn_qkcore_supported, where the coarse plane's image fits the LDS)."""
     return x_dtype in _DT and _lib.load().rcx_recattn_down_qkcore_supported(1, h, w, c, heads, _DT[x_dtype]) > 0
 
 
@@ -487,7 +487,7 @@ def recattn_down_qkcore(x, w_down_kkc, b_down, wqk_bf16, bqk, w_pe_kkc, b_pe, he
 
 
 def recattn2d_supported(c, heads, h, w, mode, dtype):
-    """Whether RecAttn2d.forward is ONE launch for this plane (rcx_recattn2d_fwd: 14 x 14 / 7 x 7, 1 .. 8 heads of 32, nearest, 16-bit)."""
+    """Whether RecAttn2d.forward is ONE launch for this plane (rcx_recattn2d_fwd: 14 x 14 / 7 x 7, 1 .. 8 heads of 32 (or 4 .. 28; never wider), nearest, 16-bit)."""
     return dtype in _DT and mode in _lib.MODES and _lib.load().rcx_recattn2d_fwd_supported(1, h, w, c, heads, _lib.MODES[mode], _DT[dtype]) > 0
 
 
