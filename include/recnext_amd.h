@@ -328,6 +328,36 @@ size_t rcx_stem_pack_bytes(int CM, int CO);
 int rcx_stem_fwd(const void* x, void* y, const void* w1frag, const float* b1, const void* w2frag, const float* b2, int N, int H, int W, int CM, int CO, int dtype, void* stream);
 
 /*
+ * The token half of a block of the LSNet-style RecNeXt-T / S / B (lsnet/model/recattn.py:226-251, eval mode, every BatchNorm folded):
+ *     r = RepVGGDW(x) = dw3x3(x) + dw1x1(x) + x                (:8-34; ONE biased depthwise 3x3 conv: lk + zero-padded sk + identity at the centre tap)
+ *     t = cat(mixer(r[..., :split]), r[..., split:])            (:226-237, PartialChannelOperation; no slice copy, no concatenation)
+ * The block then returns r + MLP(t) (:249-251), which the caller evaluates.  x, r, t: B x H x W x C NHWC, one dtype (float32, bf16 or f16); r and t
+ * must not alias x or each other.  w_rep / b_rep: the folded RepVGGDW as a (3,3,C) / (C) float32 pack.  Every other pack covers the slice only
+ * (`split` channels): w_*_kkc / b_* are (k,k,split) / (split) float32 packs (rcx_pack_dw_weight / rcx_pack_bias); wqT / wkT are the q and k rows of the
+ * folded 1x1 `qk` conv, transposed to (inputs, outputs) float32, with float32 biases bq / bk.  All pointers non-NULL; x, r, t and every pack 16-byte
+ * aligned; C and split multiples of 4.  float32 arithmetic, each output rounded once at its store, deterministic (fixed-order reductions, no atomics);
+ * two launches: the passthrough channels on a wide grid, the slice on one workgroup per image with all of the mixer's intermediates in LDS.
+ *
+ * rcx_ls_recattn_fwd: mixer = RecAttn2d (:115-127) with one head of `split` channels: d = dw5 stride 2 (w_down), q / k = elu(grouped 1x1 qk(d)) + 1
+ * (q from d's channels [0, split/2), k from [split/2, split)), o = q (k^T v) n^-1 / (q . mean(k) + 1e-6) + pe(d) (LinearAttention1 / 2, :37-86,
+ * which are the same function), then t_s = conv5(r_s + nearest(o)) (w_conv).  wqT / wkT: (split/2, split).  `heads` must be 1; planes whose image
+ * (the fine slice, d, k / q and k^T v in float32) fits the LDS: 28 x 28 at split 32, 14 x 14 at 64, 7 x 7 at 96 and their 256-input counterparts
+ * except 32 x 32.
+ * rcx_ls_la3_fwd: mixer = LinearAttention3 (:89-112) at full resolution: qk = elu(full 1x1 qk(r_s)) + 1, q = its channels [0, split/2), k = [split/2,
+ * split), each split into `heads` heads (the module's own num_heads, i.e. the constructor's / 2), v = r_s split into as many heads of split/heads;
+ * o = q (k^T v) n^-1 / (q . mean(k) + 1e-6) + pe(r_s).  wqT / wkT: (split, split/2).  Planes of at most 64 tokens.
+ * The *_supported queries say whether a shape has a kernel (1 / 0); else the entries return RCX_ERR_UNSUPPORTED.
+ */
+int rcx_ls_recattn_supported(int B, int H, int W, int C, int split, int heads, int dtype);
+int rcx_ls_recattn_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* w_down_kkc, const float* b_down,
+                       const float* wqT, const float* bq, const float* wkT, const float* bk, const float* w_pe_kkc, const float* b_pe,
+                       const float* w_conv_kkc, const float* b_conv, int B, int H, int W, int C, int split, int heads, int dtype, void* stream);
+int rcx_ls_la3_supported(int B, int H, int W, int C, int split, int heads, int dtype);
+int rcx_ls_la3_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* wqT, const float* bq,
+                   const float* wkT, const float* bk, const float* w_pe_kkc, const float* b_pe, int B, int H, int W, int C, int split, int heads,
+                   int dtype, void* stream);
+
+/*
  * Backward of rcx_linear_attention_fwd (the gradients engine.py:48-64 needs through RecAttn2d, model/recattn.py:16-28 / :39-51):
  *   given gout = dL/dout (B x n x C), writes gq = dL/dqpre, gk = dL/dkpre, gv = dL/dv (all B x n x C, `dtype`); dL/dpe = gout is the
  *   caller's.  float32 arithmetic, deterministic (fixed summation order).  C/heads at most 64.

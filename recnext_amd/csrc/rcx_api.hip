@@ -5,6 +5,7 @@
 #include "rcx_launch.h"
 
 #include <cstdarg>
+#include <initializer_list>
 #include <cstdio>
 #include <cstdlib>
 
@@ -1178,6 +1179,63 @@ int rcx_channel_mlp_fwd(const void* z, const void* x, void* y, const void* wfrag
                                          "(192, 384), (256, 512), (320, 640); M C 2 < 2^31)", M, C, H, dtype);
     hipError_t e = rcx::channel_mlp(z, x, y, wfrag, bias, M, C, H, dtype, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_channel_mlp_fwd");
+}
+
+int rcx_ls_recattn_supported(int B, int H, int W, int C, int split, int heads, int dtype)
+{
+    return rcx::ls_recattn_applicable(B, H, W, C, split, heads, dtype) ? 1 : 0;
+}
+
+int rcx_ls_la3_supported(int B, int H, int W, int C, int split, int heads, int dtype)
+{
+    return rcx::ls_la3_applicable(B, H, W, C, split, heads, dtype) ? 1 : 0;
+}
+
+namespace {
+bool any_misaligned(std::initializer_list<const void*> ps)
+{
+    for (const void* p : ps)
+        if ((size_t)p & 15) return true;
+    return false;
+}
+}  // namespace
+
+int rcx_ls_recattn_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* w_down_kkc, const float* b_down,
+                       const float* wqT, const float* bq, const float* wkT, const float* bk, const float* w_pe_kkc, const float* b_pe,
+                       const float* w_conv_kkc, const float* b_conv, int B, int H, int W, int C, int split, int heads, int dtype, void* stream)
+{
+    if (!x || !r || !t || !w_rep || !b_rep || !w_down_kkc || !b_down || !wqT || !bq || !wkT || !bk || !w_pe_kkc || !b_pe || !w_conv_kkc || !b_conv)
+        return fail(RCX_ERR_BAD_ARG, "rcx_ls_recattn_fwd: null pointer");
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || split <= 0 || heads <= 0)
+        return fail(RCX_ERR_BAD_ARG, "non-positive extent B=%d H=%d W=%d C=%d split=%d heads=%d", B, H, W, C, split, heads);
+    if (!known_dtype(dtype)) return fail(RCX_ERR_BAD_ARG, "unknown dtype %d", dtype);
+    if (r == x || t == x || r == t) return fail(RCX_ERR_BAD_ARG, "rcx_ls_recattn_fwd: r and t must alias neither x nor each other");
+    if (any_misaligned({x, r, t, w_rep, b_rep, w_down_kkc, b_down, wqT, bq, wkT, bk, w_pe_kkc, b_pe, w_conv_kkc, b_conv}))
+        return fail(RCX_ERR_BAD_ARG, "rcx_ls_recattn_fwd: every tensor must be 16-byte aligned");
+    if (!rcx::ls_recattn_applicable(B, H, W, C, split, heads, dtype))
+        return fail(RCX_ERR_UNSUPPORTED, "rcx_ls_recattn_fwd: %d x %d plane, C=%d, split=%d, %d heads: one head, C and split multiples of 4, and an image whose slice "
+                                         "mixer fits the LDS", H, W, C, split, heads);
+    hipError_t e = rcx::ls_recattn_fwd(x, r, t, w_rep, b_rep, w_down_kkc, b_down, wqT, bq, wkT, bk, w_pe_kkc, b_pe, w_conv_kkc, b_conv,
+                                       B, H, W, C, split, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rcx_ls_recattn_fwd");
+}
+
+int rcx_ls_la3_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* wqT, const float* bq,
+                   const float* wkT, const float* bk, const float* w_pe_kkc, const float* b_pe, int B, int H, int W, int C, int split, int heads,
+                   int dtype, void* stream)
+{
+    if (!x || !r || !t || !w_rep || !b_rep || !wqT || !bq || !wkT || !bk || !w_pe_kkc || !b_pe) return fail(RCX_ERR_BAD_ARG, "rcx_ls_la3_fwd: null pointer");
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || split <= 0 || heads <= 0)
+        return fail(RCX_ERR_BAD_ARG, "non-positive extent B=%d H=%d W=%d C=%d split=%d heads=%d", B, H, W, C, split, heads);
+    if (!known_dtype(dtype)) return fail(RCX_ERR_BAD_ARG, "unknown dtype %d", dtype);
+    if (r == x || t == x || r == t) return fail(RCX_ERR_BAD_ARG, "rcx_ls_la3_fwd: r and t must alias neither x nor each other");
+    if (any_misaligned({x, r, t, w_rep, b_rep, wqT, bq, wkT, bk, w_pe_kkc, b_pe}))
+        return fail(RCX_ERR_BAD_ARG, "rcx_ls_la3_fwd: every tensor must be 16-byte aligned");
+    if (!rcx::ls_la3_applicable(B, H, W, C, split, heads, dtype))
+        return fail(RCX_ERR_UNSUPPORTED, "rcx_ls_la3_fwd: %d x %d plane, C=%d, split=%d, %d heads: at most 64 tokens, C and split multiples of 4, split a multiple "
+                                         "of 2 heads", H, W, C, split, heads);
+    hipError_t e = rcx::ls_la3_fwd(x, r, t, w_rep, b_rep, wqT, bq, wkT, bk, w_pe_kkc, b_pe, B, H, W, C, split, heads, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rcx_ls_la3_fwd");
 }
 
 int rcx_linear_attention_bwd(const void* qpre, const void* kpre, const void* v, const void* gout, void* gq, void* gk, void* gv,

@@ -185,6 +185,15 @@ hipError_t channel_mlp(const void* z, const void* x, void* y, const void* wfrag,
 bool recattn2d_unit_applicable(int B, int H, int W, int C, int heads, int x_dt, int mode);
 hipError_t recattn2d_unit(const void* x, const float* wdn, const float* bdn, const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe,
                           const float* wcv, const float* bcv, void* y, int B, int H, int C, int heads, int x_dt, hipStream_t s);
+// rcx_lsmix.hip: the token half of an LSNet-style RecNeXt-T / S / B block, x -> (r, t), two launches
+bool ls_recattn_applicable(int B, int H, int W, int C, int split, int heads, int dtype);
+bool ls_la3_applicable(int B, int H, int W, int C, int split, int heads, int dtype);
+hipError_t ls_recattn_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* w_dn, const float* b_dn,
+                          const float* wqT, const float* bq, const float* wkT, const float* bk, const float* w_pe, const float* b_pe,
+                          const float* w_cv, const float* b_cv, int B, int H, int W, int C, int split, int dtype, hipStream_t s);
+hipError_t ls_la3_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* wqT, const float* bq,
+                      const float* wkT, const float* bk, const float* w_pe, const float* b_pe, int B, int H, int W, int C, int split, int heads,
+                      int dtype, hipStream_t s);
 hipError_t recattn_qkcore(const float* d, const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe, float* out, void* workspace,
                           int B, int Hp, int Wp, int C, int heads, hipStream_t s);
 

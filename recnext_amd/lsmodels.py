@@ -1,0 +1,327 @@
+"""The LSNet-style RecNeXt-T / S / B (lsnet/model/recattn.py:8-466): RecAttn2d applied to a quarter of the channels.
+
+Each block computes ``r = RepVGGDW(x)`` (:8-34), ``t = cat(mixer(r[:, :C/4]), r[:, C/4:])`` (:226-237) and returns ``r + MLP(t)`` (:240-251); the
+mixer is RecAttn2d at stages 0-2 (:115-127) and LinearAttention3 at stage 3 (:89-112).  Module and parameter names equal the reference's, so its
+checkpoints load with ``strict=True`` and ``models.replace_batchnorm`` gives the keys of its ``RecNext.fuse()``.
+
+The token half ``x -> (r, t)`` of every block is ONE HIP entry (two launches: ``ops.ls_recattn`` / ``ops.ls_la3``), BatchNorms folded into float32
+packs whether or not ``replace_batchnorm`` has run; where the support query says no and the head is at most 64 wide, the block falls back to the
+HIP depthwise conv and the library's ``RecAttn2d`` on a contiguous slice.  Inference only: a forward in training mode or one that needs a gradient
+raises, as does a CPU tensor.  The stem, Downsample's grouped conv and the classifier are PyTorch-ROCm library operators.
+
+RecAttn2d's ``stage -> LinearAttention1 | 2`` label (:119) is cosmetic: the two are the same function (the reference asserts it, :481-501).
+"""
+import math
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+from .layers import ConvNorm as _ConvNorm
+from .layers import DropPath
+from .recattn import RecAttn2d, _folded, head_dim_supported
+
+# lsnet/model/recattn.py:441-466 (drop_path_rate of the non-distilled recipe; 0 with distillation)
+LS_CONFIGS = {
+    "recnext_t": dict(embed_dim=(64, 128, 256, 512), depth=(0, 2, 8, 10), drop_path_rate=0.0),
+    "recnext_s": dict(embed_dim=(128, 256, 384, 512), depth=(0, 2, 8, 10), drop_path_rate=0.1),
+    "recnext_b": dict(embed_dim=(128, 256, 384, 512), depth=(2, 8, 8, 12), drop_path_rate=0.2),
+}
+_COMMON = dict(mlp_ratios=(2, 2, 2, 1.5), num_heads=(1, 1, 1, 2), split_rates=(4, 4, 4, 4))
+
+
+def ConvNorm(*args, **kwargs):
+    """The family's ConvNorm: the reference's has a conv bias (:130-146), unlike the M / A families'."""
+    kwargs.setdefault("bias", True)
+    return _ConvNorm(*args, **kwargs)
+
+
+def _fold_rep(lk, sk):
+    """RepVGGDW.fuse (:17-34) in float32: lk + zero-padded sk + identity at the centre tap.  Both the fuse and the HIP pack use it, so a folded
+    and an unfolded model run on bit-identical packs."""
+    wl, bl = _folded(lk)
+    ws, bs = _folded(sk)
+    wl, ws = wl.float(), ws.float()
+    ident = F.pad(torch.ones(wl.shape[0], wl.shape[1], 1, 1, device=wl.device), [1, 1, 1, 1])
+    w = wl + F.pad(ws, [1, 1, 1, 1]) + ident
+    zero = torch.zeros(wl.shape[0], device=wl.device)
+    b = (zero if bl is None else bl.float()) + (zero if bs is None else bs.float())
+    return w, b
+
+
+class RepVGGDW(nn.Module):
+    def __init__(self, in_channels):
+        super().__init__()
+        self.lk = ConvNorm(in_channels, in_channels, kernel_size=3, padding=1, groups=in_channels)
+        self.sk = ConvNorm(in_channels, in_channels, kernel_size=1, padding=0, groups=in_channels)
+
+    def forward(self, x):
+        return self.lk(x) + self.sk(x) + x
+
+    @torch.no_grad()
+    def fuse(self):
+        w, b = _fold_rep(self.lk, self.sk)
+        conv = self.lk.conv
+        out = nn.Conv2d(conv.in_channels, conv.out_channels, 3, padding=1, groups=conv.groups, bias=True, device=w.device, dtype=conv.weight.dtype)
+        out.weight.copy_(w)
+        out.bias.copy_(b)
+        return out
+
+
+def _rep_params(m):
+    """(weight (C,1,3,3), bias (C)) in float32 of a RepVGGDW or of its fused nn.Conv2d."""
+    if isinstance(m, nn.Conv2d):
+        return m.weight.float(), m.bias.float()
+    return _fold_rep(m.lk, m.sk)
+
+
+class LsRecAttn2d(RecAttn2d):
+    """The library's RecAttn2d with the family's biased ConvNorms (keys ``down.0.conv.bias`` ... as :115-127).  Stage 0 carries the label
+    LinearAttention1, stages 1-2 LinearAttention2 (:119); the function is the same."""
+
+    def __init__(self, dim, num_heads, kernel_size=5, stage=1, mode="nearest"):
+        super().__init__(dim, num_heads, kernel_size=kernel_size, stage=stage, mode=mode)
+        p = kernel_size // 2
+        self.down[0] = ConvNorm(dim, dim, kernel_size=kernel_size, padding=p, stride=2, groups=dim)
+        la = self.down[1]
+        la.variant = 1 if stage == 0 else 2
+        la.qk = ConvNorm(dim, dim * 2, kernel_size=1, groups=2)
+        la.pe = ConvNorm(dim, dim, kernel_size=3, padding=1, groups=dim)
+        self.conv = ConvNorm(dim, dim, kernel_size=kernel_size, padding=p, groups=dim)
+
+    def _tensors(self):
+        out = super()._tensors()
+        for m in (self.down[0], self.conv, self.down[1].qk, self.down[1].pe):      # the conv biases, which the A family does not have
+            if not isinstance(m, nn.Conv2d) and m.conv.bias is not None:
+                out.append(m.conv.bias)
+        return out
+
+
+class LinearAttention3(nn.Module):
+    """:89-112.  ``num_heads`` is half the constructor's; q and k take ``dim / 2`` channels of the full 1x1 ``qk`` each, v is the input."""
+
+    def __init__(self, dim, num_heads, **kwargs):
+        super().__init__()
+        self.num_heads = num_heads // 2
+        self.head_dim = dim // self.num_heads // 2
+        self.qk = ConvNorm(dim, dim, kernel_size=1, groups=1)
+        self.pe = ConvNorm(dim, dim, kernel_size=3, padding=1, groups=dim)
+
+    def forward(self, x):
+        raise NotImplementedError("LinearAttention3 runs inside MetaNeXtBlock's token half (recnext_amd.ops.ls_la3); it has no kernel of its own")
+
+    def extra_repr(self):
+        return f"num_heads={self.num_heads}, head_dim={self.head_dim}"
+
+
+def default_token_mixer(dim, num_heads, stage):
+    """The slice mixer of a block (:222): RecAttn2d at stages 0-2, LinearAttention3 at stage 3."""
+    if stage >= 3:
+        return LinearAttention3(dim, num_heads=num_heads, stage=stage)
+    return LsRecAttn2d(dim, num_heads=num_heads, stage=stage)
+
+
+class PartialChannelOperation(nn.Module):
+    def __init__(self, in_channels, attn, split_rate=4):
+        super().__init__()
+        assert in_channels % split_rate == 0, "in_channels must be divisible by split_rate"
+        self.split_idx = in_channels // split_rate
+        self.attn = attn
+
+    def forward(self, x):
+        return torch.cat([self.attn(x[:, :self.split_idx]), x[:, self.split_idx:]], dim=1)
+
+
+def mlp(in_channels, hidden_channels, act_layer=nn.GELU):
+    hidden_channels = int(hidden_channels)
+    return nn.Sequential(ConvNorm(in_channels, hidden_channels, kernel_size=1), act_layer(), ConvNorm(hidden_channels, in_channels, kernel_size=1))
+
+
+def _pack_dw(w, b):
+    return ops.pack_dw_weight(w.float().contiguous()), ops.pack_bias(b.float().contiguous())
+
+
+class MetaNeXtBlock(nn.Module):
+    """r = rep_mixer(x); return r + drop_path(channel_mixer(token_mixer(r))) (:240-251).  With the family's own slice mixers the token half runs on HIP."""
+
+    def __init__(self, in_channels, mlp_ratio, num_heads=2, act_layer=nn.GELU, stage=0, block=0, drop_path=0, split_rate=4, token_mixer=None):
+        super().__init__()
+        self.rep_mixer = RepVGGDW(in_channels)
+        attn = (token_mixer or default_token_mixer)(in_channels // split_rate, num_heads, stage)
+        self.token_mixer = PartialChannelOperation(in_channels, attn, split_rate=split_rate)
+        self.channel_mixer = mlp(in_channels, in_channels * mlp_ratio, act_layer=act_layer)
+        self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
+        self._pack_key = None
+        self._pack = None
+
+    def _hip_mixer(self):
+        return isinstance(self.token_mixer, PartialChannelOperation) and type(self.token_mixer.attn) in (LsRecAttn2d, LinearAttention3)
+
+    def _pack_tensors(self):
+        out = [t for t in self.rep_mixer.parameters()] + [t for t in self.rep_mixer.buffers()]
+        out += [t for t in self.token_mixer.attn.parameters()] + [t for t in self.token_mixer.attn.buffers()]
+        return out
+
+    def packed_params(self):
+        """Float32 packs of the token half: the folded RepVGGDW, then the slice mixer's folded convs (q / k rows transposed)."""
+        key = tuple((t.data_ptr(), t._version, t.dtype, t.device) for t in self._pack_tensors())
+        if key != self._pack_key:
+            with torch.no_grad():
+                attn = self.token_mixer.attn
+                s = self.token_mixer.split_idx
+                pack = list(_pack_dw(*_rep_params(self.rep_mixer)))
+                if isinstance(attn, LinearAttention3):
+                    wqk, bqk = _folded(attn.qk)                    # (s, s, 1, 1): rows [0, s/2) = q, [s/2, s) = k
+                    wqk = wqk[:, :, 0, 0].float()
+                    bqk = bqk.float()
+                    pack += [wqk[:s // 2].t().contiguous(), bqk[:s // 2].contiguous(), wqk[s // 2:].t().contiguous(), bqk[s // 2:].contiguous()]
+                    pack += list(_pack_dw(*_folded(attn.pe)))
+                else:
+                    la = attn.down[1]
+                    pack += list(_pack_dw(*_folded(attn.down[0])))
+                    wqk, bqk = _folded(la.qk)                      # (2s, s/2, 1, 1): rows [0, s) = q from channels [0, s/2), [s, 2s) = k from [s/2, s)
+                    wqk = wqk[:, :, 0, 0].float()
+                    bqk = bqk.float()
+                    pack += [wqk[:s].t().contiguous(), bqk[:s].contiguous(), wqk[s:].t().contiguous(), bqk[s:].contiguous()]
+                    pack += list(_pack_dw(*_folded(la.pe)))
+                    pack += list(_pack_dw(*_folded(attn.conv)))
+                self._pack = tuple(pack)
+            self._pack_key = key
+        return self._pack
+
+    def token_half(self, x):
+        """(r, t) on HIP: one entry (two launches) where the support query says yes, else the HIP depthwise conv + the library's RecAttn2d on a
+        contiguous slice (heads of at most 64 channels); raises otherwise."""
+        attn = self.token_mixer.attn
+        s = self.token_mixer.split_idx
+        b, c, h, w = x.shape
+        if self.training or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            raise NotImplementedError("training RecNeXt-T / S / B (or a forward that needs a gradient) is not built yet: run it in eval mode under torch.no_grad()")
+        if not x.is_cuda:
+            raise RuntimeError("recnext_amd's RecNeXt-T / S / B token mixer runs on the GPU only (HIP kernels); the CPU formulation is tests/ls_eager.py")
+        if isinstance(attn, LinearAttention3):
+            if ops.ls_la3_supported(b, h, w, c, s, attn.num_heads, x.dtype):
+                return ops.ls_la3(x, *self.packed_params(), s, attn.num_heads)
+            raise NotImplementedError(f"RecNeXt-T / S / B LinearAttention3: no kernel for a {h} x {w} plane of {c} channels (slice {s}, {attn.num_heads} heads, {x.dtype})")
+        heads = attn.down[1].num_heads
+        if ops.ls_recattn_supported(b, h, w, c, s, heads, x.dtype):
+            return ops.ls_recattn(x, *self.packed_params(), s, heads)
+        if s % heads == 0 and head_dim_supported(s // heads) and x.dtype in ops._DT:
+            wr, br = self.packed_params()[:2]
+            r = ops.dwconv2d(x, wr, br, k=3, stride=1)
+            t = torch.cat([attn(r[:, :s].contiguous(memory_format=torch.channels_last)), r[:, s:]], dim=1)
+            return r, t.contiguous(memory_format=torch.channels_last)
+        raise NotImplementedError(f"RecNeXt-T / S / B RecAttn2d: no kernel for a {h} x {w} plane of {c} channels (slice {s}, {heads} heads of {s // heads}, {x.dtype})")
+
+    def forward(self, x):
+        if self._hip_mixer():
+            r, t = self.token_half(x)
+        else:
+            r = self.rep_mixer(x)
+            t = self.token_mixer(r)
+        fused = self.__dict__.get("_fused_mlp")
+        if fused is not None and not self.training and fused.usable(self.channel_mixer, t, r):
+            return fused(t, r)                              # r + channel_mixer(t) in one launch (models.use_fused_mlp)
+        return r + self.drop_path(self.channel_mixer(t))
+
+
+class Downsample(nn.Module):
+    def __init__(self, in_channels, out_channels, mlp_ratio=2, act_layer=nn.GELU, kernel_size=5, stage=0, drop_path=0):
+        super().__init__()
+        self.token_mixer = ConvNorm(in_channels, out_channels, kernel_size=kernel_size, padding=(kernel_size - 1) // 2, stride=2,
+                                    groups=math.gcd(in_channels, out_channels))
+        self.channel_mixer = mlp(out_channels, out_channels * mlp_ratio, act_layer=act_layer)
+        self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
+
+    def forward(self, x):
+        x = self.token_mixer(x)
+        fused = self.__dict__.get("_fused_mlp")
+        if fused is not None and not self.training and fused.usable(self.channel_mixer, x, x):
+            return fused(x, x)
+        return x + self.drop_path(self.channel_mixer(x))
+
+
+class RecNextStem(nn.Module):
+    def __init__(self, in_channels, out_channels, act_layer=nn.GELU, kernel_size=3, stride=2, additional_activation=False):
+        super().__init__()
+        kw = dict(kernel_size=kernel_size, stride=stride, padding=(kernel_size - 1) // 2)
+        self.stem = nn.Sequential(ConvNorm(in_channels, out_channels // 4, **kw), act_layer(), ConvNorm(out_channels // 4, out_channels // 2, **kw), act_layer(),
+                                  ConvNorm(out_channels // 2, out_channels, **kw), act_layer() if additional_activation else nn.Identity())
+
+    def forward(self, x):
+        return self.stem(x)
+
+
+class RecNextStage(nn.Module):
+    def __init__(self, in_channels, out_channels, depth, mlp_ratio, num_heads=2, act_layer=nn.GELU, downsample=True, stage=0, split_rate=4,
+                 drop_path_rates=None, token_mixer=None):
+        super().__init__()
+        drop_path_rates = drop_path_rates or [0.0] * depth
+        self.downsample = Downsample(in_channels, out_channels, mlp_ratio, act_layer=act_layer, stage=stage,
+                                     drop_path=drop_path_rates[0] if depth else 0.0) if downsample else nn.Identity()
+        self.blocks = nn.Sequential(*[MetaNeXtBlock(out_channels, mlp_ratio, num_heads=num_heads, act_layer=act_layer, stage=stage, block=i,
+                                                    drop_path=drop_path_rates[i], split_rate=split_rate, token_mixer=token_mixer) for i in range(depth)])
+
+    def forward(self, x):
+        return self.blocks(self.downsample(x))
+
+
+class RecNext(nn.Module):
+    def __init__(self, in_chans=3, embed_dim=(48,), depth=(2,), mlp_ratios=(2,), num_heads=(2,), global_pool="avg", num_classes=1000, act_layer=nn.GELU,
+                 distillation=False, split_rates=(4,), drop_rate=0.0, drop_path_rate=0.0, token_mixer=None):
+        from .models import RecNextClassifier
+        super().__init__()
+        self.global_pool = global_pool
+        self.embed_dim = tuple(embed_dim)
+        self.num_classes = num_classes
+        in_channels = embed_dim[0]
+        self.stem = RecNextStem(in_chans, in_channels, act_layer=act_layer, additional_activation=depth[0] == 0)
+        dpr = [x.tolist() for x in torch.linspace(0, drop_path_rate, sum(depth)).split(list(depth))]
+        stages = []
+        for i in range(len(embed_dim)):
+            stages.append(RecNextStage(in_channels, embed_dim[i], depth[i], mlp_ratio=mlp_ratios[i], num_heads=num_heads[i], act_layer=act_layer,
+                                       downsample=i != 0, stage=i, split_rate=split_rates[i], drop_path_rates=dpr[i], token_mixer=token_mixer))
+            in_channels = embed_dim[i]
+        self.stages = nn.Sequential(*stages)
+        self.num_features = embed_dim[-1]
+        self.head_drop = nn.Dropout(drop_rate)
+        self.head = RecNextClassifier(embed_dim[-1], num_classes, distillation)
+
+    def forward_features(self, x):
+        return self.stages(self.stem(x))
+
+    def forward_head(self, x):
+        if self.global_pool == "avg":
+            x = x.mean((2, 3))
+        return self.head(self.head_drop(x))
+
+    def forward(self, x):
+        return self.forward_head(self.forward_features(x))
+
+
+def create_model(name, distillation=False, token_mixer=None, **overrides):
+    """recnext_t / _s / _b (:441-466).  ``token_mixer(dim, num_heads, stage)`` replaces the slice mixer (tests host tests/ls_eager.py's restatement)."""
+    cfg = dict(_COMMON, **LS_CONFIGS[name])
+    if distillation:
+        cfg["drop_path_rate"] = 0.0
+    cfg.update(overrides)
+    return RecNext(distillation=distillation, token_mixer=token_mixer, **cfg)
+
+
+def mixer_shapes(name, resolution=224):
+    """[(stage, H, W, C, split, heads, kind, blocks)] of every block's token half in one forward (kind 'recattn' | 'la3'; heads as the entries take them)."""
+    cfg = dict(_COMMON, **LS_CONFIGS[name])
+    side = resolution
+    for _ in range(3):
+        side = (side + 1) // 2                                  # the stem: three 3x3 stride-2 convs
+    out = []
+    for i, (c, d) in enumerate(zip(cfg["embed_dim"], cfg["depth"])):
+        if i:
+            side = (side + 1) // 2                              # Downsample: 5x5 stride 2, padding 2
+        if d:
+            split = c // cfg["split_rates"][i]
+            kind = "la3" if i >= 3 else "recattn"
+            heads = cfg["num_heads"][i] // 2 if kind == "la3" else cfg["num_heads"][i]
+            out.append((i, side, side, c, split, heads, kind, d))
+    return out

@@ -184,12 +184,23 @@ class RecNext(nn.Module):
 
 
 def create_model(name, distillation=False, token_mixer=None, **overrides):
-    """``timm.create_model`` stand-in for the twelve registered names (model/recnext.py:365-407, model/recattn.py:378-420)."""
+    """``timm.create_model`` stand-in for the twelve registered names (model/recnext.py:365-407, model/recattn.py:378-420) and the LSNet-style
+    recnext_t / _s / _b (lsnet/model/recattn.py:441-466, built by recnext_amd.lsmodels; ``token_mixer(dim, num_heads, stage)`` there)."""
+    if name not in CONFIGS:
+        from . import lsmodels
+        if name in lsmodels.LS_CONFIGS:
+            return lsmodels.create_model(name, distillation=distillation, token_mixer=token_mixer, **overrides)
     cfg = dict(CONFIGS[name])
     if distillation:
         cfg["drop_path"] = 0.0                      # drop_path applies to the non-distilled recipe only
     cfg.update(overrides)
     return RecNext(distillation=distillation, token_mixer=token_mixer, **cfg)
+
+
+def _mlp_hosts():
+    """The module types whose ``channel_mixer`` the pointwise / fused-MLP passes rewrite: the M / A families' and the T / S / B family's blocks and Downsamples."""
+    from . import lsmodels
+    return (MetaNeXtBlock, Downsample, lsmodels.MetaNeXtBlock, lsmodels.Downsample)
 
 
 def replace_batchnorm(net):
@@ -252,7 +263,7 @@ def use_linear_pointwise(net):
     from .layers import PointwiseLinear
     n = 0
     for m in net.modules():
-        if isinstance(m, (MetaNeXtBlock, Downsample)):
+        if isinstance(m, _mlp_hosts()):
             seq = m.channel_mixer
             for i, sub in enumerate(seq):
                 if isinstance(sub, nn.Conv2d) and sub.kernel_size == (1, 1) and sub.groups == 1 and sub.bias is not None:
@@ -286,7 +297,7 @@ def use_fused_mlp(net):
     from .layers import FusedChannelMlp, PointwiseLinear
     n = 0
     for m in net.modules():
-        if isinstance(m, (MetaNeXtBlock, Downsample)) and m.__dict__.get("_fused_mlp") is None:
+        if isinstance(m, _mlp_hosts()) and m.__dict__.get("_fused_mlp") is None:
             seq = m.channel_mixer
             if len(seq) == 3 and isinstance(seq[0], PointwiseLinear) and isinstance(seq[2], PointwiseLinear) and isinstance(seq[1], nn.GELU) \
                     and getattr(seq[1], "approximate", "none") == "none":            # (drop_path is the identity in eval mode, the only mode the fused path runs in)
@@ -311,7 +322,7 @@ def pad_mlp_hidden(net):
     from .layers import PointwiseLinear
     n = 0
     for m in net.modules():
-        if isinstance(m, (MetaNeXtBlock, Downsample)):
+        if isinstance(m, _mlp_hosts()):
             seq = m.channel_mixer
             if len(seq) != 3 or not isinstance(seq[0], PointwiseLinear) or not isinstance(seq[2], PointwiseLinear):
                 continue

@@ -509,6 +509,74 @@ def recattn2d(x, w_down_kkc, b_down, wqk_bf16, bqk, w_pe_kkc, b_pe, w_conv_kkc, 
     return y
 
 
+def ls_recattn_supported(b, h, w, c, split, heads, dtype):
+    """Whether rcx_ls_recattn_fwd has a kernel for the token half of an LSNet-style RecNeXt block whose slice mixer is RecAttn2d (one head of `split` channels)."""
+    return dtype in _DT and _lib.load().rcx_ls_recattn_supported(b, h, w, c, split, heads, _DT[dtype]) > 0
+
+
+def ls_la3_supported(b, h, w, c, split, heads, dtype):
+    """Whether rcx_ls_la3_fwd has a kernel for the token half whose slice mixer is LinearAttention3 (`heads` = the module's own num_heads)."""
+    return dtype in _DT and _lib.load().rcx_ls_la3_supported(b, h, w, c, split, heads, _DT[dtype]) > 0
+
+
+def _check_ls_args(fn, x, split, packs):
+    """Shape / dtype / device checks of a token-half entry, before anything is allocated or launched.  packs: (name, tensor, element count)."""
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise ValueError(f"{fn}: x must be a 4-D (N, C, H, W) tensor")
+    if x.dtype not in _DT:
+        raise ValueError(f"{fn}: x must be float32, bfloat16 or float16, got {x.dtype}")
+    _require_gpu(x, "x")
+    c = x.shape[1]
+    if not (0 < split <= c) or split % 4 or c % 4:
+        raise ValueError(f"{fn}: C ({c}) and split ({split}) must be multiples of 4 with 0 < split <= C")
+    for name, t, numel in packs:
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != numel or not t.is_contiguous():
+            raise ValueError(f"{fn}: {name} must be a contiguous float32 tensor of {numel} elements")
+        if t.device != x.device:
+            raise ValueError(f"{fn}: {name} is on {t.device}, x on {x.device}")
+
+
+def ls_recattn(x, w_rep, b_rep, w_down_kkc, b_down, wqT, bq, wkT, bk, w_pe_kkc, b_pe, w_conv_kkc, b_conv, split, heads=1):
+    """The token half of an LSNet-style RecNeXt block whose slice mixer is RecAttn2d (lsnet/model/recattn.py:8-34, :115-127, :226-251; eval, BatchNorms folded):
+    x (N, C, H, W) channels_last -> (r, t), r = RepVGGDW(x), t = cat(RecAttn2d(r[:, :split]), r[:, split:]), both like x.  Packs: w_rep / b_rep the folded
+    RepVGGDW ((3,3,C) / C), the slice's convs as (k,k,split) / split packs, wqT / wkT (split/2, split) the transposed q / k rows of the folded grouped `qk`."""
+    c = x.shape[1] if torch.is_tensor(x) and x.dim() == 4 else 0
+    _check_ls_args("ls_recattn", x, split, [("w_rep", w_rep, 9 * c), ("b_rep", b_rep, c), ("w_down_kkc", w_down_kkc, 25 * split), ("b_down", b_down, split),
+                                            ("wqT", wqT, split * (split // 2)), ("bq", bq, split), ("wkT", wkT, split * (split // 2)), ("bk", bk, split),
+                                            ("w_pe_kkc", w_pe_kkc, 9 * split), ("b_pe", b_pe, split), ("w_conv_kkc", w_conv_kkc, 25 * split), ("b_conv", b_conv, split)])
+    b, _, h, w = x.shape
+    if not ls_recattn_supported(b, h, w, c, split, heads, x.dtype):
+        raise ValueError(f"ls_recattn: no kernel for a {h} x {w} plane, C={c}, split={split}, {heads} heads, {x.dtype} (ls_recattn_supported)")
+    x = _nhwc(x, "x")
+    r = torch.empty_like(x, memory_format=torch.channels_last)
+    t = torch.empty_like(x, memory_format=torch.channels_last)
+    with _on(x.device):
+        rc = _lib.load().rcx_ls_recattn_fwd(x.data_ptr(), r.data_ptr(), t.data_ptr(), w_rep.data_ptr(), b_rep.data_ptr(), w_down_kkc.data_ptr(), b_down.data_ptr(),
+                                            wqT.data_ptr(), bq.data_ptr(), wkT.data_ptr(), bk.data_ptr(), w_pe_kkc.data_ptr(), b_pe.data_ptr(),
+                                            w_conv_kkc.data_ptr(), b_conv.data_ptr(), b, h, w, c, split, heads, _dt(x), _stream(x.device))
+    _lib.check(rc, "rcx_ls_recattn_fwd")
+    return r, t
+
+
+def ls_la3(x, w_rep, b_rep, wqT, bq, wkT, bk, w_pe_kkc, b_pe, split, heads):
+    """The token half whose slice mixer is LinearAttention3 (lsnet/model/recattn.py:89-112; `heads` = the module's own num_heads): x -> (r, t) as ls_recattn.
+    wqT / wkT (split, split/2): the transposed q rows [0, split/2) and k rows [split/2, split) of the folded full 1x1 `qk`."""
+    c = x.shape[1] if torch.is_tensor(x) and x.dim() == 4 else 0
+    _check_ls_args("ls_la3", x, split, [("w_rep", w_rep, 9 * c), ("b_rep", b_rep, c), ("wqT", wqT, split * (split // 2)), ("bq", bq, split // 2),
+                                        ("wkT", wkT, split * (split // 2)), ("bk", bk, split // 2), ("w_pe_kkc", w_pe_kkc, 9 * split), ("b_pe", b_pe, split)])
+    b, _, h, w = x.shape
+    if not ls_la3_supported(b, h, w, c, split, heads, x.dtype):
+        raise ValueError(f"ls_la3: no kernel for a {h} x {w} plane, C={c}, split={split}, {heads} heads, {x.dtype} (ls_la3_supported)")
+    x = _nhwc(x, "x")
+    r = torch.empty_like(x, memory_format=torch.channels_last)
+    t = torch.empty_like(x, memory_format=torch.channels_last)
+    with _on(x.device):
+        rc = _lib.load().rcx_ls_la3_fwd(x.data_ptr(), r.data_ptr(), t.data_ptr(), w_rep.data_ptr(), b_rep.data_ptr(), wqT.data_ptr(), bq.data_ptr(),
+                                        wkT.data_ptr(), bk.data_ptr(), w_pe_kkc.data_ptr(), b_pe.data_ptr(), b, h, w, c, split, heads, _dt(x), _stream(x.device))
+    _lib.check(rc, "rcx_ls_la3_fwd")
+    return r, t
+
+
 def _mlp_acc_unit(i, h):
     """Hidden unit (within a 32-unit tile) that accumulator register i of lane half h holds after the first product (rcx_mlp.hip acc_row)."""
     return (i & 3) + 8 * (i >> 2) + 4 * h
