@@ -12,7 +12,7 @@
 //   D2 += W2[:][32 ht ..] h                                      ... the second product, with W2's columns stored in the order the registers imply
 //   y   = D2 + b2 + x                                            8-byte loads / stores of four channels per lane (token on the lane)
 // The weights are ready-made fragments (one conflict-free 16-byte LDS read per lane and product), packed once on the host (ops.pack_channel_mlp), hidden tile by
-// hidden tile: resident in LDS for C <= 128 (k_channel_mlp), streamed through a two-slot LDS ring for C = 128 .. 320 (k_channel_mlp_stream, further down).  Global
+// hidden tile: resident in LDS for C <= 128 (k_channel_mlp), streamed through a two-slot LDS ring for C = 128 .. 320 (k_channel_mlp_stream, further down; C = 256: k_channel_mlp_pair, two waves per SIMD).  Global
 // accesses are whole-wave contiguous kilobytes, transposed to / from the token-on-lane layouts in per-wave LDS images (measurements: profiles/r05_channel_mlp.txt).
 // GELU is the exact form 0.5 v (1 + erf(v / sqrt 2)) with erf as an odd degree-15 polynomial of the argument clamped to +-2.8: |error| < 7.7e-5 in erf, i.e. 4e-5 |v|
 // in gelu -- a fiftieth of a bf16 ulp; the library's erff would be most of this kernel's vector work.
@@ -385,6 +385,126 @@ k_channel_mlp_stream(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// C = 256, H = 512 (the 14 x 14 stage of M3 / A3): the streamed block of k_channel_mlp_stream with TWO waves per SIMD.  At 4 waves (128 tokens) a workgroup the
+// 1 568 token tiles of batch 256 were 1.53 rounds on 256 CUs, paid as two, and a wave alone on its SIMD left its GELU, fragment waits and barriers exposed between
+// its matrix products (profiles/r05_channel_mlp.txt).  Here 8 waves x 32 tokens = 256 tokens a workgroup: one round at batch 256, and one wave's vector work runs
+// under its partner's products.  That takes <= 256 registers a wave: d2 (128) + the z fragments (64) + d1, the hidden bf16 values, the fragment ring and the GELU
+// batch; so the chunks move global -> LDS by LDS-DMA (no staging registers) and the residual is requested only after the products.  The arithmetic is
+// hidden_tile_ring's, so y is bit-identical to k_channel_mlp_stream's.
+// LDS: a three-slot ring of chunks (3 x 32 KB), b1 / b2, and per wave a 32-token image of 144-byte rows: z staged in four column parts of 64 channels, the output
+// in quarters of one output tile (32 channels).  Ring: chunk ht lands in slot (step % 3) two steps ahead of its use; each step waits for its own chunk's DMAs
+// (counted vmcnt: the next chunk's stay in flight), then one barrier -- every wave's pieces have landed and every wave is done with the slot of the step before,
+// which then takes the chunk two ahead.  Raw s_barrier: __syncthreads() would wait for the DMAs in flight as well.
+template <int KS1, int HT, int CT>
+__global__ void __launch_bounds__(512, 2)
+k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf16_t* __restrict__ y, const u32x4q* __restrict__ wfrag, const float* __restrict__ bias,
+                   int M, int C, int nblocks)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    constexpr int NW = 8, NT = 64 * NW, NS = 3, NCH = KS1 + 2 * CT, PER = NCH * 64 / NT;   // PER: 1-KB DMA pieces of a chunk per wave
+    static_assert(NCH * 64 % NT == 0 && HT >= 2, "whole pieces per wave");
+    constexpr int ZH = 4, RB = 32 * KS1, RBH = RB / ZH, KH = KS1 / ZH, ZP = RBH + 16, OP = 128 + 16, IMG = 32 * (ZP > OP ? ZP : OP);
+    static_assert(KS1 % ZH == 0 && RBH == 128, "column parts of 64 channels: a request = 8 token rows of 128 bytes");
+    u32x4q* const Lring = reinterpret_cast<u32x4q*>(lds_raw);                        // [NS][NCH * 64]
+    float* const Lb1 = reinterpret_cast<float*>(lds_raw + (size_t)NS * NCH * 1024);
+    const float* const Lb2 = Lb1 + 32 * HT;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    unsigned char* const Lt = lds_raw + (size_t)NS * NCH * 1024 + sizeof(float) * 32 * (HT + CT) + (size_t)wv * IMG;
+    // chunk -> ring slot: piece i of wave w = bytes [1024 (8 i + w), + 1024) of the chunk, lane-linear in LDS as in the pack
+    auto fill = [&](int chunk, int slot) {
+        const u32x4q* src = wfrag + (size_t)chunk * NCH * 64 + threadIdx.x;
+        u32x4q* dst = Lring + (size_t)slot * NCH * 64 + wv * 64;
+#pragma unroll
+        for (int i = 0; i < PER; ++i)
+            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(src + i * NT), (__attribute__((address_space(3))) void*)(dst + i * NT), 16, 0, 0);
+    };
+    constexpr int VM_ALL = 0x70, VM_NEXT = 0x70 | (PER & 15) | ((PER >> 4) << 14);   // s_waitcnt: lgkmcnt(0) with vmcnt(0) / vmcnt(PER)
+    fill(0, 0);
+    fill(1, 1);
+    for (int i = threadIdx.x; i < 32 * (HT + CT); i += NT) Lb1[i] = bias[i];
+    const unsigned nbytes = (unsigned)M * (unsigned)C * 2u;
+    const __amdgpu_buffer_rsrc_t zsrc = __builtin_amdgcn_make_buffer_rsrc((void*)z, 0, nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xres, 0, nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, nbytes, 0x00020000);
+    // z request i of column part q = i / KH: bytes 1024 (i % KH) + 16 lane of that part = token 8 (i % KH) + lane / 8, byte 16 (lane % 8) of its 128 bytes --
+    // a lane base plus constants (no per-request address registers: they would be live through the products)
+    const unsigned zo0 = (unsigned)(lane >> 3) * RB + 16u * (lane & 7), za0 = (unsigned)(lane >> 3) * ZP + 16u * (lane & 7);
+    // output tile ct, request j (2 per tile): token 16 j + lane / 4, bytes 64 ct + 16 (lane % 4) of its row
+    const unsigned ot = lane >> 2, ob = 16u * (lane & 3);
+    // The two waves of a SIMD leave each barrier in the same phase; at equal priority they would run their first products side by side, then both GELUs with the
+    // matrix pipe idle.  One of them at a higher priority takes the pipe first, so the other's first product runs under its GELU and its second product under the
+    // other's GELU.  (Waves 0, 3, 5, 6: one of each pair whether the SIMDs take the waves round robin -- pairs w, w + 4 -- or in pairs -- 2 i, 2 i + 1.)
+    if (!(__builtin_popcount(wv) & 1)) __builtin_amdgcn_s_setprio(1);
+    int slot = 0;                                                              // the ring slot of the current step's chunk
+    for (int block = blockIdx.x; block < nblocks; block += gridDim.x) {
+        const unsigned base = (unsigned)(32 * (block * NW + wave)) * (unsigned)RB;    // (tokens past M: past the buffer -- reads 0, stores dropped)
+        const bool more = block + (int)gridDim.x < nblocks;
+        bf16x8 zb[KS1];
+        {
+            u32x4q zq[KS1];
+#pragma unroll
+            for (int i = 0; i < KS1; ++i)
+                zq[i] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(zsrc, (int)(base + zo0 + 8u * RB * (i % KH) + RBH * (i / KH)), 0, 0));
+#pragma unroll
+            for (int q = 0; q < ZH; ++q) {
+#pragma unroll
+                for (int i = 0; i < KH; ++i) *reinterpret_cast<u32x4q*>(Lt + za0 + 8 * ZP * i) = zq[q * KH + i];
+                wave_sync();
+#pragma unroll
+                for (int k = 0; k < KH; ++k) zb[q * KH + k] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4q*>(Lt + r * ZP + 32 * k + 16 * h));
+                wave_sync();
+            }
+        }
+        f32x16 d2[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) d2[ct][i] = 0.f;
+#pragma unroll 1
+        for (int ht = 0; ht < HT; ++ht) {
+            // chunk ht + 1's pieces (requested in the step before) are the only younger ones -- unless that step had no chunk to request
+            if (ht + 1 < HT || more) __builtin_amdgcn_s_waitcnt(VM_NEXT);
+            else __builtin_amdgcn_s_waitcnt(VM_ALL);
+            __builtin_amdgcn_s_barrier();
+            if (ht + 2 < HT || more) fill((ht + 2) % HT, slot == 0 ? 2 : slot - 1);   // the chunk two ahead (the next block's first two after the last), into the slot of the step before
+            hidden_tile_ring<KS1, CT, 4>(Lring + (size_t)slot * NCH * 64, Lb1 + 32 * ht, lane, h, zb, d2);
+            slot = slot == NS - 1 ? 0 : slot + 1;
+        }
+        u32x4q xq[CT][2];                                                          // the residual: requested after the products (its registers were the z fragments')
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                xq[ct][j] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(xsrc, (int)(base + (16u * j + ot) * RB + 64u * ct + ob), 0, 0));
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + 32 * ct + 8 * g + 4 * h);
+                *reinterpret_cast<f32x4q*>(Lt + r * OP + 4 * (8 * g + 4 * h)) =
+                    f32x4q{d2[ct][4 * g] + bb.x, d2[ct][4 * g + 1] + bb.y, d2[ct][4 * g + 2] + bb.z, d2[ct][4 * g + 3] + bb.w};
+            }
+            wave_sync();
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const unsigned char* src = Lt + (16 * j + ot) * OP + 2 * ob;
+                const f32x4q lo = *reinterpret_cast<const f32x4q*>(src), hi = *reinterpret_cast<const f32x4q*>(src + 16);
+                const u32x4q xv = xq[ct][j];
+                bf16x8 o;
+                o[0] = (__bf16)(lo.x + __uint_as_float(xv.x << 16)); o[1] = (__bf16)(lo.y + __uint_as_float(xv.x & 0xffff0000u));
+                o[2] = (__bf16)(lo.z + __uint_as_float(xv.y << 16)); o[3] = (__bf16)(lo.w + __uint_as_float(xv.y & 0xffff0000u));
+                o[4] = (__bf16)(hi.x + __uint_as_float(xv.z << 16)); o[5] = (__bf16)(hi.y + __uint_as_float(xv.z & 0xffff0000u));
+                o[6] = (__bf16)(hi.z + __uint_as_float(xv.w << 16)); o[7] = (__bf16)(hi.w + __uint_as_float(xv.w & 0xffff0000u));
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, o), ysrc, (int)(base + (16u * j + ot) * RB + 64u * ct + ob), 0, 0);
+            }
+            wave_sync();
+        }
+    }
+}
+
 }  // namespace mlp
 
 // C % 8 == 0, H % 32 == 0 (the host pads the hidden layer with zero units), the weights fit the CU's LDS, M C 2 < 2^31
@@ -451,6 +571,21 @@ static hipError_t launch_mlp_stream(const void* z, const void* x, void* y, const
     return hipGetLastError();
 }
 
+// C = 256, H = 512: 8 waves (two per SIMD), 256 tokens a workgroup
+static hipError_t launch_mlp_pair256(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, int ncu, hipStream_t s)
+{
+    constexpr int KS1 = 16, HT = 16, CT = 8, NCH = KS1 + 2 * CT, IMG = 32 * (128 + 16);
+    constexpr size_t lds = (size_t)3 * NCH * 1024 + sizeof(float) * 32 * (HT + CT) + (size_t)8 * IMG;
+    static_assert(lds <= 160 * 1024, "the ring and the waves' images must fit the LDS");
+    if (C != 16 * KS1) return hipErrorInvalidConfiguration;
+    auto kfn = mlp::k_channel_mlp_pair<KS1, HT, CT>;
+    RCX_SET_LDS_ONCE(kfn, lds);
+    const int nblocks = (M + 255) / 256;
+    const int grid = nblocks < ncu ? nblocks : ncu;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(512), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, C, nblocks);
+    return hipGetLastError();
+}
+
 hipError_t channel_mlp(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, int H, int dtype, hipStream_t s)
 {
     int ks1, ht, ct;
@@ -465,7 +600,7 @@ hipError_t channel_mlp(const void* z, const void* x, void* y, const void* wfrag,
             cus[dev].store(ncu, std::memory_order_relaxed);
         }
     }
-    if (C == 256 && ht == 16) return launch_mlp_stream<16, 16, 8, 4>(z, x, y, wfrag, bias, M, C, ncu, s);           // M3 / A3 stage 2
+    if (C == 256 && ht == 16) return launch_mlp_pair256(z, x, y, wfrag, bias, M, C, ncu, s);                         // M3 / A3 stage 2
     if (C == 192 && ht == 12) return launch_mlp_stream<12, 12, 6, 4>(z, x, y, wfrag, bias, M, C, ncu, s);           // M1 stage 2
     if (C == 160 && ht == 10) return launch_mlp_stream<10, 10, 6, 4>(z, x, y, wfrag, bias, M, C, ncu, s);           // M5 / A5 stage 1
     if (C == 320 && ht == 20) return launch_mlp_stream<20, 20, 10, 4, 2, false>(z, x, y, wfrag, bias, M, C, ncu, s); // M5 / A5 stage 2
