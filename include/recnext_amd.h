@@ -365,6 +365,26 @@ int rcx_ls_la3_fwd(const void* x, void* r, void* t, const float* w_rep, const fl
 int rcx_linear_attention_bwd(const void* qpre, const void* kpre, const void* v, const void* gout, void* gq, void* gk, void* gv,
                              int B, int n, int C, int heads, int dtype, void* stream);
 
+/*
+ * The linear-attention core with separate q / k and v widths, forward and backward, for the LSNet-style RecNeXt-T / S / B in training:
+ * LinearAttention3 (lsnet/model/recattn.py:97-109: q and k take s/2 channels of the full 1x1 `qk`, v is the whole slice) and the 96-channel heads
+ * of LinearAttention1 / 2 (:45-56 / :71-82) that rcx_linear_attention_fwd / _bwd do not take.  With Dk = Cqk/heads and Dv = Cv/heads:
+ *     q = elu(qpre)+1, k = elu(kpre)+1; out = q^T (k v^T) / (n * (q^T mean_n(k) + 1e-6)) + pe
+ *   qpre, kpre: B x n x Cqk pre-activations (BatchNorm applied, bias added), head h owns channels [h*Dk, (h+1)*Dk);
+ *   v, pe, out: B x n x Cv, head h owns channels [h*Dv, (h+1)*Dv).  n tokens, token-major (= NHWC).
+ * The backward writes gq, gk (B x n x Cqk) and gv (B x n x Cv) from gout = dL/dout (B x n x Cv); dL/dpe = gout is the caller's.
+ * Every tensor has `dtype` (float32, bf16 or f16) and is aligned to four elements; out / gq / gk / gv alias no input.  float32 arithmetic, every
+ * sum in a fixed order in one thread (bitwise deterministic, no atomics); one workgroup per (image, head), so an image's results do not depend
+ * on the batch.  Dk and Dv: multiples of 4 from 4 to 128, any pairing (every pair fits the LDS: at most 115 KiB for the backward at 128 x 128);
+ * n >= 1, heads >= 1.  rcx_linear_attention_wide_supported() says whether a shape has a kernel (1 / 0); else the entries return RCX_ERR_UNSUPPORTED
+ * (RCX_ERR_BAD_ARG for a null or misaligned pointer, a non-positive extent, an unknown dtype or channels that heads do not divide).
+ */
+int rcx_linear_attention_wide_supported(int B, int n, int Cqk, int Cv, int heads, int dtype);
+int rcx_linear_attention_wide_fwd(const void* qpre, const void* kpre, const void* v, const void* pe, void* out,
+                                  int B, int n, int Cqk, int Cv, int heads, int dtype, void* stream);
+int rcx_linear_attention_wide_bwd(const void* qpre, const void* kpre, const void* v, const void* gout, void* gq, void* gk, void* gv,
+                                  int B, int n, int Cqk, int Cv, int heads, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,9 @@ SIGNATURES = {
     "rcx_ls_la3_supported": (_i, [_i] * 7),
     "rcx_ls_la3_fwd": (_i, [_vp] * 11 + [_i] * 7 + [_vp]),
     "rcx_linear_attention_bwd": (_i, [_vp] * 7 + [_i] * 5 + [_vp]),
+    "rcx_linear_attention_wide_supported": (_i, [_i] * 6),
+    "rcx_linear_attention_wide_fwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),
+    "rcx_linear_attention_wide_bwd": (_i, [_vp] * 7 + [_i] * 6 + [_vp]),
 }
 
 _lib = None

@@ -1250,4 +1250,44 @@ int rcx_linear_attention_bwd(const void* qpre, const void* kpre, const void* v, 
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_linear_attention_bwd");
 }
 
+int rcx_linear_attention_wide_supported(int B, int n, int Cqk, int Cv, int heads, int dtype)
+{
+    return rcx::linattn_wide_applicable(B, n, Cqk, Cv, heads, dtype) ? 1 : 0;
+}
+
+namespace {
+// the argument checks shared by the wide core's two entries: every pointer non-NULL and aligned to four elements of `dtype`
+int check_wide(const char* fn, std::initializer_list<const void*> ps, int B, int n, int Cqk, int Cv, int heads, int dtype)
+{
+    for (const void* p : ps)
+        if (!p) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (B <= 0 || n <= 0 || Cqk <= 0 || Cv <= 0 || heads <= 0)
+        return fail(RCX_ERR_BAD_ARG, "%s: non-positive extent B=%d n=%d Cqk=%d Cv=%d heads=%d", fn, B, n, Cqk, Cv, heads);
+    if (!known_dtype(dtype)) return fail(RCX_ERR_BAD_ARG, "%s: unknown dtype %d", fn, dtype);
+    if (Cqk % heads || Cv % heads) return fail(RCX_ERR_BAD_ARG, "%s: Cqk=%d and Cv=%d must be multiples of heads=%d", fn, Cqk, Cv, heads);
+    const size_t align = dtype == RCX_DTYPE_F32 ? 16 : 8;
+    for (const void* p : ps)
+        if ((size_t)p % align) return fail(RCX_ERR_BAD_ARG, "%s: every tensor must be aligned to four elements (%zu bytes)", fn, (size_t)align);
+    if (!rcx::linattn_wide_applicable(B, n, Cqk, Cv, heads, dtype))
+        return fail(RCX_ERR_UNSUPPORTED, "%s: heads of %d (q / k) x %d (v) channels: both must be multiples of 4 from 4 to 128", fn, Cqk / heads, Cv / heads);
+    return 0;
+}
+}  // namespace
+
+int rcx_linear_attention_wide_fwd(const void* qpre, const void* kpre, const void* v, const void* pe, void* out,
+                                  int B, int n, int Cqk, int Cv, int heads, int dtype, void* stream)
+{
+    if (int rc = check_wide("rcx_linear_attention_wide_fwd", {qpre, kpre, v, pe, out}, B, n, Cqk, Cv, heads, dtype)) return rc;
+    hipError_t e = rcx::linattn_wide_fwd(qpre, kpre, v, pe, out, B, n, Cqk, Cv, heads, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rcx_linear_attention_wide_fwd");
+}
+
+int rcx_linear_attention_wide_bwd(const void* qpre, const void* kpre, const void* v, const void* gout, void* gq, void* gk, void* gv,
+                                  int B, int n, int Cqk, int Cv, int heads, int dtype, void* stream)
+{
+    if (int rc = check_wide("rcx_linear_attention_wide_bwd", {qpre, kpre, v, gout, gq, gk, gv}, B, n, Cqk, Cv, heads, dtype)) return rc;
+    hipError_t e = rcx::linattn_wide_bwd(qpre, kpre, v, gout, gq, gk, gv, B, n, Cqk, Cv, heads, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rcx_linear_attention_wide_bwd");
+}
+
 }  // extern "C"

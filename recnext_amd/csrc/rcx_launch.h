@@ -199,6 +199,12 @@ hipError_t recattn_qkcore(const float* d, const void* wqk_bf16, const float* bqk
 
 hipError_t linattn_core_bwd(const void* qpre, const void* kpre, const void* v, const void* gout, void* gq, void* gk, void* gv,
                             int B, int n, int C, int heads, int dtype, hipStream_t s);
+// rcx_attnw.hip -- the core with separate q / k and v head widths (4 .. 128 in fours each), forward and backward: a workgroup per (image, head)
+bool linattn_wide_applicable(int B, int n, int Cqk, int Cv, int heads, int dtype);
+hipError_t linattn_wide_fwd(const void* qpre, const void* kpre, const void* v, const void* pe, void* out, int B, int n, int Cqk, int Cv, int heads,
+                            int dtype, hipStream_t s);
+hipError_t linattn_wide_bwd(const void* qpre, const void* kpre, const void* v, const void* gout, void* gq, void* gk, void* gv, int B, int n, int Cqk,
+                            int Cv, int heads, int dtype, hipStream_t s);
 
 // rcx_bwd.hip -- backward pieces (deterministic gathers + two-stage weight-gradient reduction)
 size_t wgrad_partial_bytes(int C, int k);

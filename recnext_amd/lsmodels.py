@@ -6,8 +6,11 @@ checkpoints load with ``strict=True`` and ``models.replace_batchnorm`` gives the
 
 The token half ``x -> (r, t)`` of every block is ONE HIP entry (two launches: ``ops.ls_recattn`` / ``ops.ls_la3``), BatchNorms folded into float32
 packs whether or not ``replace_batchnorm`` has run; where the support query says no and the head is at most 64 wide, the block falls back to the
-HIP depthwise conv and the library's ``RecAttn2d`` on a contiguous slice.  Inference only: a forward in training mode or one that needs a gradient
-raises, as does a CPU tensor.  The stem, Downsample's grouped conv and the classifier are PyTorch-ROCm library operators.
+HIP depthwise conv and the library's ``RecAttn2d`` on a contiguous slice.  A forward in training mode or one that needs a gradient takes the training
+form (``_token_half_train``): BatchNorms on batch statistics under autograd, nothing folded, the depthwise convs and the attention cores with HIP
+forward and backward kernels -- ``RecAttn2d``'s own training branch at stages 0-2 (the 96-wide heads of S / B's stage 2 on the wide core,
+``rcx_linear_attention_wide_*``) and ``LinearAttention3.forward`` at stage 3 (q / k of s/2 and v of s channels: the wide core) -- and library GEMMs
+for the 1x1 projections.  A CPU tensor raises.  The stem, Downsample's grouped conv and the classifier are PyTorch-ROCm library operators.
 
 RecAttn2d's ``stage -> LinearAttention1 | 2`` label (:119) is cosmetic: the two are the same function (the reference asserts it, :481-501).
 """
@@ -20,7 +23,8 @@ import torch.nn.functional as F
 from . import ops
 from .layers import ConvNorm as _ConvNorm
 from .layers import DropPath
-from .recattn import RecAttn2d, _folded, head_dim_supported
+from .dwconv import DwConvFn
+from .recattn import RecAttn2d, _conv_norm_train, _folded, head_dim_supported
 
 # lsnet/model/recattn.py:441-466 (drop_path_rate of the non-distilled recipe; 0 with distillation)
 LS_CONFIGS = {
@@ -69,6 +73,22 @@ class RepVGGDW(nn.Module):
         return out
 
 
+def _rep_train(m, x):
+    """RepVGGDW (or its fused nn.Conv2d) in a training step: lk = HIP depthwise 3x3 (biased) + its BatchNorm, sk = the depthwise 1x1 as a per-channel
+    affine x w + b + its BatchNorm, then lk + sk + x (:8-15).  Batch statistics in train mode, nothing folded."""
+    if isinstance(m, nn.Conv2d):
+        return DwConvFn.apply(x, m.weight, m.bias, 1)
+    lk = _conv_norm_train(m.lk, x, 1)
+    sk = m.sk if isinstance(m.sk, nn.Conv2d) else m.sk.conv
+    c = x.shape[1]
+    y = x * sk.weight.view(1, c, 1, 1)
+    if sk.bias is not None:
+        y = y + sk.bias.view(1, c, 1, 1)
+    if not isinstance(m.sk, nn.Conv2d):
+        y = m.sk.norm(y)
+    return lk + y + x
+
+
 def _rep_params(m):
     """(weight (C,1,3,3), bias (C)) in float32 of a RepVGGDW or of its fused nn.Conv2d."""
     if isinstance(m, nn.Conv2d):
@@ -109,7 +129,25 @@ class LinearAttention3(nn.Module):
         self.pe = ConvNorm(dim, dim, kernel_size=3, padding=1, groups=dim)
 
     def forward(self, x):
-        raise NotImplementedError("LinearAttention3 runs inside MetaNeXtBlock's token half (recnext_amd.ops.ls_la3); it has no kernel of its own")
+        """The training-step form (MetaNeXtBlock's token half calls it; inference runs inside ops.ls_la3): the full 1x1 `qk` as one GEMM on the
+        token-major view + the module's BatchNorm, q = its channels [0, s/2), k = [s/2, s), v = x, pe = HIP depthwise 3x3 + BatchNorm, then the
+        wide core with its HIP backward (rcx_linear_attention_wide_fwd / _bwd)."""
+        b, c, h, w = x.shape
+        n = h * w
+        if not x.is_cuda:
+            raise RuntimeError("recnext_amd's LinearAttention3 runs on the GPU only (HIP kernels); the CPU formulation is tests/ls_eager.py")
+        if c % 2 or x.dtype not in ops._DT or not ops.linear_attention_wide_supported(b, n, c // 2, c, self.num_heads, x.dtype):
+            raise NotImplementedError(f"LinearAttention3: the HIP core takes heads of 4 .. 128 channels in fours; got dim {c}, {self.num_heads} heads, {x.dtype}")
+        m = self.qk
+        conv = m if isinstance(m, nn.Conv2d) else m.conv
+        y = F.linear(x.permute(0, 2, 3, 1).reshape(b * n, c), conv.weight[:, :, 0, 0], conv.bias)
+        y = y.view(b, h, w, c).permute(0, 3, 1, 2)
+        if not isinstance(m, nn.Conv2d):
+            y = m.norm(y)
+        tok = y.to(x.dtype).permute(0, 2, 3, 1).reshape(b, n, c)        # under autocast the GEMM answers in the autocast type: the core takes x's
+        qpre, kpre = tok[..., :c // 2].contiguous(), tok[..., c // 2:].contiguous()
+        pe = _conv_norm_train(self.pe, x, 1).to(x.dtype)
+        return ops.LinearAttentionWideCoreFn.apply(qpre, kpre, x.contiguous(memory_format=torch.channels_last), pe, self.num_heads)
 
     def extra_repr(self):
         return f"num_heads={self.num_heads}, head_dim={self.head_dim}"
@@ -192,12 +230,12 @@ class MetaNeXtBlock(nn.Module):
 
     def token_half(self, x):
         """(r, t) on HIP: one entry (two launches) where the support query says yes, else the HIP depthwise conv + the library's RecAttn2d on a
-        contiguous slice (heads of at most 64 channels); raises otherwise."""
+        contiguous slice (heads of at most 64 channels); raises otherwise.  In training mode or when a gradient is needed: _token_half_train."""
         attn = self.token_mixer.attn
         s = self.token_mixer.split_idx
         b, c, h, w = x.shape
         if self.training or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
-            raise NotImplementedError("training RecNeXt-T / S / B (or a forward that needs a gradient) is not built yet: run it in eval mode under torch.no_grad()")
+            return self._token_half_train(x)
         if not x.is_cuda:
             raise RuntimeError("recnext_amd's RecNeXt-T / S / B token mixer runs on the GPU only (HIP kernels); the CPU formulation is tests/ls_eager.py")
         if isinstance(attn, LinearAttention3):
@@ -213,6 +251,18 @@ class MetaNeXtBlock(nn.Module):
             t = torch.cat([attn(r[:, :s].contiguous(memory_format=torch.channels_last)), r[:, s:]], dim=1)
             return r, t.contiguous(memory_format=torch.channels_last)
         raise NotImplementedError(f"RecNeXt-T / S / B RecAttn2d: no kernel for a {h} x {w} plane of {c} channels (slice {s}, {heads} heads of {s // heads}, {x.dtype})")
+
+    def _token_half_train(self, x):
+        """(r, t) in a training step or a forward that needs a gradient: RepVGGDW (_rep_train), the slice mixer's own training form, the concatenation
+        under autograd; channels_last kept."""
+        if not x.is_cuda:
+            raise NotImplementedError("training RecNeXt-T / S / B runs on the GPU only (HIP kernels); the CPU formulation is tests/ls_eager.py")
+        s = self.token_mixer.split_idx
+        x = x.contiguous(memory_format=torch.channels_last)
+        r = _rep_train(self.rep_mixer, x)
+        mixed = self.token_mixer.attn(r[:, :s].contiguous(memory_format=torch.channels_last))
+        t = torch.cat([mixed.to(r.dtype), r[:, s:]], dim=1)
+        return r, t.contiguous(memory_format=torch.channels_last)
 
     def forward(self, x):
         if self._hip_mixer():

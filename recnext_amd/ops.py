@@ -759,6 +759,95 @@ class LinearAttentionCoreFn(torch.autograd.Function):
         return gq, gk, gv, gout, None
 
 
+def linear_attention_wide_supported(b, n, cqk, cv, heads, dtype):
+    """Whether the wide core (rcx_linear_attention_wide_*) takes b images of n tokens, q / k of cqk and v of cv channels in `heads` heads: head widths
+    cqk / heads and cv / heads multiples of 4 from 4 to 128, in any pairing."""
+    code = _DT.get(dtype)
+    return code is not None and _lib.load().rcx_linear_attention_wide_supported(b, n, cqk, cv, heads, code) == 1
+
+
+def _check_wide_args(fn, qpre, kpre, v, other, other_name, heads):
+    """Every shape, dtype and device check of the wide core's entries, before anything is allocated or launched; raises ValueError."""
+    for name, t in (("qpre", qpre), ("kpre", kpre), ("v", v), (other_name, other)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{fn}: {name} must be a tensor, got {type(t).__name__}")
+    for name, t in (("qpre", qpre), ("kpre", kpre), ("v", v), (other_name, other)):
+        if not t.is_cuda:
+            raise ValueError(f"{fn}: {name} is on {t.device}: the wide linear-attention core runs on the GPU only (HIP kernels)")
+        if t.device != v.device:
+            raise ValueError(f"{fn}: {name} is on {t.device}, v on {v.device}")
+    if v.dim() != 4:
+        raise ValueError(f"{fn}: v must be 4-D (N, Cv, h, w), got shape {tuple(v.shape)}")
+    if v.dtype not in _DT:
+        raise ValueError(f"{fn}: v must be float32, bfloat16 or float16, got {v.dtype}")
+    b, cv, h, w = v.shape
+    n = h * w
+    if qpre.dim() != 3 or qpre.shape[0] != b or qpre.shape[1] != n:
+        raise ValueError(f"{fn}: qpre must be ({b}, {n}, Cqk), got {tuple(qpre.shape)}")
+    cqk = qpre.shape[2]
+    for name, t in (("qpre", qpre), ("kpre", kpre)):
+        if tuple(t.shape) != (b, n, cqk) or not t.is_contiguous() or t.dtype != v.dtype:
+            raise ValueError(f"{fn}: {name} must be a contiguous ({b}, {n}, {cqk}) tensor of {v.dtype}, got {tuple(t.shape)} {t.dtype}")
+    if tuple(other.shape) != tuple(v.shape):
+        raise ValueError(f"{fn}: {other_name} has shape {tuple(other.shape)}, expected v's {tuple(v.shape)}")
+    if other_name == "pe" and other.dtype != v.dtype:
+        raise ValueError(f"{fn}: pe must have v's dtype {v.dtype}, got {other.dtype}")
+    if not isinstance(heads, int) or heads <= 0 or cqk % heads or cv % heads:
+        raise ValueError(f"{fn}: heads={heads} must be a positive integer dividing Cqk={cqk} and Cv={cv}")
+    if not linear_attention_wide_supported(b, n, cqk, cv, heads, v.dtype):
+        raise ValueError(f"{fn}: no kernel for heads of {cqk // heads} (q / k) x {cv // heads} (v) channels: both must be multiples of 4 from 4 to 128")
+    return b, n, cqk, cv, h, w
+
+
+def linear_attention_wide(qpre, kpre, v, pe, heads):
+    """The linear-attention core with separate q / k and v widths (rcx_linear_attention_wide_fwd; lsnet/model/recattn.py:97-109 LinearAttention3,
+    and the 96-wide heads of LinearAttention1 / 2): qpre, kpre (B, n, Cqk) pre-activations; v, pe N x Cv x h x w, viewed as (B, n, Cv); returns
+    channels_last like v."""
+    b, n, cqk, cv, h, w = _check_wide_args("linear_attention_wide", qpre, kpre, v, pe, "pe", heads)
+    v = _nhwc(v, "v")
+    pe = _nhwc(pe, "pe")
+    out = _empty_nhwc(b, cv, h, w, v.dtype, v.device)
+    with _on(v.device):
+        rc = _lib.load().rcx_linear_attention_wide_fwd(qpre.data_ptr(), kpre.data_ptr(), v.data_ptr(), pe.data_ptr(), out.data_ptr(),
+                                                       b, n, cqk, cv, heads, _dt(v), _stream(v.device))
+    _lib.check(rc, "rcx_linear_attention_wide_fwd")
+    return out
+
+
+def linear_attention_wide_backward(qpre, kpre, v, gout, heads):
+    """Gradients of linear_attention_wide with respect to qpre, kpre (B, n, Cqk) and v (N x Cv x h x w, channels_last); dL/dpe = gout."""
+    b, n, cqk, cv, h, w = _check_wide_args("linear_attention_wide_backward", qpre, kpre, v, gout, "grad_output", heads)
+    v = _nhwc(v, "v")
+    gout = _nhwc(gout, "grad_output")
+    if gout.dtype != v.dtype:
+        gout = gout.to(v.dtype)
+    gq = torch.empty_like(qpre)
+    gk = torch.empty_like(kpre)
+    gv = _empty_nhwc(b, cv, h, w, v.dtype, v.device)
+    with _on(v.device):
+        rc = _lib.load().rcx_linear_attention_wide_bwd(qpre.data_ptr(), kpre.data_ptr(), v.data_ptr(), gout.data_ptr(),
+                                                       gq.data_ptr(), gk.data_ptr(), gv.data_ptr(), b, n, cqk, cv, heads, _dt(v), _stream(v.device))
+    _lib.check(rc, "rcx_linear_attention_wide_bwd")
+    return gq, gk, gv
+
+
+class LinearAttentionWideCoreFn(torch.autograd.Function):
+    """linear_attention_wide with its HIP backward (rcx_linear_attention_wide_bwd), as LinearAttentionCoreFn: v and pe channels_last, dL/dpe = gout."""
+
+    @staticmethod
+    def forward(ctx, qpre, kpre, v, pe, heads):
+        out = linear_attention_wide(qpre, kpre, v, pe, heads)
+        ctx.save_for_backward(qpre, kpre, v)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        qpre, kpre, v = ctx.saved_tensors
+        gq, gk, gv = linear_attention_wide_backward(qpre, kpre, v, gout, ctx.heads)
+        return gq, gk, gv, gout, None
+
+
 def recconv2d_forward_train(x, wpack, bpack, level, k, mode="bilinear"):
     """Training forward: same result as recconv2d_forward, plus the saved fp32 pyramid the backward needs."""
     x = _nhwc(x)

@@ -47,15 +47,19 @@ class LinearAttention(nn.Module):
         n = h * w
         if not x.is_cuda:
             raise RuntimeError("recnext_amd.LinearAttention runs on the GPU only (HIP kernels); the CPU formulation is oracle/torch_eager.py")
+        core = ops.LinearAttentionCoreFn
         if c % 4 or not head_dim_supported(self.head_dim) or x.dtype not in ops._DT:
-            raise NotImplementedError(f"LinearAttention: the HIP core takes head sizes up to 32, or multiples of 4 up to 64, and channel counts that "
-                                      f"are multiples of 4; got dim {c}, {self.num_heads} heads, {x.dtype}")
+            # heads the core above does not take (the 96-wide heads of RecNeXt-S / B's stage 2): the wide core, rcx_linear_attention_wide_*
+            if not (x.dtype in ops._DT and c % self.num_heads == 0 and ops.linear_attention_wide_supported(b, n, c, c, self.num_heads, x.dtype)):
+                raise NotImplementedError(f"LinearAttention: the HIP cores take head sizes up to 32, or multiples of 4 up to 128, and channel counts "
+                                          f"that are multiples of 4; got dim {c}, {self.num_heads} heads, {x.dtype}")
+            core = ops.LinearAttentionWideCoreFn
         # Under autocast the GEMMs answer in the autocast type while x stays float32: the core takes one type, x's
         qkpre = self._qk_gpu(x).to(x.dtype)                 # (b, 2c, h, w), channels_last storage
         tok = qkpre.permute(0, 2, 3, 1).reshape(b, n, 2 * c)
         qpre, kpre = tok[..., :c].contiguous(), tok[..., c:].contiguous()
         pe = _conv_norm_train(self.pe, x, 1).to(x.dtype)
-        return ops.LinearAttentionCoreFn.apply(qpre, kpre, x.contiguous(memory_format=torch.channels_last), pe, self.num_heads)
+        return core.apply(qpre, kpre, x.contiguous(memory_format=torch.channels_last), pe, self.num_heads)
 
     def _qk_gpu(self, x):
         """The grouped 1x1 `qk` conv as two GEMMs on the token-major view (same function; the GEMM library's forward and

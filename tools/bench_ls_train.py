@@ -1,0 +1,58 @@
+#!/usr/bin/env python3
+"""Training step (forward + backward + AdamW) of RecNeXt-T / S / B at 224x224: the HIP token half vs the operator chain (tests/ls_eager.py).
+
+engine.py-style step under bf16 autocast, channels_last, synthetic data; one GPU (development tool, not bench.py).  One JSON line per (model, path)
+with the sha256 of the kernel sources it ran on.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from recnext_amd import lsmodels
+from recnext_amd.build import source_fingerprint
+from tests.ls_eager import eager_token_mixer
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--models", default="recnext_t,recnext_s,recnext_b")
+ap.add_argument("--batch", type=int, default=128)
+ap.add_argument("--steps", type=int, default=8)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--which", default="hip,eager")
+args = ap.parse_args()
+dev = torch.device("cuda:0")
+sha = source_fingerprint()
+for name in args.models.split(","):
+    for which in args.which.split(","):
+        torch.manual_seed(0)
+        net = lsmodels.create_model(name, token_mixer=None if which == "hip" else eager_token_mixer)
+        net = net.to(dev).to(memory_format=torch.channels_last).train()
+        opt = torch.optim.AdamW(net.parameters(), lr=1e-3)
+        x = torch.randn(args.batch, 3, 224, 224, device=dev).contiguous(memory_format=torch.channels_last)
+        y = torch.randint(0, 1000, (args.batch,), device=dev)
+
+        def step():
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                loss = torch.nn.functional.cross_entropy(net(x).float(), y)
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
+            return loss
+
+        for _ in range(args.warmup):
+            step()
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(args.steps):
+            loss = step()
+        e.record()
+        torch.cuda.synchronize()
+        ms = s.elapsed_time(e) / args.steps
+        print(json.dumps({"model": name, "token_mixers": which, "batch": args.batch, "steps": args.steps, "ms_per_step": round(ms, 2),
+                          "images_per_s": round(args.batch / ms * 1e3, 1), "loss": round(float(loss), 4), "library_sources_sha256": sha}), flush=True)
+        del net, opt
+        torch.cuda.empty_cache()
