@@ -462,33 +462,29 @@ TrainFwdSchedule train_fwd_schedule(int N, int C, int H, int W, int level, int k
 enum BwdKind { BWD_ONE, BWD_TILED, BWD_STEPS };
 struct BwdSchedule { BwdKind kind; int m; bool split; };      // m: the tail's level (0: none); split: the 14x14 launch runs two waves per plane
 
-BwdSchedule bwd_schedule(const TrainLadder& L, int N, int C, int level, int k, int dtype)
+// The same kinds and cut-overs serve rcx_recconv2d_bwd (want_wgrads) and the input-only rcx_recconv2d_bwd_input; the one launch is the whole-block
+// backward (rcx_cplbwd.hip) for the first and the input adjoint (rcx_cpladj.hip) for the second.  That kernel keeps no partial rows, so no batch
+// limit; it runs one wave per plane (never split).
+BwdSchedule bwd_schedule(const TrainLadder& L, int N, int C, int level, int k, int dtype, bool want_wgrads)
 {
-    if (level >= 1 && rcx::cplbwd_applicable(N, C, L.h[0], L.w[0], level, k, dtype)) return {BWD_ONE, 0, L.h[0] == 14 && rcx::cplbwd_split(N, C)};
-    const int m = level >= 3 && L.h[level - 2] == 14 && L.w[level - 2] == 14 && rcx::cplbwd_applicable(N, C, 14, 14, 2, k, RCX_DTYPE_F32) ? level - 2 : 0;
+    auto one = [&](int H, int W, int lv, int dt) {
+        return want_wgrads ? rcx::cplbwd_applicable(N, C, H, W, lv, k, dt) : rcx::cpladj_applicable(N, C, H, W, lv, k, dt);
+    };
+    const bool split = want_wgrads && rcx::cplbwd_split(N, C);
+    if (level >= 1 && one(L.h[0], L.w[0], level, dtype)) return {BWD_ONE, 0, L.h[0] == 14 && split};
+    const int m = level >= 3 && L.h[level - 2] == 14 && L.w[level - 2] == 14 && one(14, 14, 2, RCX_DTYPE_F32) ? level - 2 : 0;
     bool tiled = m > 0;       // ... and every plane above the tail 56x56 or 28x28
     for (int l = 0; l < m; ++l)
         tiled = tiled && rcx::bwd_cpt_applicable(N, C, L.h[l], L.w[l], k) && L.h[l + 1] * 2 == L.h[l] && L.w[l + 1] * 2 == L.w[l];
-    return {tiled ? BWD_TILED : BWD_STEPS, m, m > 0 && rcx::cplbwd_split(N, C)};
+    return {tiled ? BWD_TILED : BWD_STEPS, m, m > 0 && split};
 }
 
-// The input-only backward's schedule (rcx_recconv2d_bwd_input): the same kinds and cut-overs as bwd_schedule, on the input adjoint
-// (rcx_cpladj.hip) instead of the whole-block backward.  That kernel keeps no partial rows, so no batch limit; it runs one wave per plane.
-BwdKind bwd_input_schedule(const TrainLadder& L, int N, int C, int level, int k, int dtype, int* m_out)
-{
-    *m_out = 0;
-    if (level >= 1 && rcx::cpladj_applicable(N, C, L.h[0], L.w[0], level, k, dtype)) return BWD_ONE;
-    const int m = level >= 3 && L.h[level - 2] == 14 && L.w[level - 2] == 14 && rcx::cpladj_applicable(N, C, 14, 14, 2, k, RCX_DTYPE_F32) ? level - 2 : 0;
-    bool tiled = m > 0;
-    for (int l = 0; l < m; ++l)
-        tiled = tiled && rcx::bwd_cpt_applicable(N, C, L.h[l], L.w[l], k) && L.h[l + 1] * 2 == L.h[l] && L.w[l + 1] * 2 == L.w[l];
-    *m_out = m;
-    return tiled ? BWD_TILED : BWD_STEPS;
-}
-
-// One rcx_recconv2d_bwd call and the weight-gradient jobs its partial buffers join (job 0 = the shared down conv, job 1 + j = convs[j])
+// One rcx_recconv2d_bwd or rcx_recconv2d_bwd_input call.  With wgrads: the weight-gradient jobs its partial buffers join (job 0 = the shared down
+// conv, job 1 + j = convs[j]).  Without: x and saved are null, J and the partial slots stay unused.  prefix starts the error messages.
 struct BwdRun {
     const TrainLadder& L;
+    bool wgrads;
+    const char* prefix;
     const void *x, *gy;
     void* gx;
     const float *wpack, *wflip;
@@ -507,20 +503,23 @@ struct BwdRun {
     void add(int job, const float* p, int rows) { J.part[job][J.nslots[job]] = p; J.rows[job][J.nslots[job]] = rows; ++J.nslots[job]; }
 };
 
-#define RCX_TRY(call, what) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, what); } while (0)
+#define RCX_TRY(call, what, prefix) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, what, prefix); } while (0)
 
-// the one-launch backward of the whole block (m = 0) or of its tail (x = F_m, g = dL/dC_m, gx = G_m): a partial row per image for jobs 0 .. level + 1
-hipError_t one_launch(BwdRun& B, const void* x, const void* g, int g_dt, void* gx, int m, int H, int level, int dtype)
+// the one-launch backward of the whole block (m = 0: x, g = gy) or of its tail (x = F_m, g = dL/dC_m, gx = G_m).  With weight gradients a partial
+// row per image for jobs 0 .. level + 1; without, the input adjoint alone, which needs neither x nor the pyramid
+hipError_t one_launch(BwdRun& B, const void* g, int g_dt, void* gx, int m, int H, int level, int dtype)
 {
+    const int md = B.mode == RCX_MODE_NEAREST ? 1 : 0;
+    if (!B.wgrads) return rcx::cpladj_recconv(g, g_dt, B.wpack, B.wflip, gx, dtype, B.N, B.C, H, md, B.s);
     float* parts[RCX_MAX_LEVEL + 2];
     for (int j = 0; j < level + 2; ++j) { parts[j] = B.next_part(); B.add(j, parts[j], B.N); }
-    return rcx::cplbwd_recconv(x, g, B.wpack, B.wflip, B.saved, B.L.f_off + m, B.L.c_off + m, gx, parts, B.N, B.C, H, level,
-                               B.mode == RCX_MODE_NEAREST ? 1 : 0, dtype, B.s, g_dt);
+    return rcx::cplbwd_recconv(m ? B.F(m) : B.x, g, B.wpack, B.wflip, B.saved, B.L.f_off + m, B.L.c_off + m, gx, parts, B.N, B.C, H, level,
+                               md, dtype, B.s, g_dt);
 }
 
 // BWD_TILED.  Top-down: gW_j from (a_l, C_{l+1}, g_l) and gC_{l+1} = R^T K^ g_l; the tail returns G_m; bottom-up: gW_d from (a_l, G_{l+1}) and
 // G_l = K^ g_l + D^T G_{l+1} (G_0 = gx).  g_0 = gy in its own type, g_l = gC_l float32 (parked in the full-resolution slot G(0) the per-step
-// schedule keeps gT_0 in: no gT plane exists here).
+// schedule keeps gT_0 in: no gT plane exists here).  Without weight gradients the gW launches and their partial rows are skipped, nothing else.
 int bwd_tiled(BwdRun& B, int m)
 {
     const TrainLadder& L = B.L;
@@ -538,23 +537,27 @@ int bwd_tiled(BwdRun& B, int m)
     // 342 vs 301 us at 128 x 64 x 56 x 56, 301 vs 220 us at 256 x 128 x 28 x 28, equal at 256 x 64 x 56 x 56; profiles/r06_backward_side_stream.txt.)
     for (int l = 0; l < m; ++l) {
         const int j = B.level - l;                              // convs[j] is level l's conv
-        float* p = B.next_part();
-        RCX_TRY(rcx::bwd_wgrad_k_cpt(a_of(l), adt_of(l), B.Cs(l + 1), g_of(l), gdt_of(l), p, N, C, L.h[l], md, B.s, &rows), "bwd: conv weight grad");
-        B.add(1 + j, p, rows);
-        RCX_TRY(rcx::bwd_gc_cpt(g_of(l), gdt_of(l), gcl[l + 1], B.Wf(1 + j), N, C, L.h[l], md, B.s), "bwd: gradient handed down");
+        if (B.wgrads) {
+            float* p = B.next_part();
+            RCX_TRY(rcx::bwd_wgrad_k_cpt(a_of(l), adt_of(l), B.Cs(l + 1), g_of(l), gdt_of(l), p, N, C, L.h[l], md, B.s, &rows), "conv weight grad", B.prefix);
+            B.add(1 + j, p, rows);
+        }
+        RCX_TRY(rcx::bwd_gc_cpt(g_of(l), gdt_of(l), gcl[l + 1], B.Wf(1 + j), N, C, L.h[l], md, B.s), "gradient handed down", B.prefix);
     }
-    RCX_TRY(one_launch(B, B.F(m), gcl[m], RCX_DTYPE_F32, B.G(m), m, 14, 2, RCX_DTYPE_F32), "bwd: fused nested block");
+    RCX_TRY(one_launch(B, gcl[m], RCX_DTYPE_F32, B.G(m), m, 14, 2, RCX_DTYPE_F32), "fused nested block", B.prefix);
     for (int l = m - 1; l >= 0; --l) {
-        float* p = B.next_part();
-        RCX_TRY(rcx::bwd_wgrad_d_cpt(a_of(l), adt_of(l), B.G(l + 1), p, N, C, L.h[l], B.s, &rows), "bwd: down weight grad");
-        B.add(0, p, rows);
+        if (B.wgrads) {
+            float* p = B.next_part();
+            RCX_TRY(rcx::bwd_wgrad_d_cpt(a_of(l), adt_of(l), B.G(l + 1), p, N, C, L.h[l], B.s, &rows), "down weight grad", B.prefix);
+            B.add(0, p, rows);
+        }
         RCX_TRY(rcx::bwd_gx_cpt(g_of(l), gdt_of(l), B.G(l + 1), l == 0 ? B.gx : (void*)B.G(l), l == 0 ? B.dtype : RCX_DTYPE_F32, B.Wf(1 + B.level - l),
-                                B.Wd(0), N, C, L.h[l], B.s), "bwd: gradient handed up");
+                                B.Wd(0), N, C, L.h[l], B.s), "gradient handed up", B.prefix);
     }
     return 0;
 }
 
-// BWD_STEPS: the per-step forward read backwards, float32 throughout, down to the tail (m > 0)
+// BWD_STEPS: the per-step forward read backwards, float32 throughout, down to the tail (m > 0); without weight gradients, minus the gW launches
 int bwd_steps(BwdRun& B, int m)
 {
     const TrainLadder& L = B.L;
@@ -564,45 +567,84 @@ int bwd_steps(BwdRun& B, int m)
     int rows = 0;
     // final conv (model/recnext.py:34): gT_0 = K_L^T gy (gx itself with no ladder) ; gW_L = <x + R(C_1), gy>
     RCX_TRY(step_dwconv(gyf, level == 0 ? B.gx : (void*)B.G(0), B.Wf(1 + level), nullptr, N, C, H, W, k, 1, RCX_DTYPE_F32,
-                        level == 0 ? dtype : RCX_DTYPE_F32, B.s), "bwd: final conv input grad");
-    float* p = B.next_part();
-    RCX_TRY(rcx::bwd_wgrad(B.x, dtype, level >= 1 ? B.Cs(1) : nullptr, gyf, p, B.J.gw[1 + level], B.J.gb[1 + level], N, C, H, W,
-                           level >= 1 ? L.h[1] : 0, level >= 1 ? L.w[1] : 0, H, W, k, 1, mode, 0, B.s, &rows), "bwd: final conv weight grad");
-    B.add(1 + level, p, rows);
+                        level == 0 ? dtype : RCX_DTYPE_F32, B.s), "final conv input grad", B.prefix);
+    if (B.wgrads) {
+        float* p = B.next_part();
+        RCX_TRY(rcx::bwd_wgrad(B.x, dtype, level >= 1 ? B.Cs(1) : nullptr, gyf, p, B.J.gw[1 + level], B.J.gb[1 + level], N, C, H, W,
+                               level >= 1 ? L.h[1] : 0, level >= 1 ? L.w[1] : 0, H, W, k, 1, mode, 0, B.s, &rows), "final conv weight grad", B.prefix);
+        B.add(1 + level, p, rows);
+    }
     // up recursion (:31-33), finest level first in the backward direction
     for (int l = 1; l <= level; ++l) {
         const int j = level - l;
-        RCX_TRY(rcx::bwd_resize(B.G(l - 1), gC, N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], mode, B.s), "bwd: resize adjoint");
-        if (l == m) { RCX_TRY(one_launch(B, B.F(m), gC, RCX_DTYPE_F32, B.G(m), m, 14, 2, RCX_DTYPE_F32), "bwd: fused nested block"); break; }
-        RCX_TRY(step_dwconv(gC, B.G(l), B.Wf(1 + j), nullptr, N, C, L.h[l], L.w[l], k, 1, RCX_DTYPE_F32, RCX_DTYPE_F32, B.s), "bwd: conv input grad");
-        p = B.next_part();
+        RCX_TRY(rcx::bwd_resize(B.G(l - 1), gC, N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], mode, B.s), "resize adjoint", B.prefix);
+        if (l == m) { RCX_TRY(one_launch(B, gC, RCX_DTYPE_F32, B.G(m), m, 14, 2, RCX_DTYPE_F32), "fused nested block", B.prefix); break; }
+        RCX_TRY(step_dwconv(gC, B.G(l), B.Wf(1 + j), nullptr, N, C, L.h[l], L.w[l], k, 1, RCX_DTYPE_F32, RCX_DTYPE_F32, B.s), "conv input grad", B.prefix);
+        if (!B.wgrads) continue;
+        float* p = B.next_part();
         RCX_TRY(rcx::bwd_wgrad(B.F(l), RCX_DTYPE_F32, l < level ? B.Cs(l + 1) : nullptr, gC, p, B.J.gw[1 + j], B.J.gb[1 + j], N, C, L.h[l], L.w[l],
-                               l < level ? L.h[l + 1] : 0, l < level ? L.w[l + 1] : 0, L.h[l], L.w[l], k, 1, mode, 0, B.s, &rows), "bwd: conv weight grad");
+                               l < level ? L.h[l + 1] : 0, l < level ? L.w[l + 1] : 0, L.h[l], L.w[l], k, 1, mode, 0, B.s, &rows), "conv weight grad", B.prefix);
         B.add(1 + j, p, rows);
     }
     // down ladder (:27-29), coarsest first: the shared weight accumulates over all levels
     for (int l = m ? m : level; l >= 1; --l) {
-        p = B.next_part();
-        RCX_TRY(rcx::bwd_wgrad(l == 1 ? B.x : (const void*)B.F(l - 1), l == 1 ? dtype : RCX_DTYPE_F32, nullptr, B.G(l), p, B.J.gw[0], B.J.gb[0],
-                               N, C, L.h[l - 1], L.w[l - 1], 0, 0, L.h[l], L.w[l], k, 2, mode, 0, B.s, &rows), "bwd: down weight grad");
-        B.add(0, p, rows);
+        if (B.wgrads) {
+            float* p = B.next_part();
+            RCX_TRY(rcx::bwd_wgrad(l == 1 ? B.x : (const void*)B.F(l - 1), l == 1 ? dtype : RCX_DTYPE_F32, nullptr, B.G(l), p, B.J.gw[0], B.J.gb[0],
+                                   N, C, L.h[l - 1], L.w[l - 1], 0, 0, L.h[l], L.w[l], k, 2, mode, 0, B.s, &rows), "down weight grad", B.prefix);
+            B.add(0, p, rows);
+        }
         RCX_TRY(rcx::bwd_down_input(B.G(l - 1), B.G(l), l == 1 ? B.gx : (void*)B.G(l - 1), l == 1 ? dtype : RCX_DTYPE_F32, B.Wd(0),
-                                    N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], k, B.s), "bwd: down input grad");
+                                    N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], k, B.s), "down input grad", B.prefix);
     }
     return 0;
+}
+
+// the seven shape queries below answer 0 / float32 / "invalid" outside these extents (the launch entries diagnose each one: check_common, check_bwd_args)
+bool bwd_extents_ok(int N, int C, int H, int W, int level, int k)
+{
+    return N > 0 && C > 0 && H > 0 && W > 0 && level >= 0 && level <= RCX_MAX_LEVEL && k > 0 && (k & 1);
+}
+
+// the argument checks rcx_recconv2d_bwd and rcx_recconv2d_bwd_input share, after check_common and their own pointer checks
+int check_bwd_args(int gy_dtype, int C, int level, int mode)
+{
+    if (!known_dtype(gy_dtype)) return fail(RCX_ERR_BAD_ARG, "unknown gy dtype %d", gy_dtype);
+    if (level < 0 || level > RCX_MAX_LEVEL) return fail(RCX_ERR_BAD_ARG, "level %d outside [0,%d]", level, RCX_MAX_LEVEL);
+    if (mode != RCX_MODE_BILINEAR && mode != RCX_MODE_NEAREST) return fail(RCX_ERR_BAD_ARG, "unknown mode %d", mode);
+    if (C % 4) return fail(RCX_ERR_UNSUPPORTED, "the backward kernels need C %% 4 == 0, got C=%d", C);
+    return 0;
+}
+
+// The workspace of an input-only backward: none for the one-launch blocks, else the float32 gradient planes of the training backward's
+// ladder (gT_0 .. gT_L and the resized-gradient plane) without its partial-sum buffers
+size_t bwd_input_workspace(const TrainLadder& L, BwdKind kind) { return kind == BWD_ONE ? 0 : L.part_off; }
+
+// rcx_recconv2d_bwd_plan / rcx_recconv2d_bwd_input_plan, into the entry's own buffer: stem is the one-launch kernel's name without its plane size
+const char* bwd_plan(char (&desc)[64], int N, int C, int H, int W, int level, int k, int dtype, bool want_wgrads, const char* stem)
+{
+    if (!bwd_extents_ok(N, C, H, W, level, k) || !known_dtype(dtype)) return "invalid";
+    if (rcx::opt::hand_kernels_off()) return "generic";
+    const BwdSchedule b = bwd_schedule(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype, want_wgrads);
+    if (b.kind == BWD_STEPS && !b.m) return "steps";
+    const char* cpl = b.kind == BWD_ONE && H != 14 ? "cpl7" : "cpl14", *split = b.split ? ",split" : "";
+    if (b.kind == BWD_ONE) snprintf(desc, sizeof(desc), "one(%s%s%s)", stem, cpl, split);
+    else if (b.kind == BWD_TILED) snprintf(desc, sizeof(desc), "tiled(levels=%d)+one(%s%s%s)", b.m, stem, cpl, split);
+    else snprintf(desc, sizeof(desc), "steps+one(%s%s%s)", stem, cpl, split);
+    return desc;
 }
 
 }  // namespace
 
 size_t rcx_recconv2d_train_saved_bytes(int N, int C, int H, int W, int level, int k)
 {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || level < 0 || level > RCX_MAX_LEVEL || k <= 0 || (k & 1) == 0) return 0;
+    if (!bwd_extents_ok(N, C, H, W, level, k)) return 0;
     return make_train_ladder(N, C, H, W, level, k).saved_total;
 }
 
 size_t rcx_recconv2d_bwd_workspace_bytes(int N, int C, int H, int W, int level, int k)
 {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || level < 0 || level > RCX_MAX_LEVEL || k <= 0 || (k & 1) == 0) return 0;
+    if (!bwd_extents_ok(N, C, H, W, level, k)) return 0;
     return make_train_ladder(N, C, H, W, level, k).bwd_total;
 }
 
@@ -629,23 +671,16 @@ int rcx_recconv2d_fwd_train(const void* x, void* y, const float* wpack, const fl
 
 int rcx_recconv2d_bwd_gy_dtype(int N, int C, int H, int W, int level, int k, int dtype)
 {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || level < 0 || level > RCX_MAX_LEVEL || k <= 0 || (k & 1) == 0 || !known_dtype(dtype)) return RCX_DTYPE_F32;
+    if (!bwd_extents_ok(N, C, H, W, level, k) || !known_dtype(dtype)) return RCX_DTYPE_F32;
     // bfloat16 (float16 rows on both sides overflow the tiled weight-gradient kernel's registers), where the one-launch or tiled backward reads it
     if (dtype != RCX_DTYPE_BF16 || C % 4) return RCX_DTYPE_F32;
-    return bwd_schedule(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype).kind != BWD_STEPS ? dtype : RCX_DTYPE_F32;
+    return bwd_schedule(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype, true).kind != BWD_STEPS ? dtype : RCX_DTYPE_F32;
 }
 
 const char* rcx_recconv2d_bwd_plan(int N, int C, int H, int W, int level, int k, int dtype)
 {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || level < 0 || level > RCX_MAX_LEVEL || k <= 0 || (k & 1) == 0 || !known_dtype(dtype)) return "invalid";
-    if (rcx::opt::hand_kernels_off()) return "generic";
     static thread_local char desc[64];
-    const BwdSchedule b = bwd_schedule(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype);
-    const char* one14 = b.split ? "one(k_recconv_bwd_cpl14,split)" : "one(k_recconv_bwd_cpl14)";
-    if (b.kind == BWD_ONE) return H == 14 ? one14 : "one(k_recconv_bwd_cpl7)";
-    if (b.kind == BWD_TILED) snprintf(desc, sizeof(desc), "tiled(levels=%d)+%s", b.m, one14);
-    else if (b.m) snprintf(desc, sizeof(desc), "steps+%s", one14);
-    return b.kind == BWD_STEPS && !b.m ? "steps" : desc;
+    return bwd_plan(desc, N, C, H, W, level, k, dtype, true, "k_recconv_bwd_");
 }
 
 int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* wpack, const float* wpack_flipped, const void* saved,
@@ -655,22 +690,20 @@ int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* 
 {
     if (int rc = check_common(x, gx, N, C, H, W, k, dtype)) return rc;
     if (!gy || !wpack || !wpack_flipped || (!gwpack && !gw_out)) return fail(RCX_ERR_BAD_ARG, "null gradient / weight pointer");
-    if (!known_dtype(gy_dtype) || (gw_out && !known_dtype(grad_dtype))) return fail(RCX_ERR_BAD_ARG, "unknown gy / gradient dtype");
-    if (level < 0 || level > RCX_MAX_LEVEL) return fail(RCX_ERR_BAD_ARG, "level %d outside [0,%d]", level, RCX_MAX_LEVEL);
-    if (mode != RCX_MODE_BILINEAR && mode != RCX_MODE_NEAREST) return fail(RCX_ERR_BAD_ARG, "unknown mode %d", mode);
-    if (C % 4) return fail(RCX_ERR_UNSUPPORTED, "the backward kernels need C %% 4 == 0, got C=%d", C);
+    if (gw_out && !known_dtype(grad_dtype)) return fail(RCX_ERR_BAD_ARG, "unknown gradient dtype %d", grad_dtype);
+    if (int rc = check_bwd_args(gy_dtype, C, level, mode)) return rc;
     const TrainLadder L = make_train_ladder(N, C, H, W, level, k);
     if (level >= 1 && !saved) return fail(RCX_ERR_BAD_ARG, "null saved-activation buffer");
     if (!workspace || workspace_bytes < L.bwd_total)
         return fail(RCX_ERR_WORKSPACE, "backward workspace too small: need %zu bytes, got %zu", L.bwd_total, workspace_bytes);
-    const BwdSchedule sch = bwd_schedule(L, N, C, level, k, dtype);
+    const BwdSchedule sch = bwd_schedule(L, N, C, level, k, dtype, true);
     if (gy_dtype != RCX_DTYPE_F32 && !(sch.kind != BWD_STEPS && gy_dtype == dtype && dtype == RCX_DTYPE_BF16))
         return fail(RCX_ERR_UNSUPPORTED, "gy of dtype %d: this problem takes float32 (rcx_recconv2d_bwd_gy_dtype)", gy_dtype);
     if (gw_out)
         for (int i = 0; i < level + 2; ++i)
             if (!gw_out[i]) return fail(RCX_ERR_BAD_ARG, "null gw_out[%d]", i);
     hipStream_t s = (hipStream_t)stream;
-    BwdRun B{L};
+    BwdRun B{L, true, "bwd: "};
     B.x = x; B.gy = gy; B.wpack = wpack; B.wflip = wpack_flipped; B.saved = (const char*)saved; B.ws = (char*)workspace; B.gx = gx;
     B.gy_dt = gy_dtype; B.N = N; B.C = C; B.level = level; B.k = k; B.mode = mode; B.dtype = dtype; B.s = s;
     // where the final reduction leaves conv i's gradients: the packed float32 rows, or the parameters' own tensors
@@ -680,13 +713,13 @@ int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* 
         J.gw[i] = gw_out ? (float*)gw_out[i] : gwpack + (size_t)i * k * k * C;
         J.gb[i] = gw_out ? (gb_out ? (float*)gb_out[i] : nullptr) : (gbpack ? gbpack + (size_t)i * C : nullptr);
     }
-    if (sch.kind == BWD_ONE) RCX_TRY(one_launch(B, x, gy, gy_dtype, gx, 0, H, level, dtype), "bwd: fused block");
+    if (sch.kind == BWD_ONE) RCX_TRY(one_launch(B, gy, gy_dtype, gx, 0, H, level, dtype), "fused block", B.prefix);
     else if (int rc = sch.kind == BWD_TILED ? bwd_tiled(B, sch.m) : bwd_steps(B, sch.m)) return rc;
     // every weight gradient of the block in one reduction launch (job 0 sums the down conv's levels, coarsest first).  With no ladder the shared
     // down weight is unused: conv 0 is reduced alone, and the down gradient zeroed.
     float* const gw0 = J.gw[0], * const gb0 = J.gb[0];
     if (level == 0) { J.njobs = 1; J.gw[0] = J.gw[1]; J.gb[0] = J.gb[1]; J.nslots[0] = J.nslots[1]; J.part[0][0] = J.part[1][0]; J.rows[0][0] = J.rows[1][0]; }
-    RCX_TRY(rcx::bwd_wgrad_reduce_jobs(J, s), "bwd: weight-gradient reduction");
+    RCX_TRY(rcx::bwd_wgrad_reduce_jobs(J, s), "weight-gradient reduction", B.prefix);
     if (level >= 1) return 0;
     const size_t esz = gw_out && grad_dtype != RCX_DTYPE_F32 ? 2 : 4;
     hipError_t e = hipMemsetAsync(gw0, 0, esz * k * k * C, s);
@@ -695,105 +728,25 @@ int rcx_recconv2d_bwd(const void* x, const void* gy, int gy_dtype, const float* 
 }
 
 // ---- the input-only backward: gx = A^T gy, from gy and the taps alone (the block is linear in x) ----
-namespace {
-
-// The workspace of an input-only backward: none for the one-launch blocks, else the float32 gradient planes of the training backward's
-// ladder (gT_0 .. gT_L and the resized-gradient plane) without its partial-sum buffers
-size_t bwd_input_workspace(const TrainLadder& L, BwdKind kind) { return kind == BWD_ONE ? 0 : L.part_off; }
-
-struct AdjRun {
-    const TrainLadder& L;
-    const void* gy;
-    void* gx;
-    const float *wpack, *wflip;
-    char* ws;
-    int gy_dt, N, C, level, k, mode, dtype;
-    hipStream_t s;
-    const float* Wd(int i) const { return wpack + (size_t)i * k * k * C; }
-    const float* Wf(int i) const { return wflip + (size_t)i * k * k * C; }
-    float* G(int l) const { return (float*)(ws + L.g_off[l]); }
-};
-
-// the 14x14 tail: g = dL/dC_m (float32) -> G_m (float32)
-hipError_t adj_tail(const AdjRun& R, const float* g, float* G)
-{
-    return rcx::cpladj_recconv(g, RCX_DTYPE_F32, R.wpack, R.wflip, G, RCX_DTYPE_F32, R.N, R.C, 14, R.mode == RCX_MODE_NEAREST ? 1 : 0, R.s);
-}
-
-// BWD_TILED without the weight gradients: gC_{l+1} = R^T K^ g_l top-down, the tail, then G_l = K^ g_l + D^T G_{l+1} bottom-up (as bwd_tiled)
-int adj_tiled(const AdjRun& R, int m)
-{
-    const TrainLadder& L = R.L;
-    const int N = R.N, C = R.C, md = R.mode == RCX_MODE_NEAREST ? 1 : 0;
-    float* gcl[RCX_MAX_LEVEL + 1] = {};
-    size_t off = 0;
-    for (int l = 1; l <= m; ++l) { gcl[l] = (float*)(R.ws + L.g_off[0] + off); off += align256(sizeof(float) * (size_t)N * C * L.h[l] * L.w[l]); }
-    auto g_of = [&](int l) { return l == 0 ? R.gy : (const void*)gcl[l]; };
-    auto gdt_of = [&](int l) { return l == 0 ? R.gy_dt : RCX_DTYPE_F32; };
-    for (int l = 0; l < m; ++l)
-        RCX_TRY(rcx::bwd_gc_cpt(g_of(l), gdt_of(l), gcl[l + 1], R.Wf(1 + R.level - l), N, C, L.h[l], md, R.s), "bwd input: gradient handed down");
-    RCX_TRY(adj_tail(R, gcl[m], R.G(m)), "bwd input: 14x14 tail");
-    for (int l = m - 1; l >= 0; --l)
-        RCX_TRY(rcx::bwd_gx_cpt(g_of(l), gdt_of(l), R.G(l + 1), l == 0 ? R.gx : (void*)R.G(l), l == 0 ? R.dtype : RCX_DTYPE_F32, R.Wf(1 + R.level - l),
-                                R.Wd(0), N, C, L.h[l], R.s), "bwd input: gradient handed up");
-    return 0;
-}
-
-// BWD_STEPS without the weight gradients: the per-step adjoint chain (as bwd_steps), float32 throughout, down to the tail (m > 0)
-int adj_steps(const AdjRun& R, int m)
-{
-    const TrainLadder& L = R.L;
-    const int N = R.N, C = R.C, H = L.h[0], W = L.w[0], level = R.level, k = R.k, mode = R.mode, dtype = R.dtype;
-    float* gC = (float*)(R.ws + L.gc_off);
-    // gT_0 = K_L^T gy (gx itself with no ladder)
-    RCX_TRY(step_dwconv(R.gy, level == 0 ? R.gx : (void*)R.G(0), R.Wf(1 + level), nullptr, N, C, H, W, k, 1, RCX_DTYPE_F32,
-                        level == 0 ? dtype : RCX_DTYPE_F32, R.s), "bwd input: final conv");
-    for (int l = 1; l <= level; ++l) {
-        RCX_TRY(rcx::bwd_resize(R.G(l - 1), gC, N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], mode, R.s), "bwd input: resize adjoint");
-        if (l == m) { RCX_TRY(adj_tail(R, gC, R.G(m)), "bwd input: 14x14 tail"); break; }
-        RCX_TRY(step_dwconv(gC, R.G(l), R.Wf(1 + level - l), nullptr, N, C, L.h[l], L.w[l], k, 1, RCX_DTYPE_F32, RCX_DTYPE_F32, R.s), "bwd input: conv");
-    }
-    for (int l = m ? m : level; l >= 1; --l)
-        RCX_TRY(rcx::bwd_down_input(R.G(l - 1), R.G(l), l == 1 ? R.gx : (void*)R.G(l - 1), l == 1 ? dtype : RCX_DTYPE_F32, R.Wd(0),
-                                    N, C, L.h[l - 1], L.w[l - 1], L.h[l], L.w[l], k, R.s), "bwd input: down conv");
-    return 0;
-}
-
-bool bwd_input_extents_ok(int N, int C, int H, int W, int level, int k, int dtype)
-{
-    return N > 0 && C > 0 && H > 0 && W > 0 && level >= 0 && level <= RCX_MAX_LEVEL && k > 0 && (k & 1) && known_dtype(dtype);
-}
-
-}  // namespace
-
 size_t rcx_recconv2d_bwd_input_workspace_bytes(int N, int C, int H, int W, int level, int k)
 {
-    if (!bwd_input_extents_ok(N, C, H, W, level, k, RCX_DTYPE_F32)) return 0;
+    if (!bwd_extents_ok(N, C, H, W, level, k)) return 0;
     const TrainLadder L = make_train_ladder(N, C, H, W, level, k);
-    int m;
     // the one-launch kernels take every dtype the fused forward does, so the float32 schedule decides for all three
-    return bwd_input_workspace(L, bwd_input_schedule(L, N, C, level, k, RCX_DTYPE_F32, &m));
+    return bwd_input_workspace(L, bwd_schedule(L, N, C, level, k, RCX_DTYPE_F32, false).kind);
 }
 
 int rcx_recconv2d_bwd_input_gy_dtype(int N, int C, int H, int W, int level, int k, int dtype)
 {
-    if (!bwd_input_extents_ok(N, C, H, W, level, k, dtype) || dtype == RCX_DTYPE_F32 || C % 4) return RCX_DTYPE_F32;
+    if (!bwd_extents_ok(N, C, H, W, level, k) || !known_dtype(dtype) || dtype == RCX_DTYPE_F32 || C % 4) return RCX_DTYPE_F32;
     // the block's own 16-bit type where the one-launch or tiled kernels read gy (bfloat16 and float16 alike: no weight-gradient kernel runs)
-    int m;
-    return bwd_input_schedule(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype, &m) != BWD_STEPS ? dtype : RCX_DTYPE_F32;
+    return bwd_schedule(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype, false).kind != BWD_STEPS ? dtype : RCX_DTYPE_F32;
 }
 
 const char* rcx_recconv2d_bwd_input_plan(int N, int C, int H, int W, int level, int k, int dtype)
 {
-    if (!bwd_input_extents_ok(N, C, H, W, level, k, dtype)) return "invalid";
-    if (rcx::opt::hand_kernels_off()) return "generic";
     static thread_local char desc[64];
-    int m;
-    const BwdKind kind = bwd_input_schedule(make_train_ladder(N, C, H, W, level, k), N, C, level, k, dtype, &m);
-    if (kind == BWD_ONE) return H == 14 ? "one(k_recconv_adj_cpl14)" : "one(k_recconv_adj_cpl7)";
-    if (kind == BWD_TILED) snprintf(desc, sizeof(desc), "tiled(levels=%d)+one(k_recconv_adj_cpl14)", m);
-    else if (m) snprintf(desc, sizeof(desc), "steps+one(k_recconv_adj_cpl14)");
-    return kind == BWD_STEPS && !m ? "steps" : desc;
+    return bwd_plan(desc, N, C, H, W, level, k, dtype, false, "k_recconv_adj_");
 }
 
 int rcx_recconv2d_bwd_input(const void* gy, int gy_dtype, const float* wpack, const float* wpack_flipped, void* gx,
@@ -803,26 +756,20 @@ int rcx_recconv2d_bwd_input(const void* gy, int gy_dtype, const float* wpack, co
     if (int rc = check_common(gy, gx, N, C, H, W, k, dtype)) return rc;
     if (!wpack || !wpack_flipped) return fail(RCX_ERR_BAD_ARG, "null weight pack");
     if (gy == gx) return fail(RCX_ERR_BAD_ARG, "gx must not alias gy");
-    if (!known_dtype(gy_dtype)) return fail(RCX_ERR_BAD_ARG, "unknown gy dtype %d", gy_dtype);
-    if (level < 0 || level > RCX_MAX_LEVEL) return fail(RCX_ERR_BAD_ARG, "level %d outside [0,%d]", level, RCX_MAX_LEVEL);
-    if (mode != RCX_MODE_BILINEAR && mode != RCX_MODE_NEAREST) return fail(RCX_ERR_BAD_ARG, "unknown mode %d", mode);
-    if (C % 4) return fail(RCX_ERR_UNSUPPORTED, "the backward kernels need C %% 4 == 0, got C=%d", C);
+    if (int rc = check_bwd_args(gy_dtype, C, level, mode)) return rc;
     const TrainLadder L = make_train_ladder(N, C, H, W, level, k);
-    int m;
-    const BwdKind kind = bwd_input_schedule(L, N, C, level, k, dtype, &m);
-    const size_t need = bwd_input_workspace(L, kind);
+    const BwdSchedule sch = bwd_schedule(L, N, C, level, k, dtype, false);
+    const size_t need = bwd_input_workspace(L, sch.kind);
     if (need && (!workspace || workspace_bytes < need))
         return fail(RCX_ERR_WORKSPACE, "input-backward workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    if (gy_dtype != RCX_DTYPE_F32 && !(kind != BWD_STEPS && gy_dtype == dtype))
+    if (gy_dtype != RCX_DTYPE_F32 && !(sch.kind != BWD_STEPS && gy_dtype == dtype))
         return fail(RCX_ERR_UNSUPPORTED, "gy of dtype %d: this problem takes float32 (rcx_recconv2d_bwd_input_gy_dtype)", gy_dtype);
-    AdjRun R{L};
-    R.gy = gy; R.gx = gx; R.wpack = wpack; R.wflip = wpack_flipped; R.ws = (char*)workspace;
-    R.gy_dt = gy_dtype; R.N = N; R.C = C; R.level = level; R.k = k; R.mode = mode; R.dtype = dtype; R.s = (hipStream_t)stream;
-    if (kind == BWD_ONE) {
-        RCX_TRY(rcx::cpladj_recconv(gy, gy_dtype, wpack, wpack_flipped, gx, dtype, N, C, H, mode == RCX_MODE_NEAREST ? 1 : 0, R.s), "bwd input: fused block");
-        return 0;
-    }
-    return kind == BWD_TILED ? adj_tiled(R, m) : adj_steps(R, m);
+    BwdRun B{L, false, "bwd input: "};
+    B.gy = gy; B.gx = gx; B.wpack = wpack; B.wflip = wpack_flipped; B.ws = (char*)workspace;
+    B.gy_dt = gy_dtype; B.N = N; B.C = C; B.level = level; B.k = k; B.mode = mode; B.dtype = dtype; B.s = (hipStream_t)stream;
+    if (sch.kind == BWD_ONE) RCX_TRY(one_launch(B, gy, gy_dtype, gx, 0, H, level, dtype), "fused block", B.prefix);
+    else return sch.kind == BWD_TILED ? bwd_tiled(B, sch.m) : bwd_steps(B, sch.m);
+    return 0;
 }
 
 #undef RCX_TRY

@@ -48,6 +48,14 @@ def _dt(t):
     return code
 
 
+def _gy_as_taken(gy, block_dtype, want):
+    """dL/dy as a backward entry reads it: as it is when float32, or when it has the block's own dtype and that is the dtype id `want` the
+    library's *_bwd_gy_dtype query answered for the problem; converted to float32 otherwise."""
+    if gy.dtype == torch.float32 or (gy.dtype == block_dtype and _DT.get(gy.dtype) == want):
+        return gy
+    return gy.to(torch.float32)
+
+
 def _require_gpu(t, name):
     if not t.is_cuda:
         raise _lib.RcxError(f"{name} is on {t.device}: the recnext_amd token mixers only run as HIP kernels on a GPU "
@@ -343,7 +351,7 @@ def upadd_dwconv_backward(x, coarse, gy, w_kkc, k=5, mode="nearest", need_input_
     hc, wc = coarse.shape[2:]
     lib = _lib.load()
     want = lib.rcx_upadd_dwconv_bwd_gy_dtype(n, c, h, w, hc, wc, k, _dt(x))
-    gy = _nhwc(gy if (gy.dtype == torch.float32 or (_DT.get(gy.dtype) == want and gy.dtype == x.dtype)) else gy.to(torch.float32), "grad_output")
+    gy = _nhwc(_gy_as_taken(gy, x.dtype, want), "grad_output")
     wflip = w_kkc.view(k, k, c).flip(0, 1).contiguous()
     gx = _empty_nhwc(n, c, h, w, x.dtype, x.device) if need_input_grad else None
     gc = _empty_nhwc(n, c, hc, wc, torch.float32, x.device) if need_coarse_grad else None
@@ -883,7 +891,7 @@ def recconv2d_backward(x, gy, wpack, saved, level, k, mode="bilinear", need_bias
                          "(recconv2d_forward_train)")
     x = _nhwc(x)
     want = lib.rcx_recconv2d_bwd_gy_dtype(n, c, h, w, level, k, _dt(x))
-    gy = _nhwc(gy if (gy.dtype == torch.float32 or (_DT.get(gy.dtype) == want and gy.dtype == x.dtype)) else gy.to(torch.float32), "grad_output")
+    gy = _nhwc(_gy_as_taken(gy, x.dtype, want), "grad_output")
     if wflip is None:
         wflip = wpack.view(level + 2, k, k, c).flip(1, 2).contiguous()
     gx = _empty_nhwc(n, c, h, w, x.dtype, x.device)
@@ -930,7 +938,7 @@ def recconv2d_input_backward(gy, wpack, wflip, level, k, mode="bilinear", dtype=
     n, c, h, w = gy.shape
     lib = _lib.load()
     want = lib.rcx_recconv2d_bwd_input_gy_dtype(n, c, h, w, level, k, _DT[dtype])
-    gy = _nhwc(gy if (gy.dtype == torch.float32 or (gy.dtype == dtype and _DT[gy.dtype] == want)) else gy.to(torch.float32), "grad_output")
+    gy = _nhwc(_gy_as_taken(gy, dtype, want), "grad_output")
     gx = _empty_nhwc(n, c, h, w, dtype, gy.device)
     nbytes = lib.rcx_recconv2d_bwd_input_workspace_bytes(n, c, h, w, level, k)    # 0 for the one-launch blocks: nothing to allocate
     ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device) if nbytes else None
