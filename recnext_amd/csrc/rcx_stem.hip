@@ -1,17 +1,46 @@
 // RecNextStem in ONE launch (bf16 inference): y = conv3x3_s2(gelu(conv3x3_s2(x) + b1)) + b2, both convs BN-folded (model/recnext.py:134-146 `RecNextStem`,
 // :75-97 ConvNorm.fuse).  As library calls the stem is two convs, two bias adds and a GELU (0.39 ms of RecNeXt-M3's 2.9 ms step): the intermediate
 // 112 x 112 x C/2 tensor -- twice the size of the stem's output -- is written once and read three times.  Here it exists only as a 17 x 17 tile in LDS:
-//   a workgroup (4 waves) owns an 8 x 8 tile of output pixels;
+//   a persistent workgroup (4 waves; two per compute unit at RecNeXt-M3's 32 / 64 channels) walks 8 x 8 tiles of output pixels, the weights in LDS once;
+//   x. the tile's 35 rows of x (36 pixels x 3 channels = 216 bytes each, from image pixel 32 tx - 4) are requested a tile ahead into registers and written to LDS at
+//      the top of the tile: as 27 aligned 8-byte pieces a row where the rows of the image allow it (W % 4 == 0, x 8-byte aligned: 4 loads a thread), else as single
+//      bf16 (15 loads a thread) -- the same LDS image either way;
 //   A. conv1 + bias + GELU for the 17 x 17 pixels of the intermediate the tile needs, ALSO on the matrix cores (K = 27 taps padded to 32; the im2col operand gathered
-//      from a 35 x 35 x 3 tile of x in LDS: a pixel's inputs are three runs of nine contiguous bf16), rounded to bf16 into LDS (zeros outside the intermediate's plane:
+//      from the x tile in LDS: a pixel's inputs are three runs of nine contiguous bf16), rounded to bf16 into LDS (zeros outside the intermediate's plane:
 //      the second conv's padding).  (A first version ran it on the vector pipe, a pixel per thread with the weights as scalar operands: 488 us, no faster than the library.)
 //   B. conv2 as an implicit GEMM on the matrix cores: D (32 out channels x 32 pixels) = sum over (tap, 16-channel group) of W2 fragment x h1 fragment, the h1
 //      fragment read straight from the LDS tile at the tap's offset (8 consecutive channels of one pixel = 16 bytes), the W2 fragments packed on the host
-//      (ops.pack_stem); + b2 -> bf16 -> y.
+//      (ops.pack_stem); + b2 -> bf16 -> the wave's own 32 pixel x 32 channel image in LDS -> y, 16 bytes a lane with a pixel's 64 bytes contiguous across four lanes
+//      (a pixel per lane straight to memory -- 8 bytes of each of 32 pixels a request -- cost this kernel 0.9 k of a tile's 15.7 k cycles per wave in the store itself
+//      and another 1.1 k in the x requests queued behind it: profiles/r09_stem_timeline.txt).
+// -DRCX_STEM_STAMPS is the diagnostic build of this file alone (tools/stem_timeline.py): s_memtime at the phase boundaries, summed per wave into a buffer of its own.
 // Numerics: float32 accumulation, the intermediate rounded to bf16 once (as the library path does), exact GELU (rcx_gelu.h).
 #include "rcx_common.h"
 #include "rcx_launch.h"
 #include "rcx_gelu.h"
+#include <type_traits>
+
+
+#ifdef RCX_STEM_STAMPS
+#define RCX_STAMP(k)                                                                                            \
+    {                                                                                                           \
+        __builtin_amdgcn_sched_barrier(0);                                                                      \
+        unsigned long long t_;                                                                                  \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                              \
+        __builtin_amdgcn_sched_barrier(0);                                                                      \
+        tsum[k] += t_ - tlast;                                                                                  \
+        tlast = t_;                                                                                             \
+    }
+#define RCX_STAMP_ARG , unsigned long long* __restrict__ stamps
+#define RCX_STAMP_VAL , g_stamps
+namespace rcx {
+static unsigned long long* g_stamps = nullptr;
+}
+#else
+#define RCX_STAMP(k)
+#define RCX_STAMP_ARG
+#define RCX_STAMP_VAL
+#endif
 
 namespace rcx {
 namespace stem {
@@ -23,23 +52,34 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4q __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2q __attribute__((ext_vector_type(2)));
+constexpr int YIMG = 32 * 64;              // bytes of a wave's output image in LDS
 
-// CM = channels of the intermediate, KC = CM rounded up to a multiple of 16 (the k-steps of a tap), M1 = ceil(CM / 32) tiles of the first product, MT = output tiles
-template <int CM, int KC, int MT>
+// what a wave wrote to its LDS image is read by its other lanes (and the other way round)
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// CM = channels of the intermediate, KC = CM rounded up to a multiple of 16 (the k-steps of a tap), M1 = ceil(CM / 32) tiles of the first product, MT = output tiles,
+// XW = x rows move as 8-byte pieces (W % 4 == 0 and an 8-byte aligned x: every piece lies wholly inside or outside a row of the image), else as single bf16
+template <int CM, int KC, int MT, bool XW>
 __global__ void __launch_bounds__(256)
 k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __restrict__ w1frag, const float* __restrict__ b1, const u32x4q* __restrict__ w2frag,
-       const float* __restrict__ b2, int N, int H, int W, int H1, int W1, int H2, int W2, int CO, int tiles_x, int tiles_y)
+       const float* __restrict__ b2, int N, int H, int W, int H1, int W1, int H2, int W2, int CO, int tiles_x, int tiles_y, int y16 RCX_STAMP_ARG)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     constexpr int KS = 9 * (KC / 16), NF = MT * KS, PIX = 2 * KC + 16, R = 17;      // k-steps, W2 fragments, bytes per pixel of the h1 tile (16 of padding: banks)
-    constexpr int M1 = (CM + 31) / 32, XR = 35, XE = 105, XP = 216;                  // x tile: 35 rows of 35 pixels x 3 channels = 105 bf16 (210 bytes), pitch 216
-    constexpr int NPT = (R * R + 31) / 32;                                           // pixel tiles of the first product; the h1 tile holds 32 NPT pixels, the x tile 37 rows: no guarded LDS writes
+    constexpr int M1 = (CM + 31) / 32, XR = 35, XE = 105, XP = 216, XROWS = 38;      // x tile: 35 rows of 36 pixels x 3 channels (216 bytes: image pixels 32 tx - 4 ..; the first is not read)
+    constexpr int NPT = (R * R + 31) / 32;                                           // pixel tiles of the first product; the h1 tile holds 32 NPT pixels, the x tile 38 rows: no guarded LDS writes
     const u32x4q* const Lf = reinterpret_cast<const u32x4q*>(lds_raw);               // [NF] W2 fragments, then [2 M1] W1 fragments
     const u32x4q* const Lf1 = Lf + NF * 64;
     unsigned char* const Lh = lds_raw + (size_t)(NF + 2 * M1) * 1024;                // h1 tile [17 x 17][PIX]
-    unsigned char* const Lx = Lh + (size_t)32 * NPT * PIX;                           // x tile [37][XP]
-    float* const Lb1 = reinterpret_cast<float*>(Lx + (size_t)(XR + 2) * XP);        // [32 M1] then b2 [32 MT]
+    unsigned char* const Lx = Lh + (size_t)32 * NPT * PIX;                           // x tile [38][XP]
+    float* const Lb1 = reinterpret_cast<float*>(Lx + (size_t)XROWS * XP);           // [32 M1] then b2 [32 MT]
     float* const Lb2 = Lb1 + 32 * M1;
+    unsigned char* const Ly = reinterpret_cast<unsigned char*>(Lb2 + 32 * MT) + (size_t)(threadIdx.x >> 6) * YIMG;      // this wave's output image: [32 pixels][32 channels] bf16
     {                                                                                // the weights: once per workgroup (it walks tiles blockIdx.x, + gridDim.x, ...)
         u32x4q* Lw = reinterpret_cast<u32x4q*>(lds_raw);
         for (int i = threadIdx.x; i < NF * 64; i += 256) Lw[i] = w2frag[i];
@@ -49,38 +89,63 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
     }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     const unsigned xbytes = (unsigned)H * (unsigned)W * 6u;                          // one image of x (3 channels, bf16); checked < 2^31 by the launcher
-    // the x tile of a tile: rows 32 ty - 3 + i, pixels 32 tx - 3 + j of the image (zeros outside it: the first conv's padding); consecutive lanes = consecutive
-    // elements; a thread's XN elements are requested a tile ahead (during the previous tile's second product) and written to LDS at the top of the tile
-    constexpr int XN = (XR * XE + 255) / 256;
-    static_assert(XN * 256 <= (XR + 2) * XE, "the two spare x-tile rows take the last round's overshoot");
-    unsigned xgo[XN], xlo[XN], xij[XN];               // element u of this thread: offset within the image relative to the tile's first element, LDS offset, (row, pixel) of the tile
+    // the x tile of a tile: rows 32 ty - 3 + i of the image, bytes 6 (32 tx - 4) .. + 216 of each (zeros outside the image: the first conv's padding).  The tile starts
+    // a pixel left of the first one read so that, with XW, its rows are 27 aligned 8-byte pieces of the image: piece e of the tile (row e / 27) lands at LDS byte 8 e,
+    // four pieces a thread.  Without XW: 35 pixels a row from 32 tx - 3 as single bf16, fifteen a thread.  Either way a thread's pieces are requested a tile ahead
+    // (during the previous tile's second product) and written to LDS at the top of the tile.
+    constexpr int XN = XW ? 4 : (XR * XE + 255) / 256;
+    static_assert(4 * 256 * 8 <= XROWS * XP && ((XR * XE + 255) / 256 * 256 + XE - 1) / XE <= XROWS, "the spare x-tile rows take the last round's overshoot");
+    unsigned xgo[XN], xlo[XN], xij[XN];               // piece u of this thread: offset within the image relative to the tile's first byte, LDS offset, (row, pixel | piece) of the tile
 #pragma unroll
     for (int u = 0; u < XN; ++u) {
-        const int e = threadIdx.x + 256 * u, i = e / XE, q = e - i * XE, px = q / 3;
-        xgo[u] = ((unsigned)(i * W + px) * 3u + (unsigned)(q - 3 * px)) * 2u;
-        xlo[u] = (unsigned)(i * XP + 2 * q);
-        xij[u] = (unsigned)i | ((unsigned)px << 8) | (e < XR * XE ? 0u : 0x10000u);
+        const int e = threadIdx.x + 256 * u;
+        if constexpr (XW) {
+            const int i = e / 27, k = e - 27 * i;
+            xgo[u] = (unsigned)(i * W) * 6u + 8u * (unsigned)k;
+            xlo[u] = 8u * (unsigned)e;
+            xij[u] = (unsigned)i | ((unsigned)k << 8) | (e < XR * 27 ? 0u : 0x10000u);
+        } else {
+            const int i = e / XE, q = e - i * XE, px = q / 3;
+            xgo[u] = ((unsigned)(i * W + px) * 3u + (unsigned)(q - 3 * px)) * 2u + 6u;
+            xlo[u] = (unsigned)(i * XP + 2 * q + 6);
+            xij[u] = (unsigned)i | ((unsigned)px << 8) | (e < XR * XE ? 0u : 0x10000u);
+        }
     }
-    bf16_t xq[XN];
+    typename std::conditional<XW, u32x2q, bf16_t>::type xq[XN];
     auto request_x = [&](int t) {
         const int nn = t / (tiles_x * tiles_y), trr = t - nn * tiles_x * tiles_y, tyy = trr / tiles_x, txx = trr - tyy * tiles_x;
         const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)nn * H * W * 3), 0, xbytes, 0x00020000);
-        const int y0 = 32 * tyy - 3, x0 = 32 * txx - 3;
-        const unsigned base = (unsigned)((y0 * W + x0) * 6);                       // (may wrap below zero: only added to offsets of elements inside the image)
+        const int y0 = 32 * tyy - 3, x0 = 32 * txx - 4;
+        const unsigned base = (unsigned)((y0 * W + x0) * 6);                       // (may wrap below zero: only added to offsets of pieces inside the image)
 #pragma unroll
         for (int u = 0; u < XN; ++u) {
-            const int yy = y0 + (int)(xij[u] & 0xff), xx = x0 + (int)((xij[u] >> 8) & 0xff);
-            const bool ok = xij[u] < 0x10000u && yy >= 0 && yy < H && xx >= 0 && xx < W;
-            xq[u] = (bf16_t)__builtin_amdgcn_raw_buffer_load_b16(xsrc, (int)(ok ? base + xgo[u] : 0x80000000u), 0, 0);      // outside the image: past the buffer, reads 0
+            const int yy = y0 + (int)(xij[u] & 0xff);
+            if constexpr (XW) {
+                const int cb = 6 * x0 + 8 * (int)((xij[u] >> 8) & 0xff);            // the piece's first byte within the row
+                const bool ok = xij[u] < 0x10000u && yy >= 0 && yy < H && cb >= 0 && cb < 6 * W;
+                xq[u] = __builtin_amdgcn_raw_buffer_load_b64(xsrc, (int)(ok ? base + xgo[u] : 0x80000000u), 0, 0);           // outside the image: past the buffer, reads 0
+            } else {
+                const int xx = x0 + 1 + (int)((xij[u] >> 8) & 0xff);
+                const bool ok = xij[u] < 0x10000u && yy >= 0 && yy < H && xx >= 0 && xx < W;
+                xq[u] = (bf16_t)__builtin_amdgcn_raw_buffer_load_b16(xsrc, (int)(ok ? base + xgo[u] : 0x80000000u), 0, 0);
+            }
         }
     };
     const int ntiles = N * tiles_x * tiles_y;
     if ((int)blockIdx.x < ntiles) request_x(blockIdx.x);
+#ifdef RCX_STEM_STAMPS
+    unsigned long long tsum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
+    RCX_STAMP(9)
+    tsum[9] = 0;
+#endif
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int n = tile / (tiles_x * tiles_y), tr = tile - n * tiles_x * tiles_y, ty = tr / tiles_x, tx = tr - ty * tiles_x;
 #pragma unroll
-    for (int u = 0; u < XN; ++u) *reinterpret_cast<bf16_t*>(Lx + xlo[u]) = xq[u];
-    __syncthreads();                                   // the x tile (and, the first time, the weights) is in LDS; every wave has left the previous tile's second product
+    for (int u = 0; u < XN; ++u) *reinterpret_cast<decltype(&xq[0])>(Lx + xlo[u]) = xq[u];
+    RCX_STAMP(0)
+    __syncthreads();
+    RCX_STAMP(1)
+    //                                  // the x tile (and, the first time, the weights) is in LDS; every wave has left the previous tile's second product
 
     // ---- A. the intermediate's 17 x 17 pixels (rows 16 ty - 1 + i, columns 16 tx - 1 + j) on the matrix cores: D (32 channels x 32 pixels) = W1 (channel x 27 taps,
     // padded to 32) x im2col.  Pixel (i, j) reads x-tile rows 2 i + dy, elements 6 j .. 6 j + 8: its 27 inputs are three runs of nine contiguous bf16, k = 9 dy + e.
@@ -96,7 +161,7 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
         const int p = 32 * pt + r, pc = p < R * R ? p : R * R - 1, i = pc / R, j = pc - i * R;
         const int r1 = 16 * ty - 1 + i, c1 = 16 * tx - 1 + j;
         const bool inside = p < R * R && r1 >= 0 && r1 < H1 && c1 >= 0 && c1 < W1;
-        const unsigned char* const xp = Lx + (2 * i) * XP + 12 * j;
+        const unsigned char* const xp = Lx + (2 * i) * XP + 12 * j + 6;
         bf16x8 bfr[2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -106,6 +171,7 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
             const u32x4q pk = {(unsigned)v[0] | ((unsigned)v[1] << 16), (unsigned)v[2] | ((unsigned)v[3] << 16), (unsigned)v[4] | ((unsigned)v[5] << 16), (unsigned)v[6] | ((unsigned)v[7] << 16)};
             bfr[ks] = __builtin_bit_cast(bf16x8, pk);
         }
+        RCX_STAMP(2)
 #pragma unroll
         for (int m1 = 0; m1 < M1; ++m1) {
             f32x16 d;
@@ -113,6 +179,10 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
             for (int q = 0; q < 16; ++q) d[q] = 0.f;
             d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Lf1[(2 * m1 + 0) * 64 + lane]), bfr[0], d, 0, 0, 0);
             d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Lf1[(2 * m1 + 1) * 64 + lane]), bfr[1], d, 0, 0, 0);
+#ifdef RCX_STEM_STAMPS
+            asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, d[15]))));       // the products have landed
+            RCX_STAMP(3)
+#endif
             // + b1, gelu, bf16 -> the h1 tile (pixels outside the intermediate's plane: zeros, the second conv's padding; channels past CM: zero weights and bias)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -125,15 +195,18 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
                     *reinterpret_cast<u32x2q*>(Lh + (size_t)p * PIX + 2 * c0) = __builtin_bit_cast(u32x2q, o);
                 }
             }
+            RCX_STAMP(4)
         }
     }
     __syncthreads();
+    RCX_STAMP(5)
     if (tile + (int)gridDim.x < ntiles) request_x(tile + gridDim.x);
+    RCX_STAMP(6)
 
     // ---- B. conv2: wave w takes the (output tile mt, pixel tile nt) pairs w, w + 4, ...; pixel q of the 8 x 8 tile = (q / 8, q % 8)
     for (int pr = wave; pr < 2 * MT; pr += 4) {
         const int mt = pr >> 1, nt = pr & 1;
-        const int q = 32 * nt + r, py = q >> 3, px = q & 7;
+        const int q = 32 * nt + r, py = q >> 3, px = q & 7;      // (the product's pixel of this lane)
         const unsigned char* const hp = Lh + (size_t)((2 * py) * R + 2 * px) * PIX + 16 * h;
         f32x16 d0, d1;
 #pragma unroll
@@ -147,23 +220,48 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
             if (ks & 1) d1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, d1, 0, 0, 0);
             else d0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, d0, 0, 0, 0);
         }
-        const int oy = 8 * ty + py, ox = 8 * tx + px;
-        if (oy < H2 && ox < W2) {
-            bf16_t* const yp = y + ((size_t)(n * H2 + oy) * W2 + ox) * CO;
+#ifdef RCX_STEM_STAMPS
+        asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, d0[15]))), "s"(__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, d1[15]))));
+        RCX_STAMP(7)
+#endif
+        // + b2 -> bf16 -> this wave's LDS image (pixel r: 64 bytes, its 8-byte pieces XOR-ed with (r >> 1) & 7: a store's 16 lanes hit 16 bank pairs), then out with a
+        // pixel's 64 bytes contiguous across 4 lanes (16 bytes each; 8 lanes of 8 bytes where 2 CO or y is not 16-byte aligned): a request covers whole 64-byte runs of y
+        // instead of 8 bytes of each of 32 pixels
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int c0 = 32 * mt + 8 * g + 4 * h;
-                if (c0 < CO) {
-                    const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + c0);
-                    bf16x4 o;
-                    o[0] = (__bf16)(d0[4 * g + 0] + d1[4 * g + 0] + bb.x); o[1] = (__bf16)(d0[4 * g + 1] + d1[4 * g + 1] + bb.y);
-                    o[2] = (__bf16)(d0[4 * g + 2] + d1[4 * g + 2] + bb.z); o[3] = (__bf16)(d0[4 * g + 3] + d1[4 * g + 3] + bb.w);
-                    *reinterpret_cast<u32x2q*>(yp + c0) = __builtin_bit_cast(u32x2q, o);
-                }
+        for (int g = 0; g < 4; ++g) {
+            const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + 32 * mt + 8 * g + 4 * h);
+            bf16x4 o;
+            o[0] = (__bf16)(d0[4 * g + 0] + d1[4 * g + 0] + bb.x); o[1] = (__bf16)(d0[4 * g + 1] + d1[4 * g + 1] + bb.y);
+            o[2] = (__bf16)(d0[4 * g + 2] + d1[4 * g + 2] + bb.z); o[3] = (__bf16)(d0[4 * g + 3] + d1[4 * g + 3] + bb.w);
+            *reinterpret_cast<u32x2q*>(Ly + 64 * r + 8 * ((2 * g + h) ^ ((r >> 1) & 7))) = __builtin_bit_cast(u32x2q, o);
+        }
+        wave_sync();
+        if (y16) {
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                const int ql = 16 * it + (lane >> 2), ck = lane & 3, sw = (ql >> 1) & 7, q2 = 32 * nt + ql, oy = 8 * ty + (q2 >> 3), ox = 8 * tx + (q2 & 7), c0 = 32 * mt + 8 * ck;
+                const u32x2q lo = *reinterpret_cast<const u32x2q*>(Ly + 64 * ql + 8 * ((2 * ck) ^ sw)), hi = *reinterpret_cast<const u32x2q*>(Ly + 64 * ql + 8 * ((2 * ck + 1) ^ sw));
+                if (oy < H2 && ox < W2 && c0 < CO) *reinterpret_cast<u32x4q*>(y + ((size_t)(n * H2 + oy) * W2 + ox) * CO + c0) = u32x4q{lo.x, lo.y, hi.x, hi.y};
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int ql = 8 * it + (lane >> 3), ck = lane & 7, sw = (ql >> 1) & 7, q2 = 32 * nt + ql, oy = 8 * ty + (q2 >> 3), ox = 8 * tx + (q2 & 7), c0 = 32 * mt + 4 * ck;
+                const u32x2q v = *reinterpret_cast<const u32x2q*>(Ly + 64 * ql + 8 * (ck ^ sw));
+                if (oy < H2 && ox < W2 && c0 < CO) *reinterpret_cast<u32x2q*>(y + ((size_t)(n * H2 + oy) * W2 + ox) * CO + c0) = v;
             }
         }
+        wave_sync();                                   // (MT = 3: the wave's next pair writes the image again)
+        RCX_STAMP(8)
     }
+#ifdef RCX_STEM_STAMPS
+    tsum[9] += 1;
+#endif
     }
+#ifdef RCX_STEM_STAMPS
+    if (lane == 0)
+        for (int k = 0; k < 10; ++k) stamps[((size_t)blockIdx.x * 4 + wave) * 10 + k] = tsum[k];
+#endif
 }
 
 }  // namespace stem
@@ -196,22 +294,28 @@ static hipError_t launch_stem(const void* x, void* y, const void* w1, const floa
     const int H1 = (H + 1) / 2, W1 = (W + 1) / 2, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2, tx = (W2 + 7) / 8, ty = (H2 + 7) / 8;
     constexpr int KS = 9 * (KC / 16), PIX = 2 * KC + 16;
     constexpr int M1 = (CM + 31) / 32;
-    const size_t lds = (size_t)(MT * KS + 2 * M1) * 1024 + (size_t)320 * PIX + (size_t)37 * 216 + sizeof(float) * 32 * (M1 + MT);
+    const size_t lds = (size_t)(MT * KS + 2 * M1) * 1024 + (size_t)320 * PIX + (size_t)38 * 216 + sizeof(float) * 32 * (M1 + MT) + (size_t)4 * stem::YIMG;
+    // rows of x as 8-byte pieces where every row of every image starts on one (else as single bf16); 16-byte stores where every pixel of y does (else 8-byte)
+    const bool xw = W % 4 == 0 && ((size_t)x & 7) == 0;
+    const int y16 = CO % 8 == 0 && ((size_t)y & 15) == 0;
     const long long ntiles = (long long)N * tx * ty;
     if (ntiles > 0x7fffffffLL || lds > 160 * 1024) return hipErrorInvalidConfiguration;
     const long long per_cu = (long long)(160 * 1024 / lds) > 0 ? (long long)(160 * 1024 / lds) : 1;
     const long long grid = ntiles < ncu * per_cu ? ntiles : ncu * per_cu;          // persistent: the weights go to LDS once per workgroup
-#define RCX_STEM_GO(MT_)                                                                                                                   \
+#define RCX_STEM_GO(MT_, XW_)                                                                                                              \
     {                                                                                                                                      \
-        auto kfn = stem::k_stem<CM, KC, MT_>;                                                                                              \
+        auto kfn = stem::k_stem<CM, KC, MT_, XW_>;                                                                                         \
         RCX_SET_LDS_ONCE(kfn, lds);                                                                                                        \
         hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(256), lds, s, (const bf16_t*)x, (bf16_t*)y, (const stem::u32x4q*)w1, b1, (const stem::u32x4q*)w2frag, b2, \
-                           N, H, W, H1, W1, H2, W2, CO, tx, ty);                                                                          \
+                           N, H, W, H1, W1, H2, W2, CO, tx, ty, y16 RCX_STAMP_VAL);                                                        \
         return hipGetLastError();                                                                                                          \
     }
-    if (MT == 1) RCX_STEM_GO(1)
-    if (MT == 2) RCX_STEM_GO(2)
-    if (MT == 3) RCX_STEM_GO(3)
+    if (MT == 1 && xw) RCX_STEM_GO(1, true)
+    if (MT == 2 && xw) RCX_STEM_GO(2, true)
+    if (MT == 3 && xw) RCX_STEM_GO(3, true)
+    if (MT == 1) RCX_STEM_GO(1, false)
+    if (MT == 2) RCX_STEM_GO(2, false)
+    if (MT == 3) RCX_STEM_GO(3, false)
 #undef RCX_STEM_GO
     return hipErrorInvalidConfiguration;
 }
@@ -241,3 +345,12 @@ hipError_t stem_fwd(const void* x, void* y, const void* w1, const float* b1, con
 }
 
 }  // namespace rcx
+
+#ifdef RCX_STEM_STAMPS
+// the diagnostic build: this translation unit alone as a shared object (tools/stem_timeline.py); stamps = [grid][4 waves][10] cycle sums
+extern "C" int rcx_stem_diag_fwd(const void* x, void* y, const void* w1frag, const float* b1, const void* w2frag, const float* b2, int N, int H, int W, int CM, int CO, void* stamps, void* stream)
+{
+    rcx::g_stamps = (unsigned long long*)stamps;
+    return (int)rcx::stem_fwd(x, y, w1frag, b1, w2frag, b2, N, H, W, CM, CO, 1, (hipStream_t)stream);
+}
+#endif
