@@ -358,7 +358,34 @@ int rcx_ls_la3_fwd(const void* x, void* r, void* t, const float* w_rep, const fl
                    int dtype, void* stream);
 
 /*
- * Backward of rcx_linear_attention_fwd (the gradients engine.py:48-64 needs through RecAttn2d, model/recattn.py:16-28 / :39-51):
+ * The same token halves for ANY plane size (H x W >= 1 x 1, odd and non-square included): the image is cut into chunks of attention tokens and any
+ * number of workgroups work on it.  Same tensors, packs, argument rules and arithmetic as the two entries above (float32, the same elu(.)+1 and
+ * normaliser, r and t rounded once at their stores), plus a caller-provided float32 workspace of rcx_ls_*_tiled_workspace_bytes(...) bytes, 16-byte
+ * aligned, aliasing none of x, r, t: it holds the slice channels only (the fine slice in float32, RecAttn2d's half-size d and attention result, and
+ * one partial k^T v and sum(k) per image and chunk).  The library allocates nothing.  The partials are summed in chunk order, no atomics; the chunk
+ * length (64 tokens for split <= 64, else 32) depends on `split` alone, never on B: a batch and its shards give the same rows bit for bit.
+ * rcx_ls_recattn_tiled_fwd replaces lsnet/model/recattn.py:8-15 (RepVGGDW), :37-86 (LinearAttention1 / 2), :115-127 (RecAttn2d) and the slice / cat
+ *   of :226-237 in four launches (RepVGGDW on every channel; d, k and the partials; q and the attention on the half-size plane (H+1)/2 x (W+1)/2;
+ *   conv5(r_s + nearest(.)) back at H x W).  `heads` must be 1.
+ * rcx_ls_la3_tiled_fwd replaces :8-15, :89-112 (LinearAttention3) and :226-237 in three launches (RepVGGDW; k and the partials; q, the attention
+ *   and pe).  split a multiple of 2 heads and split / heads a multiple of 4.
+ * A short or NULL workspace returns RCX_ERR_WORKSPACE, a shape without a kernel RCX_ERR_UNSUPPORTED (rcx_ls_*_tiled_supported: 1 / 0; the workspace
+ * query returns 0 for such a shape).  rcx_ls_recattn_fwd / rcx_ls_la3_fwd and their queries keep their meaning: a caller asks those first.
+ */
+int rcx_ls_recattn_tiled_supported(int B, int H, int W, int C, int split, int heads, int dtype);
+size_t rcx_ls_recattn_tiled_workspace_bytes(int B, int H, int W, int C, int split, int heads, int dtype);
+int rcx_ls_recattn_tiled_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* w_down_kkc, const float* b_down,
+                             const float* wqT, const float* bq, const float* wkT, const float* bk, const float* w_pe_kkc, const float* b_pe,
+                             const float* w_conv_kkc, const float* b_conv, void* workspace, size_t workspace_bytes, int B, int H, int W, int C,
+                             int split, int heads, int dtype, void* stream);
+int rcx_ls_la3_tiled_supported(int B, int H, int W, int C, int split, int heads, int dtype);
+size_t rcx_ls_la3_tiled_workspace_bytes(int B, int H, int W, int C, int split, int heads, int dtype);
+int rcx_ls_la3_tiled_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* wqT, const float* bq,
+                         const float* wkT, const float* bk, const float* w_pe_kkc, const float* b_pe, void* workspace, size_t workspace_bytes,
+                         int B, int H, int W, int C, int split, int heads, int dtype, void* stream);
+
+/*
+ * Backward of rcx_linear_attention_fwd(the gradients engine.py:48-64 needs through RecAttn2d, model/recattn.py:16-28 / :39-51):
  *   given gout = dL/dout (B x n x C), writes gq = dL/dqpre, gk = dL/dkpre, gv = dL/dv (all B x n x C, `dtype`); dL/dpe = gout is the
  *   caller's.  float32 arithmetic, deterministic (fixed summation order).  C/heads at most 64.
  */

@@ -72,6 +72,12 @@ SIGNATURES = {
     "rcx_ls_recattn_fwd": (_i, [_vp] * 15 + [_i] * 7 + [_vp]),
     "rcx_ls_la3_supported": (_i, [_i] * 7),
     "rcx_ls_la3_fwd": (_i, [_vp] * 11 + [_i] * 7 + [_vp]),
+    "rcx_ls_recattn_tiled_supported": (_i, [_i] * 7),
+    "rcx_ls_recattn_tiled_workspace_bytes": (_sz, [_i] * 7),
+    "rcx_ls_recattn_tiled_fwd": (_i, [_vp] * 16 + [_sz] + [_i] * 7 + [_vp]),
+    "rcx_ls_la3_tiled_supported": (_i, [_i] * 7),
+    "rcx_ls_la3_tiled_workspace_bytes": (_sz, [_i] * 7),
+    "rcx_ls_la3_tiled_fwd": (_i, [_vp] * 12 + [_sz] + [_i] * 7 + [_vp]),
     "rcx_linear_attention_bwd": (_i, [_vp] * 7 + [_i] * 5 + [_vp]),
     "rcx_linear_attention_wide_supported": (_i, [_i] * 6),
     "rcx_linear_attention_wide_fwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),

@@ -1185,6 +1185,74 @@ int rcx_ls_la3_fwd(const void* x, void* r, void* t, const float* w_rep, const fl
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_ls_la3_fwd");
 }
 
+int rcx_ls_recattn_tiled_supported(int B, int H, int W, int C, int split, int heads, int dtype)
+{
+    return rcx::ls_recattn_tiled_applicable(B, H, W, C, split, heads, dtype) ? 1 : 0;
+}
+
+int rcx_ls_la3_tiled_supported(int B, int H, int W, int C, int split, int heads, int dtype)
+{
+    return rcx::ls_la3_tiled_applicable(B, H, W, C, split, heads, dtype) ? 1 : 0;
+}
+
+size_t rcx_ls_recattn_tiled_workspace_bytes(int B, int H, int W, int C, int split, int heads, int dtype)
+{
+    return rcx::ls_recattn_tiled_workspace_bytes(B, H, W, C, split, heads, dtype);
+}
+
+size_t rcx_ls_la3_tiled_workspace_bytes(int B, int H, int W, int C, int split, int heads, int dtype)
+{
+    return rcx::ls_la3_tiled_workspace_bytes(B, H, W, C, split, heads, dtype);
+}
+
+namespace {
+// the argument checks the two tiled token-half entries share, in the order of rcx_ls_recattn_fwd / rcx_ls_la3_fwd, then the workspace
+int check_ls_tiled(const char* fn, std::initializer_list<const void*> ps, const void* x, const void* r, const void* t, const void* workspace,
+                   size_t workspace_bytes, size_t need, bool supported, int B, int H, int W, int C, int split, int heads, int dtype)
+{
+    for (const void* p : ps)
+        if (!p) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || split <= 0 || heads <= 0)
+        return fail(RCX_ERR_BAD_ARG, "non-positive extent B=%d H=%d W=%d C=%d split=%d heads=%d", B, H, W, C, split, heads);
+    if (!known_dtype(dtype)) return fail(RCX_ERR_BAD_ARG, "unknown dtype %d", dtype);
+    if (r == x || t == x || r == t) return fail(RCX_ERR_BAD_ARG, "%s: r and t must alias neither x nor each other", fn);
+    if (workspace && (workspace == x || workspace == r || workspace == t)) return fail(RCX_ERR_BAD_ARG, "%s: the workspace must alias none of x, r and t", fn);
+    if (any_misaligned(ps) || ((size_t)workspace & 15)) return fail(RCX_ERR_BAD_ARG, "%s: every tensor and the workspace must be 16-byte aligned", fn);
+    if (!supported)
+        return fail(RCX_ERR_UNSUPPORTED, "%s: %d x %d plane, C=%d, split=%d, %d heads: C and split multiples of 4; RecAttn2d one head, LinearAttention3 split a "
+                                         "multiple of 2 heads with heads of v in fours; a chunk's LDS within 160 KB", fn, H, W, C, split, heads);
+    if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
+    return 0;
+}
+}  // namespace
+
+int rcx_ls_recattn_tiled_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* w_down_kkc, const float* b_down,
+                             const float* wqT, const float* bq, const float* wkT, const float* bk, const float* w_pe_kkc, const float* b_pe,
+                             const float* w_conv_kkc, const float* b_conv, void* workspace, size_t workspace_bytes, int B, int H, int W, int C,
+                             int split, int heads, int dtype, void* stream)
+{
+    if (int rc = check_ls_tiled("rcx_ls_recattn_tiled_fwd", {x, r, t, w_rep, b_rep, w_down_kkc, b_down, wqT, bq, wkT, bk, w_pe_kkc, b_pe, w_conv_kkc, b_conv},
+                                x, r, t, workspace, workspace_bytes, rcx::ls_recattn_tiled_workspace_bytes(B, H, W, C, split, heads, dtype),
+                                rcx::ls_recattn_tiled_applicable(B, H, W, C, split, heads, dtype), B, H, W, C, split, heads, dtype))
+        return rc;
+    hipError_t e = rcx::ls_recattn_tiled_fwd(x, r, t, w_rep, b_rep, w_down_kkc, b_down, wqT, bq, wkT, bk, w_pe_kkc, b_pe, w_conv_kkc, b_conv, workspace,
+                                             B, H, W, C, split, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rcx_ls_recattn_tiled_fwd");
+}
+
+int rcx_ls_la3_tiled_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* wqT, const float* bq,
+                         const float* wkT, const float* bk, const float* w_pe_kkc, const float* b_pe, void* workspace, size_t workspace_bytes,
+                         int B, int H, int W, int C, int split, int heads, int dtype, void* stream)
+{
+    if (int rc = check_ls_tiled("rcx_ls_la3_tiled_fwd", {x, r, t, w_rep, b_rep, wqT, bq, wkT, bk, w_pe_kkc, b_pe}, x, r, t, workspace, workspace_bytes,
+                                rcx::ls_la3_tiled_workspace_bytes(B, H, W, C, split, heads, dtype),
+                                rcx::ls_la3_tiled_applicable(B, H, W, C, split, heads, dtype), B, H, W, C, split, heads, dtype))
+        return rc;
+    hipError_t e = rcx::ls_la3_tiled_fwd(x, r, t, w_rep, b_rep, wqT, bq, wkT, bk, w_pe_kkc, b_pe, workspace, B, H, W, C, split, heads, dtype,
+                                         (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rcx_ls_la3_tiled_fwd");
+}
+
 int rcx_linear_attention_bwd(const void* qpre, const void* kpre, const void* v, const void* gout, void* gq, void* gk, void* gv,
                              int B, int n, int C, int heads, int dtype, void* stream)
 {

@@ -194,6 +194,17 @@ hipError_t ls_recattn_fwd(const void* x, void* r, void* t, const float* w_rep, c
 hipError_t ls_la3_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* wqT, const float* bq,
                       const float* wkT, const float* bk, const float* w_pe, const float* b_pe, int B, int H, int W, int C, int split, int heads,
                       int dtype, hipStream_t s);
+// rcx_lstile.hip: the same token halves cut into token chunks for any plane size; the float32 workspace carries the image-wide sums
+bool ls_recattn_tiled_applicable(int B, int H, int W, int C, int split, int heads, int dtype);
+bool ls_la3_tiled_applicable(int B, int H, int W, int C, int split, int heads, int dtype);
+size_t ls_recattn_tiled_workspace_bytes(int B, int H, int W, int C, int split, int heads, int dtype);
+size_t ls_la3_tiled_workspace_bytes(int B, int H, int W, int C, int split, int heads, int dtype);
+hipError_t ls_recattn_tiled_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* w_dn, const float* b_dn,
+                                const float* wqT, const float* bq, const float* wkT, const float* bk, const float* w_pe, const float* b_pe,
+                                const float* w_cv, const float* b_cv, void* workspace, int B, int H, int W, int C, int split, int dtype, hipStream_t s);
+hipError_t ls_la3_tiled_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* wqT, const float* bq,
+                            const float* wkT, const float* bk, const float* w_pe, const float* b_pe, void* workspace, int B, int H, int W, int C,
+                            int split, int heads, int dtype, hipStream_t s);
 hipError_t recattn_qkcore(const float* d, const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe, float* out, void* workspace,
                           int B, int Hp, int Wp, int C, int heads, hipStream_t s);
 

@@ -5,8 +5,9 @@ mixer is RecAttn2d at stages 0-2 (:115-127) and LinearAttention3 at stage 3 (:89
 checkpoints load with ``strict=True`` and ``models.replace_batchnorm`` gives the keys of its ``RecNext.fuse()``.
 
 The token half ``x -> (r, t)`` of every block is ONE HIP entry (two launches: ``ops.ls_recattn`` / ``ops.ls_la3``), BatchNorms folded into float32
-packs whether or not ``replace_batchnorm`` has run; where the support query says no and the head is at most 64 wide, the block falls back to the
-HIP depthwise conv and the library's ``RecAttn2d`` on a contiguous slice.  A forward in training mode or one that needs a gradient takes the training
+packs whether or not ``replace_batchnorm`` has run; where that entry's support query says no (planes above 224 x 224's), the tiled entry
+(``ops.ls_recattn_tiled`` / ``ops.ls_la3_tiled``: the same function on any H x W, three or four launches) takes the block, and behind it the HIP
+depthwise conv and the library's ``RecAttn2d`` on a contiguous slice remain for heads of at most 64 channels.  A forward in training mode or one that needs a gradient takes the training
 form (``_token_half_train``): BatchNorms on batch statistics under autograd, nothing folded, the depthwise convs and the attention cores with HIP
 forward and backward kernels -- ``RecAttn2d``'s own training branch at stages 0-2 (the 96-wide heads of S / B's stage 2 on the wide core,
 ``rcx_linear_attention_wide_*``) and ``LinearAttention3.forward`` at stage 3 (q / k of s/2 and v of s channels: the wide core) -- and library GEMMs
@@ -229,8 +230,9 @@ class MetaNeXtBlock(nn.Module):
         return self._pack
 
     def token_half(self, x):
-        """(r, t) on HIP: one entry (two launches) where the support query says yes, else the HIP depthwise conv + the library's RecAttn2d on a
-        contiguous slice (heads of at most 64 channels); raises otherwise.  In training mode or when a gradient is needed: _token_half_train."""
+        """(r, t) on HIP: the one-workgroup entry (two launches) where its support query says yes, else the tiled entry (any plane size), else the
+        HIP depthwise conv + the library's RecAttn2d on a contiguous slice (heads of at most 64 channels; no registered model reaches it); raises
+        otherwise.  In training mode or when a gradient is needed: _token_half_train."""
         attn = self.token_mixer.attn
         s = self.token_mixer.split_idx
         b, c, h, w = x.shape
@@ -241,10 +243,14 @@ class MetaNeXtBlock(nn.Module):
         if isinstance(attn, LinearAttention3):
             if ops.ls_la3_supported(b, h, w, c, s, attn.num_heads, x.dtype):
                 return ops.ls_la3(x, *self.packed_params(), s, attn.num_heads)
+            if ops.ls_la3_tiled_supported(b, h, w, c, s, attn.num_heads, x.dtype):
+                return ops.ls_la3_tiled(x, *self.packed_params(), s, attn.num_heads)
             raise NotImplementedError(f"RecNeXt-T / S / B LinearAttention3: no kernel for a {h} x {w} plane of {c} channels (slice {s}, {attn.num_heads} heads, {x.dtype})")
         heads = attn.down[1].num_heads
         if ops.ls_recattn_supported(b, h, w, c, s, heads, x.dtype):
             return ops.ls_recattn(x, *self.packed_params(), s, heads)
+        if ops.ls_recattn_tiled_supported(b, h, w, c, s, heads, x.dtype):
+            return ops.ls_recattn_tiled(x, *self.packed_params(), s, heads)
         if s % heads == 0 and head_dim_supported(s // heads) and x.dtype in ops._DT:
             wr, br = self.packed_params()[:2]
             r = ops.dwconv2d(x, wr, br, k=3, stride=1)
@@ -360,18 +366,21 @@ def create_model(name, distillation=False, token_mixer=None, **overrides):
 
 
 def mixer_shapes(name, resolution=224):
-    """[(stage, H, W, C, split, heads, kind, blocks)] of every block's token half in one forward (kind 'recattn' | 'la3'; heads as the entries take them)."""
+    """[(stage, H, W, C, split, heads, kind, blocks)] of every block's token half in one forward (kind 'recattn' | 'la3'; heads as the entries take them).
+    `resolution`: the input's side, or its (H, W)."""
     cfg = dict(_COMMON, **LS_CONFIGS[name])
-    side = resolution
+    sides = [resolution, resolution] if isinstance(resolution, int) else [int(v) for v in resolution]
+    if len(sides) != 2:
+        raise ValueError("resolution must be an int or an (H, W) pair")
     for _ in range(3):
-        side = (side + 1) // 2                                  # the stem: three 3x3 stride-2 convs
+        sides = [(v + 1) // 2 for v in sides]                   # the stem: three 3x3 stride-2 convs
     out = []
     for i, (c, d) in enumerate(zip(cfg["embed_dim"], cfg["depth"])):
         if i:
-            side = (side + 1) // 2                              # Downsample: 5x5 stride 2, padding 2
+            sides = [(v + 1) // 2 for v in sides]               # Downsample: 5x5 stride 2, padding 2
         if d:
             split = c // cfg["split_rates"][i]
             kind = "la3" if i >= 3 else "recattn"
             heads = cfg["num_heads"][i] // 2 if kind == "la3" else cfg["num_heads"][i]
-            out.append((i, side, side, c, split, heads, kind, d))
+            out.append((i, sides[0], sides[1], c, split, heads, kind, d))
     return out

@@ -585,6 +585,74 @@ def ls_la3(x, w_rep, b_rep, wqT, bq, wkT, bk, w_pe_kkc, b_pe, split, heads):
     return r, t
 
 
+def ls_recattn_tiled_supported(b, h, w, c, split, heads, dtype):
+    """Whether rcx_ls_recattn_tiled_fwd (ls_recattn's function on any plane size, the image cut into token chunks) has a kernel for the shape."""
+    return dtype in _DT and _lib.load().rcx_ls_recattn_tiled_supported(b, h, w, c, split, heads, _DT[dtype]) > 0
+
+
+def ls_la3_tiled_supported(b, h, w, c, split, heads, dtype):
+    """Whether rcx_ls_la3_tiled_fwd (ls_la3's function on any plane size) has a kernel for the shape."""
+    return dtype in _DT and _lib.load().rcx_ls_la3_tiled_supported(b, h, w, c, split, heads, _DT[dtype]) > 0
+
+
+def _ls_workspace(x, nbytes, workspace):
+    """The float32 workspace of a tiled token half: the caller's (checked) or one from torch's allocator on the current stream."""
+    if workspace is None:
+        return torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    if not torch.is_tensor(workspace) or workspace.dtype != torch.float32 or workspace.device != x.device or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous float32 tensor on x's device")
+    if workspace.numel() * 4 < nbytes:
+        raise ValueError(f"workspace of {workspace.numel() * 4} bytes, {nbytes} needed")
+    return workspace
+
+
+def ls_recattn_tiled(x, w_rep, b_rep, w_down_kkc, b_down, wqT, bq, wkT, bk, w_pe_kkc, b_pe, w_conv_kkc, b_conv, split, heads=1, workspace=None):
+    """ls_recattn's function and arguments for any H x W (rcx_ls_recattn_tiled_fwd: four launches, the image-wide sums through a float32 workspace
+    from torch's allocator unless `workspace` is given).  Deterministic; a batch and its shards give the same rows bit for bit."""
+    c = x.shape[1] if torch.is_tensor(x) and x.dim() == 4 else 0
+    _check_ls_args("ls_recattn_tiled", x, split, [("w_rep", w_rep, 9 * c), ("b_rep", b_rep, c), ("w_down_kkc", w_down_kkc, 25 * split), ("b_down", b_down, split),
+                                                  ("wqT", wqT, split * (split // 2)), ("bq", bq, split), ("wkT", wkT, split * (split // 2)), ("bk", bk, split),
+                                                  ("w_pe_kkc", w_pe_kkc, 9 * split), ("b_pe", b_pe, split), ("w_conv_kkc", w_conv_kkc, 25 * split), ("b_conv", b_conv, split)])
+    b, _, h, w = x.shape
+    if not ls_recattn_tiled_supported(b, h, w, c, split, heads, x.dtype):
+        raise ValueError(f"ls_recattn_tiled: no kernel for a {h} x {w} plane, C={c}, split={split}, {heads} heads, {x.dtype} (ls_recattn_tiled_supported)")
+    lib = _lib.load()
+    nbytes = lib.rcx_ls_recattn_tiled_workspace_bytes(b, h, w, c, split, heads, _dt(x))
+    x = _nhwc(x, "x")
+    with _on(x.device):
+        ws = _ls_workspace(x, nbytes, workspace)
+        r = torch.empty_like(x, memory_format=torch.channels_last)
+        t = torch.empty_like(x, memory_format=torch.channels_last)
+        rc = lib.rcx_ls_recattn_tiled_fwd(x.data_ptr(), r.data_ptr(), t.data_ptr(), w_rep.data_ptr(), b_rep.data_ptr(), w_down_kkc.data_ptr(), b_down.data_ptr(),
+                                          wqT.data_ptr(), bq.data_ptr(), wkT.data_ptr(), bk.data_ptr(), w_pe_kkc.data_ptr(), b_pe.data_ptr(),
+                                          w_conv_kkc.data_ptr(), b_conv.data_ptr(), ws.data_ptr(), ws.numel() * 4, b, h, w, c, split, heads, _dt(x),
+                                          _stream(x.device))
+    _lib.check(rc, "rcx_ls_recattn_tiled_fwd")
+    return r, t
+
+
+def ls_la3_tiled(x, w_rep, b_rep, wqT, bq, wkT, bk, w_pe_kkc, b_pe, split, heads, workspace=None):
+    """ls_la3's function and arguments for any H x W (rcx_ls_la3_tiled_fwd: three launches; the workspace as ls_recattn_tiled)."""
+    c = x.shape[1] if torch.is_tensor(x) and x.dim() == 4 else 0
+    _check_ls_args("ls_la3_tiled", x, split, [("w_rep", w_rep, 9 * c), ("b_rep", b_rep, c), ("wqT", wqT, split * (split // 2)), ("bq", bq, split // 2),
+                                              ("wkT", wkT, split * (split // 2)), ("bk", bk, split // 2), ("w_pe_kkc", w_pe_kkc, 9 * split), ("b_pe", b_pe, split)])
+    b, _, h, w = x.shape
+    if not ls_la3_tiled_supported(b, h, w, c, split, heads, x.dtype):
+        raise ValueError(f"ls_la3_tiled: no kernel for a {h} x {w} plane, C={c}, split={split}, {heads} heads, {x.dtype} (ls_la3_tiled_supported)")
+    lib = _lib.load()
+    nbytes = lib.rcx_ls_la3_tiled_workspace_bytes(b, h, w, c, split, heads, _dt(x))
+    x = _nhwc(x, "x")
+    with _on(x.device):
+        ws = _ls_workspace(x, nbytes, workspace)
+        r = torch.empty_like(x, memory_format=torch.channels_last)
+        t = torch.empty_like(x, memory_format=torch.channels_last)
+        rc = lib.rcx_ls_la3_tiled_fwd(x.data_ptr(), r.data_ptr(), t.data_ptr(), w_rep.data_ptr(), b_rep.data_ptr(), wqT.data_ptr(), bq.data_ptr(),
+                                      wkT.data_ptr(), bk.data_ptr(), w_pe_kkc.data_ptr(), b_pe.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                      b, h, w, c, split, heads, _dt(x), _stream(x.device))
+    _lib.check(rc, "rcx_ls_la3_tiled_fwd")
+    return r, t
+
+
 def _mlp_acc_unit(i, h):
     """Hidden unit (within a 32-unit tile) that accumulator register i of lane half h holds after the first product (rcx_mlp.hip acc_row)."""
     return (i & 3) + 8 * (i >> 2) + 4 * h

@@ -60,6 +60,10 @@ for (path, r), name in zip(rows, names):
         gated = True                                       # the input adjoint: every instantiation, float16 included, is default dispatch
     elif re.search(r"k_recattn_(short|kv|out)_w(<|I)", short):
         gated = True                                       # wide heads (36 .. 64 channels): every instantiation, float16 x included (mangled when undemangled)
+    elif re.search(r"\dk_lt_(rep|kv|out|conv)I", r["name"]):
+        gated = True                                       # the tiled T / S / B token half: every instantiation (by the mangled name: the
+        m = re.search(r"k_lt_\w+<[^(]*>", name)                        # kernels of an anonymous namespace lose theirs to the cut above)
+        short = short or (m.group(0) if m else name)
     elif re.match(r"mlp::k_channel_mlp(_pair|_stream)?<", short):
         # the channel mixer: every instantiation but the 320-channel stream kernel (ZPF off), whose 15 spilled registers sit outside its hidden-tile loop
         gated = not (short.startswith("mlp::k_channel_mlp_stream<") and short.endswith(", false>"))
