@@ -19,6 +19,7 @@
 #include "rcx_common.h"
 #include "rcx_launch.h"
 #include "rcx_gelu.h"
+#include <type_traits>
 
 namespace rcx {
 namespace mlp {
@@ -505,6 +506,203 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// C = 512, H = 1024 (the 7 x 7 stage of M3 / A3): the forms above do not stretch to it.  A wave that owned 32 tokens and all 512 outputs would need 256 accumulator
+// registers next to 128 for its z fragments, and at 49 tokens an image a workgroup must pull all 2 MB of weights whatever its size: next to the matrix cores the
+// weight delivery is the limit, not HBM.  So the work is split by WEIGHT FRAGMENT, not by token: a workgroup of 8 waves (two per SIMD) owns 64 tokens = two
+// 32-token tiles, and every fragment of the pack is read by exactly one of its waves, straight from global memory (the L2) into registers -- a whole-wave
+// contiguous kilobyte, requested RD fragments ahead of its use -- and feeds TWO products, one per token tile.  LDS carries only B operands:
+//   z, staged once as the first product's B fragments (tile tt, k-step ks: 1 KB lane-linear; 64 KB);
+//   the hidden layer, SH = 8 hidden tiles (256 units) per step, in a double-buffered exchange of 2 x 32 KB.
+// Step s of HT / SH = 4:
+//   phase A  wave w forms D1 of hidden tile SH s + w for both token tiles (2 KS1 = 64 products, A = W1 fragments (ht, ks)), adds b1, takes 2 gelu(.) and writes
+//            the bf16 result -- as in hidden_tile_ring already the second product's B operands, (tt, q) 1 KB each -- lane-linearly into exchange buffer s & 1;
+//   one barrier (raw s_barrier behind an LDS-only wait: __syncthreads() would drain the fragment requests in flight);
+//   phase B  wave w owns output tiles 2 w, 2 w + 1 and adds the step's 8 hidden tiles to d2[2][2] (64 registers): 64 products, A = W2 fragments (ht, 2 w + c2, q).
+// Buffer s & 1 is rewritten in phase A of step s + 2, which every wave enters only through the barrier of step s + 1, i.e. after every wave's phase B of step s.
+// The arithmetic per element is hidden_tile_ring's (float32 sums in the same k order, the hidden layer rounded once, the output once).
+// Epilogue: + b2 -> a float32 image of 32 tokens x 64 channels per wave (aliased onto the z fragments and exchange buffer 0, both dead after the last barrier)
+// -> rows: + x, 16-byte stores, 128 contiguous bytes per token.  Tokens past M: buffer descriptors (reads 0, stores dropped).
+template <int KS1, int HT, int CT, int RD>
+__global__ void __launch_bounds__(512, 2)
+k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf16_t* __restrict__ y, const u32x4q* __restrict__ wfrag, const float* __restrict__ bias, int M)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    constexpr int NW = 8, NT = 64 * NW, SH = 8, NST = HT / SH, NCH = KS1 + 2 * CT, NF = KS1 + 4 * SH;      // NF: fragments a wave consumes per step
+    static_assert(CT == 2 * NW && HT % SH == 0 && SH == NW && NF % RD == 0 && KS1 % RD == 0 && KS1 % 8 == 0, "a hidden tile (phase A) and two output tiles (phase B) per wave");
+    constexpr int RB = 32 * KS1, OP = 256 + 16, IMG = 32 * OP;                   // bytes per token row; the output image's row pitch (16 bytes of padding: banks)
+    constexpr int ZBYTES = 2 * KS1 * 1024, XBYTES = SH * 4 * 1024;
+    static_assert(NW * IMG <= ZBYTES + XBYTES, "the output images alias the z fragments and exchange buffer 0");
+    u32x4q* const Lz = reinterpret_cast<u32x4q*>(lds_raw);                      // [tt][ks][lane]
+    u32x4q* const Lx = reinterpret_cast<u32x4q*>(lds_raw + ZBYTES);             // [2][hidden tile of the step][tt][q][lane]
+    float* const Lb1 = reinterpret_cast<float*>(lds_raw + ZBYTES + 2 * XBYTES);
+    const float* const Lb2 = Lb1 + 32 * HT;
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // The wave's fragment stream: step s, i < KS1: W1 (SH s + w, ks = i); then for hidden tile hl = (i - KS1) / 4 of the step the four W2 fragments in use order
+    // j = (i - KS1) % 4: output tile c2 = j & 1, k half q = j >> 1 (alternating accumulators).
+    auto frag = [&](int s, int i) -> u32x4q {
+        const int ht = SH * s + (i < KS1 ? wv : (i - KS1) >> 2);
+        const int f = i < KS1 ? i : KS1 + 4 * wv + 2 * ((i - KS1) & 1) + (((i - KS1) >> 1) & 1);
+        return wfrag[((size_t)ht * NCH + f) * 64 + lane];
+    };
+    u32x4q ring[RD];
+#pragma unroll
+    for (int i = 0; i < RD; ++i) ring[i] = frag(0, i);
+    const unsigned nbytes = (unsigned)M * (unsigned)RB;                          // < 2^31 (checked by the launcher)
+    const __amdgpu_buffer_rsrc_t zsrc = __builtin_amdgcn_make_buffer_rsrc((void*)z, 0, nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xres, 0, nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, nbytes, 0x00020000);
+    const unsigned base = blockIdx.x * 64u * RB;
+    {
+        // z -> B fragments: wave w takes tokens 8 w .. 8 w + 7; request j = the 16-byte pieces 8 j + lane / 8 of the rows of tokens lane % 8 (128 contiguous bytes per
+        // row and request; in LDS the 8 tokens of one piece are 128 contiguous bytes of fragment (tt, ks = piece / 2), lane half piece % 2: conflict-free)
+        const unsigned go = base + (8u * wv + (lane & 7)) * RB + 16u * (lane >> 3);
+        u32x4q zq[KS1 / 4];
+#pragma unroll
+        for (int j = 0; j < KS1 / 4; ++j) zq[j] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(zsrc, (int)(go + 128u * j), 0, 0));
+        for (int i = threadIdx.x; i < 32 * (HT + CT); i += NT) Lb1[i] = bias[i];
+        u32x4q* const dst = Lz + ((wv >> 2) * KS1 + (lane >> 4)) * 64 + ((lane >> 3) & 1) * 32 + 8 * (wv & 3) + (lane & 7);
+#pragma unroll
+        for (int j = 0; j < KS1 / 4; ++j) dst[4 * j * 64] = zq[j];
+    }
+    __syncthreads();
+    if (!(__builtin_popcount(wv) & 1)) __builtin_amdgcn_s_setprio(1);            // one wave of each SIMD's pair takes the matrix pipe first (k_channel_mlp_pair)
+    constexpr int LGKM0 = 0xC07F;                                                // s_waitcnt lgkmcnt(0) alone: vmcnt 63, expcnt 7
+    f32x16 d2[2][2];
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) d2[c2][tt][i] = 0.f;
+    // output request j of token tile tt: token 8 j + lane / 8, bytes 128 w + 16 (lane % 8) of its row
+    const unsigned ot = lane >> 3, ob = 16u * (lane & 7);
+    u32x4q xq[2][4];
+    auto step = [&](int s, auto last_c) {
+        constexpr bool LAST = decltype(last_c)::value;
+        const int sn = LAST ? 0 : s + 1;
+        // ---- phase A
+        f32x16 d1[2];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) d1[tt][i] = 0.f;
+        constexpr int BD = 2;                                                   // k-steps the z fragments are read ahead of their products
+        u32x4q zb[BD][2];
+#pragma unroll
+        for (int k = 0; k < BD; ++k)
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) zb[k][tt] = Lz[(tt * KS1 + k) * 64 + lane];
+#pragma unroll
+        for (int ks = 0; ks < KS1; ++ks) {
+            const bf16x8 a = __builtin_bit_cast(bf16x8, ring[ks % RD]);
+            ring[ks % RD] = frag(s, ks + RD);
+            const bf16x8 b0 = __builtin_bit_cast(bf16x8, zb[ks % BD][0]), b1 = __builtin_bit_cast(bf16x8, zb[ks % BD][1]);
+            if (ks + BD < KS1) {
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt) zb[ks % BD][tt] = Lz[(tt * KS1 + ks + BD) * 64 + lane];
+            }
+            d1[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b0, d1[0], 0, 0, 0);
+            d1[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b1, d1[1], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);                                  // the request stays RD fragments ahead: left alone, the scheduler sinks each one to its use
+        }
+        const float* const b1t = Lb1 + 32 * (SH * s + wv);
+        u32x4q* const Lw = Lx + (size_t)(s & 1) * (XBYTES / 16) + wv * 4 * 64 + lane;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            gelu_f32x2 gv[8];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4q bb = *reinterpret_cast<const f32x4q*>(b1t + 8 * g + 4 * h);
+                gv[2 * g] = gelu_f32x2{d1[tt][4 * g] + bb.x, d1[tt][4 * g + 1] + bb.y};
+                gv[2 * g + 1] = gelu_f32x2{d1[tt][4 * g + 2] + bb.z, d1[tt][4 * g + 3] + bb.w};
+            }
+            {
+                gelu_f32x2 ga[4] = {gv[0], gv[1], gv[2], gv[3]}, gb[4] = {gv[4], gv[5], gv[6], gv[7]};
+                gelu2x_batch<4>(ga);
+                gelu2x_batch<4>(gb);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { gv[i] = ga[i]; gv[4 + i] = gb[i]; }
+            }
+            bf16x8 hb[2];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                hb[g >> 1][4 * (g & 1) + 0] = (__bf16)gv[2 * g].x; hb[g >> 1][4 * (g & 1) + 1] = (__bf16)gv[2 * g].y;
+                hb[g >> 1][4 * (g & 1) + 2] = (__bf16)gv[2 * g + 1].x; hb[g >> 1][4 * (g & 1) + 3] = (__bf16)gv[2 * g + 1].y;
+            }
+            Lw[(2 * tt) * 64] = __builtin_bit_cast(u32x4q, hb[0]);
+            Lw[(2 * tt + 1) * 64] = __builtin_bit_cast(u32x4q, hb[1]);
+        }
+        __builtin_amdgcn_s_waitcnt(LGKM0);
+        __builtin_amdgcn_s_barrier();
+        // ---- phase B
+        if constexpr (LAST) {                                                   // the residual: in flight during the last products (the fragment ring has nothing left to fetch)
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    xq[tt][j] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(xsrc, (int)(base + (32u * tt + 8u * j + ot) * RB + 128u * wv + ob), 0, 0));
+        }
+        const u32x4q* const Lr = Lx + (size_t)(s & 1) * (XBYTES / 16) + lane;
+        u32x4q hq[2][2][2];                                                      // [hl parity][tt][q]
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) hq[0][tt][q] = Lr[(2 * tt + q) * 64];
+#pragma unroll
+        for (int hl = 0; hl < SH; ++hl) {
+            if (hl + 1 < SH) {
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) hq[(hl + 1) & 1][tt][q] = Lr[((hl + 1) * 4 + 2 * tt + q) * 64];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int i = KS1 + 4 * hl + j, c2 = j & 1, q = j >> 1;
+                const bf16x8 a = __builtin_bit_cast(bf16x8, ring[i % RD]);
+                if (i + RD < NF) ring[i % RD] = frag(s, i + RD);
+                else if (!LAST) ring[i % RD] = frag(sn, i + RD - NF);
+                d2[c2][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, hq[hl & 1][0][q]), d2[c2][0], 0, 0, 0);
+                d2[c2][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, hq[hl & 1][1][q]), d2[c2][1], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+#pragma unroll 1
+    for (int s = 0; s < NST - 1; ++s) step(s, std::false_type{});
+    step(NST - 1, std::true_type{});
+    // ---- epilogue (every wave has passed the last barrier: the z fragments and exchange buffer 0 are dead)
+    unsigned char* const Lt = lds_raw + (size_t)wv * IMG;
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+#pragma unroll
+        for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + 32 * (2 * wv + c2) + 8 * g + 4 * h);
+                *reinterpret_cast<f32x4q*>(Lt + r * OP + 4 * (32 * c2 + 8 * g + 4 * h)) =
+                    f32x4q{d2[c2][tt][4 * g] + bb.x, d2[c2][tt][4 * g + 1] + bb.y, d2[c2][tt][4 * g + 2] + bb.z, d2[c2][tt][4 * g + 3] + bb.w};
+            }
+        wave_sync();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned char* src = Lt + (8 * j + ot) * OP + 2 * ob;
+            const f32x4q lo = *reinterpret_cast<const f32x4q*>(src), hi = *reinterpret_cast<const f32x4q*>(src + 16);
+            const u32x4q xv = xq[tt][j];
+            bf16x8 o;
+            o[0] = (__bf16)(lo.x + __uint_as_float(xv.x << 16)); o[1] = (__bf16)(lo.y + __uint_as_float(xv.x & 0xffff0000u));
+            o[2] = (__bf16)(lo.z + __uint_as_float(xv.y << 16)); o[3] = (__bf16)(lo.w + __uint_as_float(xv.y & 0xffff0000u));
+            o[4] = (__bf16)(hi.x + __uint_as_float(xv.z << 16)); o[5] = (__bf16)(hi.y + __uint_as_float(xv.z & 0xffff0000u));
+            o[6] = (__bf16)(hi.z + __uint_as_float(xv.w << 16)); o[7] = (__bf16)(hi.w + __uint_as_float(xv.w & 0xffff0000u));
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, o), ysrc, (int)(base + (32u * tt + 8u * j + ot) * RB + 128u * wv + ob), 0, 0);
+        }
+        wave_sync();
+    }
+}
+
 }  // namespace mlp
 
 // C % 8 == 0, H % 32 == 0 (the host pads the hidden layer with zero units), the weights fit the CU's LDS, M C 2 < 2^31
@@ -516,11 +714,18 @@ static bool mlp_shape(int C, int H, int* ks1, int* ht, int* ct)
     return true;
 }
 
+// C = 512, H = 1024 is offered from this token count upward.  Measured crossover against the four library launches (tools/bench_mlp.py, profiles/r11_channel_mlp512.txt):
+// none in the sweep -- M = 1 568 / 3 136 / 6 272 / 12 544: 29.3 / 29.8 / 31.3 / 36.5 us fused against 53.1 / 52.7 / 53.7 / 62.6 us, so it lies below 1 024, the token
+// count tests/test_mlp_gpu.py pins as unsupported; hence 2 048, the smallest sweep point above it with margin.
+static constexpr int MLP512_MIN_TOKENS = 2048;
+
 bool channel_mlp_applicable(int M, int C, int H, int dtype)
 {
     int ks1, ht, ct;
     if (dtype != 1 || M <= 0 || !mlp_shape(C, H, &ks1, &ht, &ct)) return false;
     if ((unsigned long long)M * C * 2 >= (1ull << 31)) return false;
+    // the 7 x 7 stage: a workgroup streams all 2 MB of weights for its 64 tokens, so a few workgroups on a mostly idle chip lose to the library's N-split GEMMs
+    if (C == 512 && ht == 32) return M >= MLP512_MIN_TOKENS;
     if (C == 256 && ht == 16) return true;
     if (C == 192 && ht == 12) return true;
     if ((C == 160 && ht == 10) || (C == 320 && ht == 20)) return true;
@@ -586,6 +791,19 @@ static hipError_t launch_mlp_pair256(const void* z, const void* x, void* y, cons
     return hipGetLastError();
 }
 
+// C = 512, H = 1024: 8 waves (two per SIMD), 64 tokens a workgroup, the weights straight from global memory
+static hipError_t launch_mlp_wide512(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, hipStream_t s)
+{
+    constexpr int KS1 = 32, HT = 32, CT = 16;
+    constexpr size_t lds = (size_t)2 * KS1 * 1024 + (size_t)2 * 8 * 4 * 1024 + sizeof(float) * 32 * (HT + CT);
+    static_assert(lds <= 160 * 1024, "the z fragments, the exchange buffers and the biases must fit the LDS");
+    if (C != 16 * KS1) return hipErrorInvalidConfiguration;
+    auto kfn = mlp::k_channel_mlp_wide<KS1, HT, CT, 8>;
+    RCX_SET_LDS_ONCE(kfn, lds);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)((M + 63) / 64)), dim3(512), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M);
+    return hipGetLastError();
+}
+
 hipError_t channel_mlp(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, int H, int dtype, hipStream_t s)
 {
     int ks1, ht, ct;
@@ -600,6 +818,7 @@ hipError_t channel_mlp(const void* z, const void* x, void* y, const void* wfrag,
             cus[dev].store(ncu, std::memory_order_relaxed);
         }
     }
+    if (C == 512 && ht == 32) return launch_mlp_wide512(z, x, y, wfrag, bias, M, C, s);                                // M3 / A3 stage 3
     if (C == 256 && ht == 16) return launch_mlp_pair256(z, x, y, wfrag, bias, M, C, ncu, s);                         // M3 / A3 stage 2
     if (C == 192 && ht == 12) return launch_mlp_stream<12, 12, 6, 4>(z, x, y, wfrag, bias, M, C, ncu, s);           // M1 stage 2
     if (C == 160 && ht == 10) return launch_mlp_stream<10, 10, 6, 4>(z, x, y, wfrag, bias, M, C, ncu, s);           // M5 / A5 stage 1
