@@ -12,7 +12,7 @@
 //   D2 += W2[:][32 ht ..] h                                      ... the second product, with W2's columns stored in the order the registers imply
 //   y   = D2 + b2 + x                                            8-byte loads / stores of four channels per lane (token on the lane)
 // The weights are ready-made fragments (one conflict-free 16-byte LDS read per lane and product), packed once on the host (ops.pack_channel_mlp), hidden tile by
-// hidden tile: resident in LDS for C <= 128 (k_channel_mlp), streamed through a two-slot LDS ring for C = 128 .. 320 (k_channel_mlp_stream, further down; C = 256: k_channel_mlp_pair, two waves per SIMD).  Global
+// hidden tile: resident in LDS for C <= 128 (k_channel_mlp; C = 128: k_channel_mlp_res128, free-running waves), streamed through a two-slot LDS ring for C = 160 .. 320 (k_channel_mlp_stream, further down; C = 256: k_channel_mlp_pair, two waves per SIMD).  Global
 // accesses are whole-wave contiguous kilobytes, transposed to / from the token-on-lane layouts in per-wave LDS images (measurements: profiles/r05_channel_mlp.txt).
 // GELU is the exact form 0.5 v (1 + erf(v / sqrt 2)) with erf as an odd degree-15 polynomial of the argument clamped to +-2.8: |error| < 7.7e-5 in erf, i.e. 4e-5 |v|
 // in gelu -- a fiftieth of a bf16 ulp; the library's erff would be most of this kernel's vector work.
@@ -508,6 +508,119 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
 
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
+// C = 128, H = 256 (the 28 x 28 stage of M3 / A3 and its Downsample mixer): the whole pack is 128 KB and stays RESIDENT in LDS next to per-wave images of a few
+// KB -- k_channel_mlp_pair's column parts: z staged in four parts of 32 channels, the output in pieces of OC channels of TG = 512 / OC tokens (a float32 image of
+// TG rows; the lanes of the other tokens sit the write out).  With no ring there is nothing for a workgroup's waves to meet at: after the prologue (pack -> LDS by
+// LDS-DMA, the biases, ONE barrier) each of the 8 waves (two per SIMD) walks its own 32-token tiles, tile t on wave slot t mod (8 gridDim.x), slots wave-major so
+// that a last partial round spreads over the CUs a wave each.  The next tile's z is in flight during the current tile; the residual is requested after the
+// products (its registers were the z fragments').  The arithmetic is hidden_tile_ring's on the same fragments in the same order, so y is bit-identical to
+// k_channel_mlp_stream's.  PRIO: a raised static priority on one wave of each SIMD's pair, as in k_channel_mlp_pair.
+template <int KS1, int HT, int CT, int OC, bool PRIO>
+__global__ void __launch_bounds__(512, 2)
+k_channel_mlp_res128(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf16_t* __restrict__ y, const u32x4q* __restrict__ wfrag, const float* __restrict__ bias,
+                     int M, int ntiles)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    constexpr int NW = 8, NT = 64 * NW, NCH = KS1 + 2 * CT, NF = HT * NCH, PER = NF * 64 / NT;   // PER: 1-KB DMA pieces of the pack per wave
+    static_assert(NF * 64 % NT == 0, "whole pieces per wave");
+    constexpr int ZH = 4, RB = 32 * KS1, RBH = RB / ZH, KH = KS1 / ZH, ZP = RBH + 16;
+    static_assert(KS1 % ZH == 0 && RBH == 64, "column parts of 32 channels: a request = 16 token rows of 64 bytes");
+    constexpr int TG = 512 / OC, NL = OC / 8, NG = 32 / TG, NP = 32 * CT / OC, OP = 4 * OC + 16, IMG = 32 * ZP > TG * OP ? 32 * ZP : TG * OP;
+    static_assert(OC == 16 || OC == 32 || OC == 64, "an output request = TG token rows of 2 OC bytes = 1 KB");
+    const u32x4q* const Lf = reinterpret_cast<const u32x4q*>(lds_raw);
+    float* const Lb1 = reinterpret_cast<float*>(lds_raw + (size_t)NF * 1024);
+    const float* const Lb2 = Lb1 + 32 * HT;
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    unsigned char* const Lt = lds_raw + (size_t)NF * 1024 + sizeof(float) * 32 * (HT + CT) + (size_t)wv * IMG;
+    {
+        // piece i of wave w = bytes [1024 (8 i + w), + 1024) of the pack, lane-linear in LDS as packed
+        const u32x4q* src = wfrag + threadIdx.x;
+        u32x4q* dst = reinterpret_cast<u32x4q*>(lds_raw) + wv * 64;
+#pragma unroll
+        for (int i = 0; i < PER; ++i)
+            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(src + i * NT), (__attribute__((address_space(3))) void*)(dst + i * NT), 16, 0, 0);
+        for (int i = threadIdx.x; i < 32 * (HT + CT); i += NT) Lb1[i] = bias[i];
+    }
+    const unsigned nbytes = (unsigned)M * (unsigned)RB;                          // < 2^31 (checked by the launcher)
+    const __amdgpu_buffer_rsrc_t zsrc = __builtin_amdgcn_make_buffer_rsrc((void*)z, 0, nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xres, 0, nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, nbytes, 0x00020000);
+    // z request i of column part q = i / KH: token 16 (i % KH) + lane / 4, byte 16 (lane % 4) of its 64 bytes -- a lane base plus constants
+    const unsigned zo0 = (unsigned)(lane >> 2) * RB + 16u * (lane & 3), za0 = (unsigned)(lane >> 2) * ZP + 16u * (lane & 3);
+    // output request (token group k, piece p): token TG k + lane / NL, bytes 2 OC p + 16 (lane % NL) of its row
+    const unsigned ot = lane / NL, ob = 16u * (lane % NL);
+    const int stride = NW * (int)gridDim.x;
+    int tile = wv * (int)gridDim.x + (int)blockIdx.x;
+    u32x4q zq[KS1];
+    auto load_z = [&](int t) {
+        const unsigned base = (unsigned)t * 32u * RB;                            // (tokens past M: past the buffer -- reads 0, stores dropped)
+#pragma unroll
+        for (int i = 0; i < KS1; ++i)
+            zq[i] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(zsrc, (int)(base + zo0 + 16u * RB * (i % KH) + RBH * (i / KH)), 0, 0));
+    };
+    if (tile < ntiles) load_z(tile);
+    __builtin_amdgcn_s_waitcnt(0x70);                                            // vmcnt(0) lgkmcnt(0): this wave's pieces of the pack have landed
+    __syncthreads();                                                             // the only barrier: a wave without a tile leaves right after it
+    if (PRIO && !(__builtin_popcount(wv) & 1)) __builtin_amdgcn_s_setprio(1);
+    for (; tile < ntiles; tile += stride) {
+        const unsigned base = (unsigned)tile * 32u * RB;
+        bf16x8 zb[KS1];
+#pragma unroll
+        for (int q = 0; q < ZH; ++q) {
+#pragma unroll
+            for (int i = 0; i < KH; ++i) *reinterpret_cast<u32x4q*>(Lt + za0 + 16 * ZP * i) = zq[q * KH + i];
+            wave_sync();
+#pragma unroll
+            for (int k = 0; k < KH; ++k) zb[q * KH + k] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4q*>(Lt + r * ZP + 32 * k + 16 * h));
+            wave_sync();
+        }
+        if (tile + stride < ntiles) load_z(tile + stride);                       // the next tile's channels: in flight during this tile
+        f32x16 d2[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) d2[ct][i] = 0.f;
+#pragma unroll 1
+        for (int ht = 0; ht < HT; ++ht) hidden_tile_ring<KS1, CT, 4>(Lf + (size_t)ht * NCH * 64, Lb1 + 32 * ht, lane, h, zb, d2);
+        u32x4q xq[NG][NP];                                                       // the residual: requested after the products
+#pragma unroll
+        for (int k = 0; k < NG; ++k)
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+                xq[k][p] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(xsrc, (int)(base + (TG * k + ot) * RB + 2u * OC * p + ob), 0, 0));
+#pragma unroll
+        for (int k = 0; k < NG; ++k)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                if (NG == 1 || r / TG == k) {                                    // D2 + b2 of the group's tokens (token on the lane) -> the float32 image
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            if ((32 * ct + 8 * g) / OC != p) continue;
+                            const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + 32 * ct + 8 * g + 4 * h);
+                            *reinterpret_cast<f32x4q*>(Lt + (r % TG) * OP + 4 * (32 * ct + 8 * g - OC * p + 4 * h)) =
+                                f32x4q{d2[ct][4 * g] + bb.x, d2[ct][4 * g + 1] + bb.y, d2[ct][4 * g + 2] + bb.z, d2[ct][4 * g + 3] + bb.w};
+                        }
+                }
+                wave_sync();
+                const unsigned char* src = Lt + ot * OP + 2 * ob;                // -> rows: + x, rounded once
+                const f32x4q lo = *reinterpret_cast<const f32x4q*>(src), hi = *reinterpret_cast<const f32x4q*>(src + 16);
+                const u32x4q xv = xq[k][p];
+                bf16x8 o;
+                o[0] = (__bf16)(lo.x + __uint_as_float(xv.x << 16)); o[1] = (__bf16)(lo.y + __uint_as_float(xv.x & 0xffff0000u));
+                o[2] = (__bf16)(lo.z + __uint_as_float(xv.y << 16)); o[3] = (__bf16)(lo.w + __uint_as_float(xv.y & 0xffff0000u));
+                o[4] = (__bf16)(hi.x + __uint_as_float(xv.z << 16)); o[5] = (__bf16)(hi.y + __uint_as_float(xv.z & 0xffff0000u));
+                o[6] = (__bf16)(hi.z + __uint_as_float(xv.w << 16)); o[7] = (__bf16)(hi.w + __uint_as_float(xv.w & 0xffff0000u));
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, o), ysrc, (int)(base + (TG * k + ot) * RB + 2u * OC * p + ob), 0, 0);
+                wave_sync();
+            }
+    }
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
 // C = 512, H = 1024 (the 7 x 7 stage of M3 / A3): the forms above do not stretch to it.  A wave that owned 32 tokens and all 512 outputs would need 256 accumulator
 // registers next to 128 for its z fragments, and at 49 tokens an image a workgroup must pull all 2 MB of weights whatever its size: next to the matrix cores the
 // weight delivery is the limit, not HBM.  So the work is split by WEIGHT FRAGMENT, not by token: a workgroup of 8 waves (two per SIMD) owns 64 tokens = two
@@ -791,6 +904,28 @@ static hipError_t launch_mlp_pair256(const void* z, const void* x, void* y, cons
     return hipGetLastError();
 }
 
+// C = 128, H = 256: the pack resident in LDS, 8 free-running waves (two per SIMD) a workgroup, one persistent workgroup per CU
+static hipError_t launch_mlp_res128(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, int ncu, hipStream_t s)
+{
+    // Output pieces of 16 / 32 / 64 channels: 56.8 / 57.3 / 60.7 us at batch 256 and 15.2 / 17.2 / 18.2 us at batch 16 (the streamed kernel this form replaced: 66.8 and
+    // 15.1; tools/bench_mlp.py, profiles/r12_channel_mlp128.txt) -- 16, which writes the image with every lane, is no slower than the streamed kernel at any token
+    // count of the sweep, so there is no threshold.  A raised priority on one wave of each SIMD's pair: 57.2 against 57.3 us, no gain without a barrier to align them.
+    constexpr int KS1 = 8, HT = 8, CT = 4, NW = 8, OC = 16;
+    constexpr bool PRIO = false;
+    constexpr int ZIMG = 32 * (32 * KS1 / 4 + 16), OIMG = (512 / OC) * (4 * OC + 16), IMG = ZIMG > OIMG ? ZIMG : OIMG;
+    constexpr size_t pack = (size_t)HT * (KS1 + 2 * CT) * 1024, lds = pack + sizeof(float) * 32 * (HT + CT) + (size_t)NW * IMG;
+    static_assert(pack == 128 * 1024, "the pack of channel_mlp_pack_bytes(128, 256)");
+    static_assert(lds <= 160 * 1024, "the pack, the biases and the waves' images must fit the LDS");
+    if (C != 16 * KS1) return hipErrorInvalidConfiguration;
+    auto kfn = mlp::k_channel_mlp_res128<KS1, HT, CT, OC, PRIO>;
+    RCX_SET_LDS_ONCE(kfn, lds);
+    const int ntiles = (M + 31) / 32;
+    int grid = (ntiles + NW - 1) / NW;
+    if (grid > ncu) grid = ncu;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * NW), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, ntiles);
+    return hipGetLastError();
+}
+
 // C = 512, H = 1024: 8 waves (two per SIMD), 64 tokens a workgroup, the weights straight from global memory
 static hipError_t launch_mlp_wide512(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, hipStream_t s)
 {
@@ -827,7 +962,7 @@ hipError_t channel_mlp(const void* z, const void* x, void* y, const void* wfrag,
                                             : launch_mlp<4, 4, 2, false, false>(z, x, y, wfrag, bias, M, C, ncu, s);         // ... M2 (56 channels)
     if (ks1 == 8 && ht == 8) {
         if (C != 128) return hipErrorInvalidConfiguration;
-        return launch_mlp_stream<8, 8, 4, 8>(z, x, y, wfrag, bias, M, C, ncu, s);
+        return launch_mlp_res128(z, x, y, wfrag, bias, M, C, ncu, s);                                               // M3 / A3 stage 1
     }
     if (ks1 == 3 && ht == 3) return C == 48 ? launch_mlp<3, 3, 2, true, false>(z, x, y, wfrag, bias, M, C, ncu, s)            // M1 stage 0 ...
                                             : launch_mlp<3, 3, 2, false, false>(z, x, y, wfrag, bias, M, C, ncu, s);         // ... M0 (40 channels)

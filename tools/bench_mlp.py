@@ -11,8 +11,10 @@ from recnext_amd import ops
 
 dev = torch.device("cuda:0")
 REPS = int(os.environ.get("REPS", "30"))
+ONLY_C = int(os.environ.get("ONLY_C", "0"))              # time the shapes of one channel count alone
 SHAPES = [(256, 64, 128, 56), (256, 128, 256, 28), (256, 256, 512, 14), (256, 192, 384, 14), (256, 160, 320, 28), (256, 320, 640, 14), (256, 48, 96, 56), (256, 96, 192, 28), (256, 80, 160, 56),
-          (256, 512, 1024, 7), (128, 512, 1024, 7), (64, 512, 1024, 7), (32, 512, 1024, 7), (256, 512, 960, 7)]   # the 7 x 7 stage, its crossover sweep, A3's padded 960
+          (256, 512, 1024, 7), (128, 512, 1024, 7), (64, 512, 1024, 7), (32, 512, 1024, 7), (256, 512, 960, 7),   # the 7 x 7 stage, its crossover sweep, A3's padded 960
+          (64, 128, 256, 28), (16, 128, 256, 28), (4, 128, 256, 28), (1, 128, 256, 28), (256, 128, 240, 28)]   # the resident 128-channel kernel at small M (784 B tokens), A3's padded 240
 
 
 def timed(fn, n):
@@ -29,6 +31,8 @@ def timed(fn, n):
 
 
 for b, c, hid, hw in SHAPES:
+    if ONLY_C and c != ONLY_C:
+        continue
     npool = max(2, int(700e6 / (b * c * hw * hw * 2 * 2)))
     zs = [torch.randn(b, c, hw, hw, device=dev).bfloat16().contiguous(memory_format=torch.channels_last) for _ in range(npool)]
     xs = [torch.randn(b, c, hw, hw, device=dev).bfloat16().contiguous(memory_format=torch.channels_last) for _ in range(npool)]
