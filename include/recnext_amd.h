@@ -306,7 +306,8 @@ int rcx_recattn2d_fwd(const void* x, void* y, const float* w_down_kkc, const flo
  * H % 32 == 0 (pad the hidden layer with zero units: gelu(0) = 0 meets zero weights), C % 8 == 0, M C 2 < 2^31, the weights must fit the LDS.
  * rcx_channel_mlp_supported() says whether there is a kernel for (C, H): today C = 40 / 48 with H = 96, 56 / 64 with 128, 80 / 160, 96 / 192, 128 / 256 (weights resident in LDS) and
  * C = 128 / 256, 160 / 320, 192 / 384, 256 / 512, 320 / 640 (weights streamed through LDS; W2 / b2 padded to an even number of 32-row output tiles when C > 128),
- * and C = 512 / 1024 from a minimum token count M upward (weights straight from global memory; below it the library's GEMMs are faster: ask with the real M);
+ * and C = 512 / 1024, 512 / 768 and 384 / 768, each from a minimum token count M of its own upward (weights straight from global memory; below it the library's GEMMs
+ * are faster: ask with the real M);
  * else RCX_ERR_UNSUPPORTED and the caller keeps the GEMM library.  The products run on the matrix cores with bf16 operands (the hidden activations are
  * rounded to bf16 once, after the GELU) and float32 accumulation.
  */

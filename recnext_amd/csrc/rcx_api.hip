@@ -1123,7 +1123,7 @@ int rcx_channel_mlp_fwd(const void* z, const void* x, void* y, const void* wfrag
     if (y == z || y == x) return fail(RCX_ERR_BAD_ARG, "rcx_channel_mlp_fwd: y must not alias its inputs");
     if (!rcx::channel_mlp_applicable(M, C, H, dtype))
         return fail(RCX_ERR_UNSUPPORTED, "rcx_channel_mlp_fwd: no kernel for M=%d C=%d H=%d dtype %d (bf16; (C, H) = (40 | 48, 96), (56 | 64, 128), (80, 160), (96, 192), (128, 256), (160, 320), "
-                                         "(192, 384), (256, 512), (320, 640), (512, 1024) from a minimum M upward; M C 2 < 2^31)", M, C, H, dtype);
+                                         "(192, 384), (256, 512), (320, 640), and (384, 768), (512, 768), (512, 1024) each from a minimum M upward; M C 2 < 2^31)", M, C, H, dtype);
     hipError_t e = rcx::channel_mlp(z, x, y, wfrag, bias, M, C, H, dtype, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_channel_mlp_fwd");
 }

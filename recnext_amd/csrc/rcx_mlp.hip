@@ -637,13 +637,23 @@ k_channel_mlp_res128(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
 // The arithmetic per element is hidden_tile_ring's (float32 sums in the same k order, the hidden layer rounded once, the output once).
 // Epilogue: + b2 -> a float32 image of 32 tokens x 64 channels per wave (aliased onto the z fragments and exchange buffer 0, both dead after the last barrier)
 // -> rows: + x, 16-byte stores, 128 contiguous bytes per token.  Tokens past M: buffer descriptors (reads 0, stores dropped).
-template <int KS1, int HT, int CT, int RD>
-__global__ void __launch_bounds__(512, 2)
+//
+//
+// The same form at other widths: NW = CT / 2 waves a workgroup, SH = NW hidden tiles a step.  The step count HT / SH may be odd: step s uses exchange buffer
+// (s + HT / SH) & 1, so that the LAST step always uses buffer 1 and buffer 0 is dead behind the last barrier, whatever the parity.
+//   C = 512, H = 768 (stage 3 of RecNeXt-T / S / B):                  <32, 24, 16, RD>: three steps of 8 hidden tiles
+//   C = 384, H = 768 (stage 2 of S / B; the 7 x 7 stage of M1 / A1):  <24, 24, 12, RD, 6>: six waves (SIMDs 0 and 1 hold two, 2 and 3 one), four steps of 6
+// One workgroup a CU in every case (LDS: 134 / 133 / 100.5 KB of 160), i.e. at most two waves a SIMD, 256 registers each: __launch_bounds__'s 2.
+template <int KS1, int HT, int CT, int RD, int NW = 8>
+__global__ void __launch_bounds__(64 * NW, 2)
 k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf16_t* __restrict__ y, const u32x4q* __restrict__ wfrag, const float* __restrict__ bias, int M)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    constexpr int NW = 8, NT = 64 * NW, SH = 8, NST = HT / SH, NCH = KS1 + 2 * CT, NF = KS1 + 4 * SH;      // NF: fragments a wave consumes per step
-    static_assert(CT == 2 * NW && HT % SH == 0 && SH == NW && NF % RD == 0 && KS1 % RD == 0 && KS1 % 8 == 0, "a hidden tile (phase A) and two output tiles (phase B) per wave");
+    constexpr int NT = 64 * NW, SH = NW, NST = HT / SH, NCH = KS1 + 2 * CT, NF = KS1 + 4 * SH;              // NF: fragments a wave consumes per step
+    static_assert(CT == 2 * NW && NW <= 8 && HT % SH == 0 && NF % RD == 0 && KS1 % RD == 0 && KS1 % 8 == 0, "a hidden tile (phase A) and two output tiles (phase B) per wave");
+    constexpr int XP = NST & 1;                                                  // exchange buffer of step s: (s + XP) & 1 -- the last step's is buffer 1
+    constexpr int ZR = KS1 / 4, ZU = 8 * ZR / NW;                                // z: ZR requests per group of 8 tokens, 8 groups, ZU requests a wave
+    static_assert(8 * ZR % NW == 0, "the z requests divide among the waves");
     constexpr int RB = 32 * KS1, OP = 256 + 16, IMG = 32 * OP;                   // bytes per token row; the output image's row pitch (16 bytes of padding: banks)
     constexpr int ZBYTES = 2 * KS1 * 1024, XBYTES = SH * 4 * 1024;
     static_assert(NW * IMG <= ZBYTES + XBYTES, "the output images alias the z fragments and exchange buffer 0");
@@ -669,16 +679,21 @@ k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
     const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, nbytes, 0x00020000);
     const unsigned base = blockIdx.x * 64u * RB;
     {
-        // z -> B fragments: wave w takes tokens 8 w .. 8 w + 7; request j = the 16-byte pieces 8 j + lane / 8 of the rows of tokens lane % 8 (128 contiguous bytes per
-        // row and request; in LDS the 8 tokens of one piece are 128 contiguous bytes of fragment (tt, ks = piece / 2), lane half piece % 2: conflict-free)
-        const unsigned go = base + (8u * wv + (lane & 7)) * RB + 16u * (lane >> 3);
-        u32x4q zq[KS1 / 4];
+        // z -> B fragments: token group tg = tokens 8 tg .. 8 tg + 7; its request j = the 16-byte pieces 8 j + lane / 8 of the rows of tokens lane % 8 (128 contiguous
+        // bytes per row and request; in LDS the 8 tokens of one piece are 128 contiguous bytes of fragment (tt, ks = piece / 2), lane half piece % 2: conflict-free).
+        // The 8 ZR requests go to the waves ZU at a time: 8 waves take a token group each.
+        u32x4q zq[ZU];
 #pragma unroll
-        for (int j = 0; j < KS1 / 4; ++j) zq[j] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(zsrc, (int)(go + 128u * j), 0, 0));
+        for (int i = 0; i < ZU; ++i) {
+            const int tg = ZU == ZR ? wv : (ZU * wv + i) / ZR, j = ZU == ZR ? i : (ZU * wv + i) % ZR;
+            zq[i] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(zsrc, (int)(base + (8u * tg + (lane & 7)) * RB + 16u * (lane >> 3) + 128u * j), 0, 0));
+        }
         for (int i = threadIdx.x; i < 32 * (HT + CT); i += NT) Lb1[i] = bias[i];
-        u32x4q* const dst = Lz + ((wv >> 2) * KS1 + (lane >> 4)) * 64 + ((lane >> 3) & 1) * 32 + 8 * (wv & 3) + (lane & 7);
 #pragma unroll
-        for (int j = 0; j < KS1 / 4; ++j) dst[4 * j * 64] = zq[j];
+        for (int i = 0; i < ZU; ++i) {
+            const int tg = ZU == ZR ? wv : (ZU * wv + i) / ZR, j = ZU == ZR ? i : (ZU * wv + i) % ZR;
+            Lz[((tg >> 2) * KS1 + (lane >> 4) + 4 * j) * 64 + ((lane >> 3) & 1) * 32 + 8 * (tg & 3) + (lane & 7)] = zq[i];
+        }
     }
     __syncthreads();
     if (!(__builtin_popcount(wv) & 1)) __builtin_amdgcn_s_setprio(1);            // one wave of each SIMD's pair takes the matrix pipe first (k_channel_mlp_pair)
@@ -722,7 +737,7 @@ k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
             __builtin_amdgcn_sched_barrier(0);                                  // the request stays RD fragments ahead: left alone, the scheduler sinks each one to its use
         }
         const float* const b1t = Lb1 + 32 * (SH * s + wv);
-        u32x4q* const Lw = Lx + (size_t)(s & 1) * (XBYTES / 16) + wv * 4 * 64 + lane;
+        u32x4q* const Lw = Lx + (size_t)((s + XP) & 1) * (XBYTES / 16) + wv * 4 * 64 + lane;
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             gelu_f32x2 gv[8];
@@ -758,7 +773,7 @@ k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
                 for (int j = 0; j < 4; ++j)
                     xq[tt][j] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(xsrc, (int)(base + (32u * tt + 8u * j + ot) * RB + 128u * wv + ob), 0, 0));
         }
-        const u32x4q* const Lr = Lx + (size_t)(s & 1) * (XBYTES / 16) + lane;
+        const u32x4q* const Lr = Lx + (size_t)((s + XP) & 1) * (XBYTES / 16) + lane;
         u32x4q hq[2][2][2];                                                      // [hl parity][tt][q]
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt)
@@ -831,6 +846,12 @@ static bool mlp_shape(int C, int H, int* ks1, int* ht, int* ct)
 // none in the sweep -- M = 1 568 / 3 136 / 6 272 / 12 544: 29.3 / 29.8 / 31.3 / 36.5 us fused against 53.1 / 52.7 / 53.7 / 62.6 us, so it lies below 1 024, the token
 // count tests/test_mlp_gpu.py pins as unsupported; hence 2 048, the smallest sweep point above it with margin.
 static constexpr int MLP512_MIN_TOKENS = 2048;
+// C = 512, H = 768 and C = 384, H = 768 likewise, each from the smallest point of its sweep (tools/bench_mlp.py, three runs in one job, profiles/r13_channel_mlp768.txt): no
+// crossover in either -- 4 x 4 planes, M = 512 / 1 024 / 2 048 / 4 096 / 8 192: 23.2-23.6 / 23.9-24.9 / 23.8-26.4 / 25.3-25.6 / 28.5-33.0 us fused against 51.0-53.4 /
+// 51.9-67.8 / 51.0-53.3 / 51.0-52.5 / 49.7-50.6 us for the four library launches; 7 x 7 planes, M = 784 / 1 568 / 3 136 / 6 272 / 12 544: 23.6-23.8 / 23.3-23.4 / 23.8-24.1 /
+// 24.8-27.9 / 27.3-27.9 us against 52.8-54.8 / 50.8-52.5 / 50.9-52.7 / 50.9-53.1 / 51.8-54.2.  Below the sweeps nothing was measured, so nothing is offered there.
+static constexpr int MLP512X768_MIN_TOKENS = 512;
+static constexpr int MLP384_MIN_TOKENS = 784;
 
 bool channel_mlp_applicable(int M, int C, int H, int dtype)
 {
@@ -839,6 +860,8 @@ bool channel_mlp_applicable(int M, int C, int H, int dtype)
     if ((unsigned long long)M * C * 2 >= (1ull << 31)) return false;
     // the 7 x 7 stage: a workgroup streams all 2 MB of weights for its 64 tokens, so a few workgroups on a mostly idle chip lose to the library's N-split GEMMs
     if (C == 512 && ht == 32) return M >= MLP512_MIN_TOKENS;
+    if (C == 512 && ht == 24) return M >= MLP512X768_MIN_TOKENS;
+    if (C == 384 && ht == 24) return M >= MLP384_MIN_TOKENS;
     if (C == 256 && ht == 16) return true;
     if (C == 192 && ht == 12) return true;
     if ((C == 160 && ht == 10) || (C == 320 && ht == 20)) return true;
@@ -926,16 +949,16 @@ static hipError_t launch_mlp_res128(const void* z, const void* x, void* y, const
     return hipGetLastError();
 }
 
-// C = 512, H = 1024: 8 waves (two per SIMD), 64 tokens a workgroup, the weights straight from global memory
-static hipError_t launch_mlp_wide512(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, hipStream_t s)
+// C = 512, H = 1024 | 768 and C = 384, H = 768: NW waves, 64 tokens a workgroup, the weights straight from global memory
+template <int KS1, int HT, int CT, int NW>
+static hipError_t launch_mlp_wide(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, hipStream_t s)
 {
-    constexpr int KS1 = 32, HT = 32, CT = 16;
-    constexpr size_t lds = (size_t)2 * KS1 * 1024 + (size_t)2 * 8 * 4 * 1024 + sizeof(float) * 32 * (HT + CT);
+    constexpr size_t lds = (size_t)2 * KS1 * 1024 + (size_t)2 * NW * 4 * 1024 + sizeof(float) * 32 * (HT + CT);
     static_assert(lds <= 160 * 1024, "the z fragments, the exchange buffers and the biases must fit the LDS");
     if (C != 16 * KS1) return hipErrorInvalidConfiguration;
-    auto kfn = mlp::k_channel_mlp_wide<KS1, HT, CT, 8>;
+    auto kfn = mlp::k_channel_mlp_wide<KS1, HT, CT, 8, NW>;
     RCX_SET_LDS_ONCE(kfn, lds);
-    hipLaunchKernelGGL(kfn, dim3((unsigned)((M + 63) / 64)), dim3(512), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)((M + 63) / 64)), dim3(64 * NW), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M);
     return hipGetLastError();
 }
 
@@ -953,7 +976,9 @@ hipError_t channel_mlp(const void* z, const void* x, void* y, const void* wfrag,
             cus[dev].store(ncu, std::memory_order_relaxed);
         }
     }
-    if (C == 512 && ht == 32) return launch_mlp_wide512(z, x, y, wfrag, bias, M, C, s);                                // M3 / A3 stage 3
+    if (C == 512 && ht == 32) return launch_mlp_wide<32, 32, 16, 8>(z, x, y, wfrag, bias, M, C, s);                 // M3 / A3 stage 3
+    if (C == 512 && ht == 24) return launch_mlp_wide<32, 24, 16, 8>(z, x, y, wfrag, bias, M, C, s);                 // T / S / B stage 3
+    if (C == 384 && ht == 24) return launch_mlp_wide<24, 24, 12, 6>(z, x, y, wfrag, bias, M, C, s);                    // S / B stage 2, M1 / A1 stage 3
     if (C == 256 && ht == 16) return launch_mlp_pair256(z, x, y, wfrag, bias, M, C, ncu, s);                         // M3 / A3 stage 2
     if (C == 192 && ht == 12) return launch_mlp_stream<12, 12, 6, 4>(z, x, y, wfrag, bias, M, C, ncu, s);           // M1 stage 2
     if (C == 160 && ht == 10) return launch_mlp_stream<10, 10, 6, 4>(z, x, y, wfrag, bias, M, C, ncu, s);           // M5 / A5 stage 1

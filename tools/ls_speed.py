@@ -1,7 +1,7 @@
 """Throughput of the LSNet-style RecNeXt-T / S / B: the HIP token half against the same models with the token half on the operator chain of
 tests/ls_eager.py, in one process (recnext_amd.speed's loop: BN folded, channels_last, tuned GEMMs).  One JSON line per (model, path).
 
-    python tools/ls_speed.py [--models recnext_t,recnext_s,recnext_b] [--batch-size 256] [--dtype bf16] [--t0 3] [--t1 6] [--out FILE]
+    python tools/ls_speed.py [--models recnext_t,recnext_s,recnext_b] [--batch-size 256] [--dtype bf16] [--t0 3] [--t1 6] [--paths hip,ops_chain] [--out FILE]
     python tools/ls_speed.py --models recnext_t --batch-size 256 --once      # one forward after a warm-up (for a kernel trace)
 """
 import argparse
@@ -28,13 +28,16 @@ def main():
     ap.add_argument("--t0", type=float, default=3.0)
     ap.add_argument("--t1", type=float, default=6.0)
     ap.add_argument("--once", action="store_true", help="HIP path only: warm up, then one synchronised forward")
+    ap.add_argument("--paths", default="hip,ops_chain", help="which token halves to time: hip, ops_chain or both")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if not args.paths or set(args.paths.split(",")) - {"hip", "ops_chain"}:
+        ap.error(f"--paths takes hip, ops_chain or both, got {args.paths!r}")
     dtype = speed.DTYPES[args.dtype]
     dev = "cuda:0"
     lines = []
     for name in args.models.split(","):
-        paths = (("hip", None),) if args.once else (("hip", None), ("ops_chain", eager_token_mixer))
+        paths = (("hip", None),) if args.once else tuple(p for p in (("hip", None), ("ops_chain", eager_token_mixer)) if p[0] in args.paths.split(","))
         for path, mixer in paths:
             net = speed.build_inference_model(name, dev, dtype, token_mixer=mixer)
             with torch.no_grad():
