@@ -387,6 +387,24 @@ int rcx_ls_la3_tiled_fwd(const void* x, void* r, void* t, const float* w_rep, co
                          int B, int H, int W, int C, int split, int heads, int dtype, void* stream);
 
 /*
+ * The token half of a SHARE block of the share-channel RecNeXt-T / S / B (lsnet/model/recattn_share_channel.py): replaces :8-15 (RepVGGDW), :281-283
+ * (ShareChannelOperation: x + cat(x1s)) and the token side of :302-304 in one launch (eval mode, BatchNorms folded):
+ *     r = dw3x3(x; w_rep, b_rep)                                  the folded RepVGGDW pack of the entries above, the same bits as their r
+ *     t[pixel, j*split + c] = r[pixel, j*split + c] + srcs[j][pixel * src_pixel_stride + c]        c < split, j < n_src
+ * x, r, t: B x H x W x C NHWC of `dtype` (float32, bf16 or f16).  srcs: a HOST array of n_src device pointers, read during the call and not kept
+ * (the pointers travel to the kernel by value).  Each is the first channel of a B x H x W tensor of `dtype` whose pixels lie src_pixel_stride
+ * elements apart: C for the first `split` channels of an earlier block's t (the slice mixer's output x1, :272-276, read in place), `split` for a
+ * dense tensor.  Elements [split, stride) of a source pixel are never read.  r and t alias neither x, nor each other, nor a source.  Every pointer
+ * non-NULL and aligned to four elements of `dtype` (the packs to 16 bytes).  float32 arithmetic; t is the unrounded r plus the source, so each output
+ * is rounded once at its store; no atomics, no workspace, any H x W >= 1 x 1.  Supported (rcx_ls_share_supported: 1 / 0; the entry also wants
+ * src_pixel_stride >= split and a multiple of 4): C and split multiples of 4, n_src * split == C, 1 <= n_src <= 8, B*H*W*C < 2^31, a known dtype;
+ * else RCX_ERR_UNSUPPORTED.  RCX_ERR_BAD_ARG for a NULL or misaligned pointer, a non-positive extent, an unknown dtype or aliasing outputs.
+ */
+int rcx_ls_share_supported(int B, int H, int W, int C, int split, int n_src, int dtype);
+int rcx_ls_share_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const void* const* srcs, int n_src,
+                     long long src_pixel_stride, int B, int H, int W, int C, int split, int dtype, void* stream);
+
+/*
  * Backward of rcx_linear_attention_fwd(the gradients engine.py:48-64 needs through RecAttn2d, model/recattn.py:16-28 / :39-51):
  *   given gout = dL/dout (B x n x C), writes gq = dL/dqpre, gk = dL/dkpre, gv = dL/dv (all B x n x C, `dtype`); dL/dpe = gout is the
  *   caller's.  float32 arithmetic, deterministic (fixed summation order).  C/heads at most 64.

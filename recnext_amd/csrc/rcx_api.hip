@@ -1253,6 +1253,34 @@ int rcx_ls_la3_tiled_fwd(const void* x, void* r, void* t, const float* w_rep, co
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_ls_la3_tiled_fwd");
 }
 
+int rcx_ls_share_supported(int B, int H, int W, int C, int split, int n_src, int dtype)
+{
+    return rcx::ls_share_applicable(B, H, W, C, split, n_src, split, dtype) ? 1 : 0;
+}
+
+int rcx_ls_share_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const void* const* srcs, int n_src,
+                     long long src_pixel_stride, int B, int H, int W, int C, int split, int dtype, void* stream)
+{
+    if (!x || !r || !t || !w_rep || !b_rep || !srcs) return fail(RCX_ERR_BAD_ARG, "rcx_ls_share_fwd: null pointer");
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || split <= 0 || n_src <= 0)
+        return fail(RCX_ERR_BAD_ARG, "non-positive extent B=%d H=%d W=%d C=%d split=%d n_src=%d", B, H, W, C, split, n_src);
+    if (!known_dtype(dtype)) return fail(RCX_ERR_BAD_ARG, "unknown dtype %d", dtype);
+    if (r == x || t == x || r == t) return fail(RCX_ERR_BAD_ARG, "rcx_ls_share_fwd: r and t must alias neither x nor each other");
+    const size_t align = dtype == RCX_DTYPE_F32 ? 16 : 8;           // four elements, as check_wide
+    if ((size_t)x % align || (size_t)r % align || (size_t)t % align || any_misaligned({w_rep, b_rep}))
+        return fail(RCX_ERR_BAD_ARG, "rcx_ls_share_fwd: x, r and t must be aligned to four elements (%zu bytes), the packs to 16 bytes", align);
+    for (int j = 0; j < n_src; ++j) {
+        if (!srcs[j]) return fail(RCX_ERR_BAD_ARG, "rcx_ls_share_fwd: null source %d", j);
+        if ((size_t)srcs[j] % align) return fail(RCX_ERR_BAD_ARG, "rcx_ls_share_fwd: source %d must be aligned to four elements (%zu bytes)", j, align);
+        if (srcs[j] == r || srcs[j] == t) return fail(RCX_ERR_BAD_ARG, "rcx_ls_share_fwd: r and t must not alias source %d", j);
+    }
+    if (!rcx::ls_share_applicable(B, H, W, C, split, n_src, src_pixel_stride, dtype))
+        return fail(RCX_ERR_UNSUPPORTED, "rcx_ls_share_fwd: C=%d, split=%d, %d sources, pixel stride %lld: C, split and the stride multiples of 4, n_src * split "
+                                         "== C, 1 .. %d sources, stride >= split, B*H*W*C < 2^31", C, split, n_src, src_pixel_stride, rcx::kLsShareMaxSrc);
+    hipError_t e = rcx::ls_share_fwd(x, r, t, w_rep, b_rep, srcs, n_src, src_pixel_stride, B, H, W, C, split, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rcx_ls_share_fwd");
+}
+
 int rcx_linear_attention_bwd(const void* qpre, const void* kpre, const void* v, const void* gout, void* gq, void* gk, void* gv,
                              int B, int n, int C, int heads, int dtype, void* stream)
 {

@@ -205,6 +205,11 @@ hipError_t ls_recattn_tiled_fwd(const void* x, void* r, void* t, const float* w_
 hipError_t ls_la3_tiled_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* wqT, const float* bq,
                             const float* wkT, const float* bk, const float* w_pe, const float* b_pe, void* workspace, int B, int H, int W, int C,
                             int split, int heads, int dtype, hipStream_t s);
+// rcx_lsshare.hip: the token half of a share block of the share-channel T / S / B: r = RepVGGDW(x), t = r + the sources side by side, one launch
+constexpr int kLsShareMaxSrc = 8;
+bool ls_share_applicable(int B, int H, int W, int C, int split, int n_src, long long stride, int dtype);
+hipError_t ls_share_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const void* const* srcs, int n_src, long long stride,
+                        int B, int H, int W, int C, int split, int dtype, hipStream_t s);
 hipError_t recattn_qkcore(const float* d, const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe, float* out, void* workspace,
                           int B, int Hp, int Wp, int C, int heads, hipStream_t s);
 

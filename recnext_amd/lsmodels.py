@@ -276,6 +276,10 @@ class MetaNeXtBlock(nn.Module):
         else:
             r = self.rep_mixer(x)
             t = self.token_mixer(r)
+        return self._channel_half(r, t)
+
+    def _channel_half(self, r, t):
+        """r + drop_path(channel_mixer(t)): the block's tail, whatever made (r, t)."""
         fused = self.__dict__.get("_fused_mlp")
         if fused is not None and not self.training and fused.usable(self.channel_mixer, t, r):
             return fused(t, r)                              # r + channel_mixer(t) in one launch (models.use_fused_mlp)
@@ -325,9 +329,10 @@ class RecNextStage(nn.Module):
 
 class RecNext(nn.Module):
     def __init__(self, in_chans=3, embed_dim=(48,), depth=(2,), mlp_ratios=(2,), num_heads=(2,), global_pool="avg", num_classes=1000, act_layer=nn.GELU,
-                 distillation=False, split_rates=(4,), drop_rate=0.0, drop_path_rate=0.0, token_mixer=None):
+                 distillation=False, split_rates=(4,), drop_rate=0.0, drop_path_rate=0.0, token_mixer=None, stage_factory=None):
         from .models import RecNextClassifier
         super().__init__()
+        stage_factory = stage_factory or RecNextStage        # RecNextStage's signature (recnext_amd.lsshare brings its own stage)
         self.global_pool = global_pool
         self.embed_dim = tuple(embed_dim)
         self.num_classes = num_classes
@@ -336,8 +341,8 @@ class RecNext(nn.Module):
         dpr = [x.tolist() for x in torch.linspace(0, drop_path_rate, sum(depth)).split(list(depth))]
         stages = []
         for i in range(len(embed_dim)):
-            stages.append(RecNextStage(in_channels, embed_dim[i], depth[i], mlp_ratio=mlp_ratios[i], num_heads=num_heads[i], act_layer=act_layer,
-                                       downsample=i != 0, stage=i, split_rate=split_rates[i], drop_path_rates=dpr[i], token_mixer=token_mixer))
+            stages.append(stage_factory(in_channels, embed_dim[i], depth[i], mlp_ratio=mlp_ratios[i], num_heads=num_heads[i], act_layer=act_layer,
+                                        downsample=i != 0, stage=i, split_rate=split_rates[i], drop_path_rates=dpr[i], token_mixer=token_mixer))
             in_channels = embed_dim[i]
         self.stages = nn.Sequential(*stages)
         self.num_features = embed_dim[-1]

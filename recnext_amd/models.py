@@ -185,11 +185,15 @@ class RecNext(nn.Module):
 
 def create_model(name, distillation=False, token_mixer=None, **overrides):
     """``timm.create_model`` stand-in for the twelve registered names (model/recnext.py:365-407, model/recattn.py:378-420) and the LSNet-style
-    recnext_t / _s / _b (lsnet/model/recattn.py:441-466, built by recnext_amd.lsmodels; ``token_mixer(dim, num_heads, stage)`` there)."""
+    recnext_t / _s / _b (lsnet/model/recattn.py:441-466, built by recnext_amd.lsmodels; ``token_mixer(dim, num_heads, stage)`` there) and their
+    share-channel siblings recnext_t_share_channel / _s_ / _b_ (lsnet/model/recattn_share_channel.py:461-485, built by recnext_amd.lsshare)."""
     if name not in CONFIGS:
         from . import lsmodels
         if name in lsmodels.LS_CONFIGS:
             return lsmodels.create_model(name, distillation=distillation, token_mixer=token_mixer, **overrides)
+        from . import lsshare
+        if name in lsshare.SHARE_CONFIGS:
+            return lsshare.create_model(name, distillation=distillation, token_mixer=token_mixer, **overrides)
     cfg = dict(CONFIGS[name])
     if distillation:
         cfg["drop_path"] = 0.0                      # drop_path applies to the non-distilled recipe only
