@@ -21,6 +21,52 @@
 #include "rcx_gelu.h"
 #include <type_traits>
 
+// -DRCX_MLP_STAMPS is the diagnostic build of this file alone (tools/mlp_timeline.py): s_memtime at the phase boundaries of a hidden step, summed per wave into a
+// buffer of the tool's own -- [wave slot][8]: 0 ring preload, 1 D1, 2 b1 + GELU, 3 D2, 4 barrier / DMA wait, 5 the tile's prologue and epilogue, 6 hidden steps.
+// Each stamp drains the wave's LDS reads (s_memtime returns through the same counter), so a request that the product build keeps in flight across a phase
+// boundary lands in the phase that issued it; a product's own latency shows in the phase that first reads its result.  Without the macro all of it expands to nothing.
+#ifdef RCX_MLP_STAMPS
+#define RCX_MLP_STAMP(k)                                                                                        \
+    {                                                                                                           \
+        __builtin_amdgcn_sched_barrier(0);                                                                      \
+        unsigned long long t_;                                                                                  \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                              \
+        __builtin_amdgcn_sched_barrier(0);                                                                      \
+        tsum[k] += t_ - tlast;                                                                                  \
+        tlast = t_;                                                                                             \
+    }
+#define RCX_MLP_STAMP_BEGIN                                                                                     \
+    unsigned long long tsum[7] = {0, 0, 0, 0, 0, 0, 0}, tlast;                                                  \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast)::"memory");
+#define RCX_MLP_STAMP_STEP tsum[6] += 1;
+#define RCX_MLP_STAMP_END(slot)                                                                                 \
+    if (stamps && (threadIdx.x & 63) == 0) {                                                                    \
+        _Pragma("unroll") for (int k_ = 0; k_ < 7; ++k_) stamps[(size_t)(slot) * 8 + k_] = tsum[k_];            \
+    }
+#define RCX_MLP_STAMP_PARM , unsigned long long (&tsum)[7], unsigned long long& tlast
+#define RCX_MLP_STAMP_PASS , tsum, tlast
+#define RCX_MLP_STAMP_ARG , unsigned long long* __restrict__ stamps
+#define RCX_MLP_STAMP_VAL , g_stamps
+namespace rcx {
+static unsigned long long* g_stamps = nullptr;
+}
+#else
+#define RCX_MLP_STAMP(k)
+#define RCX_MLP_STAMP_BEGIN
+#define RCX_MLP_STAMP_STEP
+#define RCX_MLP_STAMP_END(slot)
+#define RCX_MLP_STAMP_PARM
+#define RCX_MLP_STAMP_PASS
+#define RCX_MLP_STAMP_ARG
+#define RCX_MLP_STAMP_VAL
+#endif
+
+// k_channel_mlp_pair runs the hidden step in its pinned form (hidden_tile_pinned); -DRCX_MLP_PINNED=false builds it in hidden_tile_ring's, as the compiler
+// schedules it: the "before" of tools/mlp_timeline.py
+#ifndef RCX_MLP_PINNED
+#define RCX_MLP_PINNED true
+#endif
+
 namespace rcx {
 namespace mlp {
 
@@ -41,17 +87,46 @@ __device__ __forceinline__ void wave_sync()
 }
 // (row of accumulator register i in lane half h of a 32 x 32 tile: (i & 3) + 8 (i >> 2) + 4 h -- ops.py::_mlp_acc_unit orders W2's columns by it)
 
+// The middle of a hidden tile, ONE text for both forms of the step below so that they cannot drift apart: h = 2 gelu(D1 + b1) in float32, rounded to bf16 -- with
+// D1's accumulator layout already the second product's two B operands.  Declares hb[2]; QUAD: the lane's b1 quad g (units 8 g + 4 h ..), read from LDS on the spot
+// (hidden_tile_ring) or requested earlier (hidden_tile_pinned).  A macro, not a function: through a helper the compiler scheduled the kernels that keep
+// hidden_tile_ring's form differently from the parent's listing; expanded in place their code is the parent's, instruction for instruction.
+// The tile's 16 values go four pairs in lockstep at a time (eight: the kernels at their register limit spill); TWICE the GELU -- W2 is stored halved (ops.pack_channel_mlp).
+#define RCX_MLP_HIDDEN_GELU(QUAD)                                                                                                         \
+    bf16x8 hb[2];                                                                                                                         \
+    gelu_f32x2 gv[8];                                                                                                                     \
+    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                                                       \
+        const f32x4q bb = QUAD;                                                                                                           \
+        gv[2 * g] = gelu_f32x2{d1[4 * g] + bb.x, d1[4 * g + 1] + bb.y};                                                                   \
+        gv[2 * g + 1] = gelu_f32x2{d1[4 * g + 2] + bb.z, d1[4 * g + 3] + bb.w};                                                           \
+    }                                                                                                                                     \
+    {                                                                                                                                     \
+        gelu_f32x2 ga[4] = {gv[0], gv[1], gv[2], gv[3]}, gb[4] = {gv[4], gv[5], gv[6], gv[7]};                                            \
+        gelu2x_batch<4>(ga);                                                                                                              \
+        gelu2x_batch<4>(gb);                                                                                                              \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) { gv[i] = ga[i]; gv[4 + i] = gb[i]; }                                               \
+    }                                                                                                                                     \
+    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                                                       \
+        hb[g >> 1][4 * (g & 1) + 0] = (__bf16)gv[2 * g].x; hb[g >> 1][4 * (g & 1) + 1] = (__bf16)gv[2 * g].y;                             \
+        hb[g >> 1][4 * (g & 1) + 2] = (__bf16)gv[2 * g + 1].x; hb[g >> 1][4 * (g & 1) + 3] = (__bf16)gv[2 * g + 1].y;                     \
+    }
+
 // One 32-unit tile of the hidden layer from its chunk of fragments in LDS (Lc: KS1 W1 fragments, then 2 CT W2 fragments in (ct, q) order):
 //   D1 = W1 tile x z^T, h = gelu(D1 + b1) -> bf16 (already the second product's B operand), D2 += W2 columns x h.
 // The fragments go through register rings RD deep, requested RD products ahead -- and the second product's first RD before the GELU: a read issued right in
 // front of its product costs the LDS latency per product (measured: 13 % of the matrix-core peak whatever the shape).
+// AS WRITTEN the compiler does not emit that: its scheduler regroups the requests into batches that each end in a full drain (lgkmcnt(0)) right behind the newest
+// request, fetches the four b1 quads one dependent round trip at a time behind the last D1 product, and -- in the kernels at their register limit -- sinks the
+// second product's first fragments below the GELU (tools/check_mlp_waits.py counts it in the listing).  This is the form of k_channel_mlp, k_channel_mlp_res128,
+// k_channel_mlp_stream and the non-staged path; hidden_tile_pinned below is the same arithmetic with the order pinned.
 template <int KS1, int CT, int RD>
-__device__ __forceinline__ void hidden_tile_ring(const u32x4q* Lc, const float* b1t, int lane, int h, const bf16x8 (&zb)[KS1], f32x16 (&d2)[CT])
+__device__ __forceinline__ void hidden_tile_ring(const u32x4q* Lc, const float* b1t, int lane, int h, const bf16x8 (&zb)[KS1], f32x16 (&d2)[CT] RCX_MLP_STAMP_PARM)
 {
     constexpr int R1 = KS1 < RD ? KS1 : RD, N2 = 2 * CT, R2 = N2 < RD ? N2 : RD;
     u32x4q ring[RD];
 #pragma unroll
     for (int j = 0; j < R1; ++j) ring[j] = Lc[j * 64 + lane];
+    RCX_MLP_STAMP(0)
     f32x16 d1;
 #pragma unroll
     for (int i = 0; i < 16; ++i) d1[i] = 0.f;
@@ -61,36 +136,83 @@ __device__ __forceinline__ void hidden_tile_ring(const u32x4q* Lc, const float* 
         if (ks + R1 < KS1) ring[ks % R1] = Lc[(ks + R1) * 64 + lane];
         d1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, zb[ks], d1, 0, 0, 0);
     }
+    RCX_MLP_STAMP(1)
     // the second product's fragments in use order: f = q CT + ct  ->  pack slot KS1 + 2 ct + q
+#ifndef RCX_MLP_STAMPS                                // (the diagnostic build requests them behind the GELU, where the product build's scheduler puts all but one:
+                                                      // fenced in here by the stamps they would spill in the kernels at their register limit)
 #pragma unroll
     for (int f = 0; f < R2; ++f) ring[f] = Lc[(KS1 + 2 * (f % CT) + f / CT) * 64 + lane];
-    bf16x8 hb[2];
-    gelu_f32x2 gv[8];
+#endif
+    RCX_MLP_HIDDEN_GELU(*reinterpret_cast<const f32x4q*>(b1t + 8 * g + 4 * h))
+#ifdef RCX_MLP_STAMPS
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4q bb = *reinterpret_cast<const f32x4q*>(b1t + 8 * g + 4 * h);
-        gv[2 * g] = gelu_f32x2{d1[4 * g] + bb.x, d1[4 * g + 1] + bb.y};
-        gv[2 * g + 1] = gelu_f32x2{d1[4 * g + 2] + bb.z, d1[4 * g + 3] + bb.w};
-    }
-    {                                                 // the tile's 16 values, four pairs in lockstep at a time (eight: the kernels at their register limit spill); TWICE
-                                                      // the GELU -- W2 is stored halved (ops.pack_channel_mlp)
-        gelu_f32x2 ga[4] = {gv[0], gv[1], gv[2], gv[3]}, gb[4] = {gv[4], gv[5], gv[6], gv[7]};
-        gelu2x_batch<4>(ga);
-        gelu2x_batch<4>(gb);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { gv[i] = ga[i]; gv[4 + i] = gb[i]; }
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        hb[g >> 1][4 * (g & 1) + 0] = (__bf16)gv[2 * g].x; hb[g >> 1][4 * (g & 1) + 1] = (__bf16)gv[2 * g].y;
-        hb[g >> 1][4 * (g & 1) + 2] = (__bf16)gv[2 * g + 1].x; hb[g >> 1][4 * (g & 1) + 3] = (__bf16)gv[2 * g + 1].y;
-    }
+    for (int f = 0; f < R2; ++f) ring[f] = Lc[(KS1 + 2 * (f % CT) + f / CT) * 64 + lane];
+#endif
+    RCX_MLP_STAMP(2)
 #pragma unroll
     for (int f = 0; f < N2; ++f) {
         const bf16x8 a = __builtin_bit_cast(bf16x8, ring[f % R2]);
         if (f + R2 < N2) ring[f % R2] = Lc[(KS1 + 2 * ((f + R2) % CT) + (f + R2) / CT) * 64 + lane];
         d2[f % CT] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, hb[f / CT], d2[f % CT], 0, 0, 0);
     }
+    RCX_MLP_STAMP(3)
+}
+
+// The same tile -- every float32 operation and its order are hidden_tile_ring's, so the result is bit-identical -- with the ORDER of the LDS requests pinned:
+// a scheduling barrier behind every product keeps each request where it is written (k_channel_mlp_wide's remedy), and the compiler's own wait insertion then
+// counts: LDS reads of a wave return in order, so a product waits for lgkmcnt(requests issued after its fragment's), not for 0.
+//   D1     request ks + R1 goes out in front of product ks; the last R1 products have nothing left to request and drain the ring.
+//   b1     all four quads are requested together in front of the B1AT-th product from the end of D1 (B1AT <= R1: behind the ring's last request) -- one wait, under
+//          D1's last products.
+//   W2     its first P2 fragments are requested behind D1's last product, in front of the b1 adds and the GELU; P2 < R2 where the GELU's batch leaves no more
+//          registers (the rest of the ring follows right behind the GELU).  Then as D1: R2 ahead, the last R2 products drain.
+// PRE2 / B1AT are per kernel: the budget is its registers, and the only guard of that budget is the build's scratch scan (_obj/scratch.ok) -- the values were
+// found by compiling, so a compiler that allocates differently may ask for smaller ones.
+// Only k_channel_mlp_pair takes this form.  (The resident 128-channel kernel with the ring carried from step to step -- D2's last products requesting the next
+// chunk's first W1 fragments, no drain at all -- and k_channel_mlp measured no faster than in hidden_tile_ring's form: profiles/r15_mlp_ring.txt.)
+template <int KS1, int CT, int RD, int PRE2, int B1AT>
+__device__ __forceinline__ void hidden_tile_pinned(const u32x4q* Lc, const float* b1t, int lane, int h, const bf16x8 (&zb)[KS1], f32x16 (&d2)[CT] RCX_MLP_STAMP_PARM)
+{
+    constexpr int R1 = KS1 < RD ? KS1 : RD, N2 = 2 * CT, R2 = N2 < RD ? N2 : RD, P2 = PRE2 < R2 ? PRE2 : R2;
+    static_assert(B1AT >= 1 && B1AT <= KS1 && P2 >= 1, "b1 is requested inside D1, W2 before the GELU");
+    u32x4q ring[RD];
+#pragma unroll
+    for (int j = 0; j < R1; ++j) ring[j] = Lc[j * 64 + lane];
+    RCX_MLP_STAMP(0)
+    f32x16 d1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) d1[i] = 0.f;
+    f32x4q bq[4];
+#pragma unroll
+    for (int ks = 0; ks < KS1; ++ks) {
+        const bf16x8 a = __builtin_bit_cast(bf16x8, ring[ks % R1]);
+        if (ks + R1 < KS1) ring[ks % R1] = Lc[(ks + R1) * 64 + lane];
+        if (ks == KS1 - B1AT) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4q*>(b1t + 8 * g + 4 * h);
+        }
+        d1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, zb[ks], d1, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    RCX_MLP_STAMP(1)
+    // the second product's fragments in use order: f = q CT + ct  ->  pack slot KS1 + 2 ct + q
+#pragma unroll
+    for (int f = 0; f < P2; ++f) ring[f] = Lc[(KS1 + 2 * (f % CT) + f / CT) * 64 + lane];
+    __builtin_amdgcn_sched_barrier(0);
+    RCX_MLP_HIDDEN_GELU(bq[g])
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int f = P2; f < R2; ++f) ring[f] = Lc[(KS1 + 2 * (f % CT) + f / CT) * 64 + lane];
+    __builtin_amdgcn_sched_barrier(0);                // (without it the scheduler issues these behind D2's first product, in another order, and drains)
+    RCX_MLP_STAMP(2)
+#pragma unroll
+    for (int f = 0; f < N2; ++f) {
+        const bf16x8 a = __builtin_bit_cast(bf16x8, ring[f % R2]);
+        if (f + R2 < N2) ring[f % R2] = Lc[(KS1 + 2 * ((f + R2) % CT) + (f + R2) / CT) * 64 + lane];
+        d2[f % CT] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, hb[f / CT], d2[f % CT], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    RCX_MLP_STAMP(3)
 }
 
 // LDS: per hidden tile ht its KS1 W1 fragments and 2 CT W2 fragments (1 KB each: 64 lanes x 16 bytes; ops.pack_channel_mlp), then b1 (32 HT floats), b2 (32 CT floats)
@@ -101,7 +223,7 @@ __device__ __forceinline__ void hidden_tile_ring(const u32x4q* Lc, const float* 
 template <int KS1, int HT, int CT, int NW, int WPS, bool KX, bool OX, bool STAGED>
 __global__ void __launch_bounds__(64 * NW, WPS)
 k_channel_mlp(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf16_t* __restrict__ y, const u32x4q* __restrict__ wfrag, const float* __restrict__ bias,
-              int M, int C, int ntiles)
+              int M, int C, int ntiles RCX_MLP_STAMP_ARG)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     constexpr int NF = HT * KS1 + CT * 2 * HT;
@@ -129,8 +251,11 @@ k_channel_mlp(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf1
 #pragma unroll
         for (int g = 0; g < 4; ++g) oc[ct][g] = OX || 32 * ct + 8 * g + 4 * h < C ? 2u * (32 * ct + 8 * g + 4 * h) : 0x80000000u;
 
+    RCX_MLP_STAMP_BEGIN
     auto hidden_tile = [&](int ht, const bf16x8 (&zb)[KS1], f32x16 (&d2)[CT]) {
-        hidden_tile_ring<KS1, CT, 4>(Lf + (size_t)ht * (KS1 + 2 * CT) * 64, Lb1 + 32 * ht, lane, h, zb, d2);
+        // (hidden_tile_ring's form: pinned, the 56 x 56 kernel measured 73.0 against 74.5 - 75.0 us, inside its own run-to-run spread -- it is memory-bound)
+        hidden_tile_ring<KS1, CT, 4>(Lf + (size_t)ht * (KS1 + 2 * CT) * 64, Lb1 + 32 * ht, lane, h, zb, d2 RCX_MLP_STAMP_PASS);
+        RCX_MLP_STAMP_STEP
     };
     const int stride = gridDim.x * NW;
     int tile = blockIdx.x * NW + wave;
@@ -181,6 +306,7 @@ k_channel_mlp(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf1
             for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) d2[ct][i] = 0.f;
+            RCX_MLP_STAMP(5)
 #pragma unroll 1
             for (int ht = 0; ht < HT; ++ht) hidden_tile(ht, zb, d2);
             // D2 + b2 (token on the lane) -> the float32 image -> rows
@@ -207,6 +333,8 @@ k_channel_mlp(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf1
             }
             wave_sync();
         }
+        RCX_MLP_STAMP(5)
+        RCX_MLP_STAMP_END(blockIdx.x * NW + wave)
         return;
     }
     // ---- three output tiles or more (C = 80, 96): the weights take the LDS the images would need; a token per lane straight from / to memory
@@ -264,6 +392,7 @@ __global__ void __launch_bounds__(64 * NW, WPS)
 k_channel_mlp_stream(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf16_t* __restrict__ y, const u32x4q* __restrict__ wfrag, const float* __restrict__ bias,
                      int M, int C, int nblocks)
 {
+    RCX_MLP_STAMP_BEGIN                                                               // (the diagnostic build: never written out for this kernel)
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     constexpr int NCH = KS1 + 2 * CT, NT = 64 * NW, PER = (NCH * 64 + NT - 1) / NT;          // fragments per chunk; 16-byte pieces of a chunk per thread (the last one ragged)
     constexpr bool RAG = NCH * 64 % NT != 0;
@@ -349,11 +478,11 @@ k_channel_mlp_stream(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
                     for (int j = 0; j < 4; ++j)
                         xq[hf][j] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(xsrc, (int)(128u * hf + ht_b < RB ? base + (8u * j + ht_tok) * RB + 128u * hf + ht_b : 0x80000000u), 0, 0));
             }
-            hidden_tile_ring<KS1, CT, (NW > 4 || KS1 > 16 ? 4 : 8)>(Lring, Lb1 + 32 * ht, lane, h, zb, d2);                               // chunk ht: slot 0
+            hidden_tile_ring<KS1, CT, (NW > 4 || KS1 > 16 ? 4 : 8)>(Lring, Lb1 + 32 * ht, lane, h, zb, d2 RCX_MLP_STAMP_PASS);                               // chunk ht: slot 0
             deposit(cp[1], 1);                                                                                  // chunk ht + 1
             __syncthreads();                      // every wave is done with slot 0; slot 1 is complete
             request(cp[1], (ht + 3) % HT);
-            hidden_tile_ring<KS1, CT, (NW > 4 || KS1 > 16 ? 4 : 8)>(Lring + NCH * 64, Lb1 + 32 * (ht + 1), lane, h, zb, d2);              // chunk ht + 1: slot 1
+            hidden_tile_ring<KS1, CT, (NW > 4 || KS1 > 16 ? 4 : 8)>(Lring + NCH * 64, Lb1 + 32 * (ht + 1), lane, h, zb, d2 RCX_MLP_STAMP_PASS);              // chunk ht + 1: slot 1
             deposit(cp[0], 0);                                                                                  // chunk ht + 2 (the next block's chunk 0 after the last)
             __syncthreads();
         }
@@ -398,10 +527,10 @@ k_channel_mlp_stream(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
 // in quarters of one output tile (32 channels).  Ring: chunk ht lands in slot (step % 3) two steps ahead of its use; each step waits for its own chunk's DMAs
 // (counted vmcnt: the next chunk's stay in flight), then one barrier -- every wave's pieces have landed and every wave is done with the slot of the step before,
 // which then takes the chunk two ahead.  Raw s_barrier: __syncthreads() would wait for the DMAs in flight as well.
-template <int KS1, int HT, int CT>
+template <int KS1, int HT, int CT, bool PIN>
 __global__ void __launch_bounds__(512, 2)
 k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf16_t* __restrict__ y, const u32x4q* __restrict__ wfrag, const float* __restrict__ bias,
-                   int M, int C, int nblocks)
+                   int M, int C, int nblocks RCX_MLP_STAMP_ARG)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     constexpr int NW = 8, NT = 64 * NW, NS = 3, NCH = KS1 + 2 * CT, PER = NCH * 64 / NT;   // PER: 1-KB DMA pieces of a chunk per wave
@@ -414,13 +543,25 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(wave);
     unsigned char* const Lt = lds_raw + (size_t)NS * NCH * 1024 + sizeof(float) * 32 * (HT + CT) + (size_t)wv * IMG;
-    // chunk -> ring slot: piece i of wave w = bytes [1024 (8 i + w), + 1024) of the chunk, lane-linear in LDS as in the pack
+    // chunk -> ring slot: piece i of wave w = bytes [1024 (8 i + w), + 1024) of the chunk, lane-linear in LDS as in the pack.
+    // PIN: the DMA instruction is issued from inline asm (M0 = the piece's LDS address, saved and restored).  The compiler's wait insertion books the builtin as
+    // a FLAT access that may touch LDS and, while one is in flight -- here: always, the next chunk's -- turns EVERY wait for an LDS read into lgkmcnt(0): the full
+    // drains of hidden_tile_ring's listing.  Out of its sight the waits are counted.  Its vmcnt for the z / x loads only grows stricter by DMAs it does not see
+    // (memory operations complete in order), and the ring's own waits are the counted ones below, as before.
     auto fill = [&](int chunk, int slot) {
         const u32x4q* src = wfrag + (size_t)chunk * NCH * 64 + threadIdx.x;
         u32x4q* dst = Lring + (size_t)slot * NCH * 64 + wv * 64;
+        if constexpr (PIN) {
+            const unsigned l0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)dst;
+            unsigned m0_;
 #pragma unroll
-        for (int i = 0; i < PER; ++i)
-            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(src + i * NT), (__attribute__((address_space(3))) void*)(dst + i * NT), 16, 0, 0);
+            for (int i = 0; i < PER; ++i)
+                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(m0_) : "v"(src + i * NT), "s"(l0 + 16u * i * NT) : "memory");
+        } else {
+#pragma unroll
+            for (int i = 0; i < PER; ++i)
+                __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(src + i * NT), (__attribute__((address_space(3))) void*)(dst + i * NT), 16, 0, 0);
+        }
     };
     constexpr int VM_ALL = 0x70, VM_NEXT = 0x70 | (PER & 15) | ((PER >> 4) << 14);   // s_waitcnt: lgkmcnt(0) with vmcnt(0) / vmcnt(PER)
     fill(0, 0);
@@ -439,6 +580,7 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
     // matrix pipe idle.  One of them at a higher priority takes the pipe first, so the other's first product runs under its GELU and its second product under the
     // other's GELU.  (Waves 0, 3, 5, 6: one of each pair whether the SIMDs take the waves round robin -- pairs w, w + 4 -- or in pairs -- 2 i, 2 i + 1.)
     if (!(__builtin_popcount(wv) & 1)) __builtin_amdgcn_s_setprio(1);
+    RCX_MLP_STAMP_BEGIN
     int slot = 0;                                                              // the ring slot of the current step's chunk
     for (int block = blockIdx.x; block < nblocks; block += gridDim.x) {
         const unsigned base = (unsigned)(32 * (block * NW + wave)) * (unsigned)RB;    // (tokens past M: past the buffer -- reads 0, stores dropped)
@@ -464,6 +606,7 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int i = 0; i < 16; ++i) d2[ct][i] = 0.f;
+        RCX_MLP_STAMP(5)
 #pragma unroll 1
         for (int ht = 0; ht < HT; ++ht) {
             // chunk ht + 1's pieces (requested in the step before) are the only younger ones -- unless that step had no chunk to request
@@ -471,7 +614,15 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
             else __builtin_amdgcn_s_waitcnt(VM_ALL);
             __builtin_amdgcn_s_barrier();
             if (ht + 2 < HT || more) fill((ht + 2) % HT, slot == 0 ? 2 : slot - 1);   // the chunk two ahead (the next block's first two after the last), into the slot of the step before
-            hidden_tile_ring<KS1, CT, 4>(Lring + (size_t)slot * NCH * 64, Lb1 + 32 * ht, lane, h, zb, d2);
+            RCX_MLP_STAMP(4)
+            if constexpr (PIN) {
+                // the registers are the budget: next to d2 (128) and the z fragments (64) the GELU's batch of four pairs leaves room for ONE W2 fragment in
+                // flight across it (two: 16 bytes of scratch, four: 48), and the b1 quads go out in front of D1's last three products, when a ring slot is
+                // free (four: 8 bytes of scratch).  The chunk of step ht + 1 lands only at the barrier, so the ring starts empty in every step.
+                hidden_tile_pinned<KS1, CT, 4, 1, 3>(Lring + (size_t)slot * NCH * 64, Lb1 + 32 * ht, lane, h, zb, d2 RCX_MLP_STAMP_PASS);
+            } else
+                hidden_tile_ring<KS1, CT, 4>(Lring + (size_t)slot * NCH * 64, Lb1 + 32 * ht, lane, h, zb, d2 RCX_MLP_STAMP_PASS);
+            RCX_MLP_STAMP_STEP
             slot = slot == NS - 1 ? 0 : slot + 1;
         }
         u32x4q xq[CT][2];                                                          // the residual: requested after the products (its registers were the z fragments')
@@ -504,6 +655,8 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
             wave_sync();
         }
     }
+    RCX_MLP_STAMP(5)
+    RCX_MLP_STAMP_END(blockIdx.x * NW + wv)
 }
 
 
@@ -518,7 +671,7 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
 template <int KS1, int HT, int CT, int OC, bool PRIO>
 __global__ void __launch_bounds__(512, 2)
 k_channel_mlp_res128(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf16_t* __restrict__ y, const u32x4q* __restrict__ wfrag, const float* __restrict__ bias,
-                     int M, int ntiles)
+                     int M, int ntiles RCX_MLP_STAMP_ARG)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     constexpr int NW = 8, NT = 64 * NW, NCH = KS1 + 2 * CT, NF = HT * NCH, PER = NF * 64 / NT;   // PER: 1-KB DMA pieces of the pack per wave
@@ -563,6 +716,7 @@ k_channel_mlp_res128(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
     __builtin_amdgcn_s_waitcnt(0x70);                                            // vmcnt(0) lgkmcnt(0): this wave's pieces of the pack have landed
     __syncthreads();                                                             // the only barrier: a wave without a tile leaves right after it
     if (PRIO && !(__builtin_popcount(wv) & 1)) __builtin_amdgcn_s_setprio(1);
+    RCX_MLP_STAMP_BEGIN
     for (; tile < ntiles; tile += stride) {
         const unsigned base = (unsigned)tile * 32u * RB;
         bf16x8 zb[KS1];
@@ -581,8 +735,12 @@ k_channel_mlp_res128(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int i = 0; i < 16; ++i) d2[ct][i] = 0.f;
+        RCX_MLP_STAMP(5)
 #pragma unroll 1
-        for (int ht = 0; ht < HT; ++ht) hidden_tile_ring<KS1, CT, 4>(Lf + (size_t)ht * NCH * 64, Lb1 + 32 * ht, lane, h, zb, d2);
+        for (int ht = 0; ht < HT; ++ht) {
+            hidden_tile_ring<KS1, CT, 4>(Lf + (size_t)ht * NCH * 64, Lb1 + 32 * ht, lane, h, zb, d2 RCX_MLP_STAMP_PASS);
+            RCX_MLP_STAMP_STEP
+        }
         u32x4q xq[NG][NP];                                                       // the residual: requested after the products
 #pragma unroll
         for (int k = 0; k < NG; ++k)
@@ -617,6 +775,8 @@ k_channel_mlp_res128(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
                 wave_sync();
             }
     }
+    RCX_MLP_STAMP(5)
+    RCX_MLP_STAMP_END(wv * (int)gridDim.x + (int)blockIdx.x)
 }
 
 
@@ -891,7 +1051,7 @@ static hipError_t launch_mlp(const void* z, const void* x, void* y, const void* 
     const int ntiles = (M + 31) / 32;
     int grid = ncu;
     if (grid * NW > ntiles) grid = (ntiles + NW - 1) / NW;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * NW), lds + stage, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, C, ntiles);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * NW), lds + stage, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, C, ntiles RCX_MLP_STAMP_VAL);
     return hipGetLastError();
 }
 
@@ -919,11 +1079,11 @@ static hipError_t launch_mlp_pair256(const void* z, const void* x, void* y, cons
     constexpr size_t lds = (size_t)3 * NCH * 1024 + sizeof(float) * 32 * (HT + CT) + (size_t)8 * IMG;
     static_assert(lds <= 160 * 1024, "the ring and the waves' images must fit the LDS");
     if (C != 16 * KS1) return hipErrorInvalidConfiguration;
-    auto kfn = mlp::k_channel_mlp_pair<KS1, HT, CT>;
+    auto kfn = mlp::k_channel_mlp_pair<KS1, HT, CT, RCX_MLP_PINNED>;
     RCX_SET_LDS_ONCE(kfn, lds);
     const int nblocks = (M + 255) / 256;
     const int grid = nblocks < ncu ? nblocks : ncu;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(512), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, C, nblocks);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(512), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, C, nblocks RCX_MLP_STAMP_VAL);
     return hipGetLastError();
 }
 
@@ -945,7 +1105,7 @@ static hipError_t launch_mlp_res128(const void* z, const void* x, void* y, const
     const int ntiles = (M + 31) / 32;
     int grid = (ntiles + NW - 1) / NW;
     if (grid > ncu) grid = ncu;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * NW), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, ntiles);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * NW), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, ntiles RCX_MLP_STAMP_VAL);
     return hipGetLastError();
 }
 
@@ -997,3 +1157,12 @@ hipError_t channel_mlp(const void* z, const void* x, void* y, const void* wfrag,
 }
 
 }  // namespace rcx
+
+#ifdef RCX_MLP_STAMPS
+// the diagnostic build: this translation unit alone as a shared object (tools/mlp_timeline.py); stamps = [wave slot][8] cycle sums, wave slots as the kernels number them
+extern "C" int rcx_mlp_diag_fwd(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, int H, void* stamps, void* stream)
+{
+    rcx::g_stamps = (unsigned long long*)stamps;
+    return (int)rcx::channel_mlp(z, x, y, wfrag, bias, M, C, H, 1, (hipStream_t)stream);
+}
+#endif

@@ -135,7 +135,7 @@ for i, l in enumerate(lines):
             del flight[r]
     if op.startswith(VMEM):
         issued += 1
-        if in_asm and "load" in op and " lds" not in args:
+        if in_asm and "load" in op and " lds" not in args and "_lds_" not in op:       # (LDS-DMA, either spelling: its first operand is the address, no register is written)
             dst = args.split(",")[0]
             for r in vregs(dst):
                 flight[r] = (issued, i + 1)

@@ -24,13 +24,15 @@ first = marks[-need - 1] + 1            # right after the last marker launch of 
 last = marks[-1]
 win = rows[first:last + 1]
 span = (int(win[-1]["End_Timestamp"]) - int(win[0]["Start_Timestamp"])) / a.steps / 1e3
-agg = collections.defaultdict(lambda: [0, 0])
+agg = collections.defaultdict(lambda: [0, 0, 1 << 62, 0])          # total ns, launches, shortest and longest launch of the window
 for r in win:
     d = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
     k = r["Kernel_Name"]
     agg[k][0] += d
     agg[k][1] += 1
+    agg[k][2] = min(agg[k][2], d)
+    agg[k][3] = max(agg[k][3], d)
 busy = sum(v[0] for v in agg.values()) / a.steps / 1e3
 print(f"window: {a.steps} steps, {span:.1f} us per step wall (marker to marker), {busy:.1f} us per step of kernel time, {len(win) / a.steps:.1f} launches per step")
-for k, (d, c) in sorted(agg.items(), key=lambda kv: -kv[1][0])[:a.top]:
-    print(f"{d / a.steps / 1e3:9.1f} us/step {c / a.steps:7.1f} x {d / c / 1e3:8.1f} us  {k[:150]}")
+for k, (d, c, lo, hi) in sorted(agg.items(), key=lambda kv: -kv[1][0])[:a.top]:
+    print(f"{d / a.steps / 1e3:9.1f} us/step {c / a.steps:7.1f} x {d / c / 1e3:8.1f} us (min {lo / 1e3:6.1f}, max {hi / 1e3:6.1f})  {k[:150]}")
