@@ -12,10 +12,16 @@
 //   D2 += W2[:][32 ht ..] h                                      ... the second product, with W2's columns stored in the order the registers imply
 //   y   = D2 + b2 + x                                            8-byte loads / stores of four channels per lane (token on the lane)
 // The weights are ready-made fragments (one conflict-free 16-byte LDS read per lane and product), packed once on the host (ops.pack_channel_mlp), hidden tile by
-// hidden tile: resident in LDS for C <= 128 (k_channel_mlp; C = 128: k_channel_mlp_res128, free-running waves), streamed through a two-slot LDS ring for C = 160 .. 320 (k_channel_mlp_stream, further down; C = 256: k_channel_mlp_pair, two waves per SIMD).  Global
-// accesses are whole-wave contiguous kilobytes, transposed to / from the token-on-lane layouts in per-wave LDS images (measurements: profiles/r05_channel_mlp.txt).
+// hidden tile: resident in LDS for C <= 128 (k_channel_mlp; C = 128: k_channel_mlp_res128, free-running waves), streamed through a two-slot LDS ring for
+// C = 160 .. 320 (k_channel_mlp_stream; C = 256: k_channel_mlp_pair, two waves per SIMD), read straight from global memory by the wave that owns them for
+// C = 384 / 512 (k_channel_mlp_wide).  Global accesses are whole-wave contiguous kilobytes, transposed to / from the token-on-lane layouts in per-wave LDS
+// images (measurements: profiles/r05_channel_mlp.txt).
 // GELU is the exact form 0.5 v (1 + erf(v / sqrt 2)) with erf as an odd degree-15 polynomial of the argument clamped to +-2.8: |error| < 7.7e-5 in erf, i.e. 4e-5 |v|
 // in gelu -- a fiftieth of a bf16 ulp; the library's erff would be most of this kernel's vector work.
+// The file: the text all forms share and each form's LDS layout (one struct, read by the kernel and by its launcher); the hidden step; the five kernels, each its
+// schedule and nothing else; a launcher per form; MLP_ROWS, the one table of the shapes that have a kernel, which channel_mlp_applicable and channel_mlp both read.
+// No kernel-side piece is shared at the cost of a kernel's schedule: the compiler's schedule for these kernels depends on how the source is factored, so a piece
+// is a function where the device listing stayed the same and a macro where a function moved it.
 #include "rcx_common.h"
 #include "rcx_launch.h"
 #include "rcx_gelu.h"
@@ -87,18 +93,100 @@ __device__ __forceinline__ void wave_sync()
 }
 // (row of accumulator register i in lane half h of a 32 x 32 tile: (i & 3) + 8 (i >> 2) + 4 h -- ops.py::_mlp_acc_unit orders W2's columns by it)
 
-// The middle of a hidden tile, ONE text for both forms of the step below so that they cannot drift apart: h = 2 gelu(D1 + b1) in float32, rounded to bf16 -- with
-// D1's accumulator layout already the second product's two B operands.  Declares hb[2]; QUAD: the lane's b1 quad g (units 8 g + 4 h ..), read from LDS on the spot
+// ---- the text every kernel form shares.  Each piece is here only because the device listing of every kernel stayed the same, instruction for instruction, when
+// the in-place text became a call (or, where a call moved the schedule, a macro)
+
+// z, x and y as buffers of M token rows (nbytes < 2^31, checked by the launcher): a token past M reads 0 and its stores are dropped; an offset with bit 31 set is
+// out of range whatever the token
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t token_rows(const void* p, unsigned nbytes) { return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, nbytes, 0x00020000); }
+
+// Accumulators D[N] = 0.  A macro: as a function it moved the listings of the stream, pair and wide kernels (other registers, another order)
+#define RCX_MLP_ZERO(D, N)                                                                                                                \
+    _Pragma("unroll") for (int n_ = 0; n_ < N; ++n_) _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) D[n_][i_] = 0.f;
+
+// The tokens' channels zq[KS1] -> the first product's B operands zb[KS1] through the wave's image Lt (rows of ZP bytes), in ZH column parts of KH = KS1 / ZH
+// k-steps: request i of part q goes to byte ZA (an expression in q and i) of the image, then lane (r, h) reads k-step k of its token's row back.  A macro over
+// the kernel's own names: as a function taking ZA as a lambda it moved the listings of the pair kernel and two stream kernels
+#define RCX_MLP_STAGE_Z(ZA)                                                                                                               \
+    _Pragma("unroll") for (int q = 0; q < ZH; ++q) {                                                                                      \
+        _Pragma("unroll") for (int i = 0; i < KH; ++i) *reinterpret_cast<u32x4q*>(Lt + (ZA)) = zq[q * KH + i];                            \
+        wave_sync();                                                                                                                      \
+        _Pragma("unroll") for (int k = 0; k < KH; ++k)                                                                                    \
+            zb[q * KH + k] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4q*>(Lt + r * ZP + 32 * k + 16 * h));                 \
+        wave_sync();                                                                                                                      \
+    }
+
+// Four accumulators of a lane (register group g of D2: its token's channels 8 g + 4 h .. + 3 of an output tile) + b2 -> the float32 image.  A macro: as a function
+// it moved the listings of the stream, pair and wide kernels
+#define RCX_MLP_IMAGE_QUAD(D2, B2, DST)                                                                                                   \
+    {                                                                                                                                     \
+        const f32x4q bb = *reinterpret_cast<const f32x4q*>(B2);                                                                           \
+        *reinterpret_cast<f32x4q*>(DST) = f32x4q{D2[4 * g] + bb.x, D2[4 * g + 1] + bb.y, D2[4 * g + 2] + bb.z, D2[4 * g + 3] + bb.w};     \
+    }
+
+// 8 channels of a token's row: the float32 image's (lo, hi) + the residual's (bf16 pairs), rounded once
+__device__ __forceinline__ bf16x8 rows_plus_x(f32x4q lo, f32x4q hi, u32x4q xv)
+{
+    bf16x8 o;
+    o[0] = (__bf16)(lo.x + __uint_as_float(xv.x << 16)); o[1] = (__bf16)(lo.y + __uint_as_float(xv.x & 0xffff0000u));
+    o[2] = (__bf16)(lo.z + __uint_as_float(xv.y << 16)); o[3] = (__bf16)(lo.w + __uint_as_float(xv.y & 0xffff0000u));
+    o[4] = (__bf16)(hi.x + __uint_as_float(xv.z << 16)); o[5] = (__bf16)(hi.y + __uint_as_float(xv.z & 0xffff0000u));
+    o[6] = (__bf16)(hi.z + __uint_as_float(xv.w << 16)); o[7] = (__bf16)(hi.w + __uint_as_float(xv.w & 0xffff0000u));
+    return o;
+}
+
+// ---- the dynamic LDS of every form, ONE statement for the kernel (offsets) and its launcher (bytes):
+//     [weights: the resident pack | the ring of chunks | wide: the B operands]  [b1: 32 HT floats] [b2: 32 CT floats]  [NW per-wave images of IMG bytes]
+// The pack: per hidden tile its KS1 W1 fragments and 2 CT W2 fragments (1 KB each: 64 lanes x 16 bytes; ops.pack_channel_mlp).  An image holds a wave's 32 tokens
+// as rows, the bf16 z (pitch ZP) and then the float32 output (pitch OP) -- 16 bytes of padding a row: banks
+constexpr int imax(int a, int b) { return a > b ? a : b; }
+constexpr size_t bias_bytes(int HT, int CT) { return sizeof(float) * 32 * (HT + CT); }
+
+// k_channel_mlp: the pack resident; images of whole rows, only where STAGED
+template <int KS1, int HT, int CT, int NW, bool STAGED>
+struct SmallLds {
+    static constexpr int NF = HT * (KS1 + 2 * CT), ZP = 32 * KS1 + 16, OP = 128 * CT + 16, IMG = STAGED ? 32 * imax(ZP, OP) : 0;
+    static constexpr size_t b1 = (size_t)NF * 1024, images = b1 + bias_bytes(HT, CT), bytes = images + (size_t)NW * IMG;
+};
+// k_channel_mlp_stream: a ring of two chunks; z rows in ZH column parts, the output in halves of two tiles (64 channels)
+template <int KS1, int HT, int CT, int NW, int ZH>
+struct StreamLds {
+    static constexpr int NCH = KS1 + 2 * CT, ZP = 32 * KS1 / ZH + 16, OP = 256 + 16, IMG = 32 * imax(ZP, OP);
+    static constexpr size_t b1 = (size_t)2 * NCH * 1024, images = b1 + bias_bytes(HT, CT), bytes = images + (size_t)NW * IMG;
+};
+// k_channel_mlp_pair: a ring of NS = 3 chunks, 8 waves; z in four column parts, the output one tile (32 channels) at a time
+template <int KS1, int HT, int CT>
+struct PairLds {
+    static constexpr int NW = 8, NS = 3, ZH = 4, NCH = KS1 + 2 * CT, ZP = 32 * KS1 / ZH + 16, OP = 128 + 16, IMG = 32 * imax(ZP, OP);
+    static constexpr size_t b1 = (size_t)NS * NCH * 1024, images = b1 + bias_bytes(HT, CT), bytes = images + (size_t)NW * IMG;
+};
+// k_channel_mlp_res128: the pack resident, 8 waves; z in four column parts, the output in pieces of OC = 16 channels of all 32 tokens
+template <int KS1, int HT, int CT>
+struct Res128Lds {
+    static constexpr int NW = 8, ZH = 4, NCH = KS1 + 2 * CT, NF = HT * NCH, ZP = 32 * KS1 / ZH + 16, OC = 16, OP = 4 * OC + 16, IMG = 32 * imax(ZP, OP);
+    static constexpr size_t b1 = (size_t)NF * 1024, images = b1 + bias_bytes(HT, CT), bytes = images + (size_t)NW * IMG;
+};
+// k_channel_mlp_wide: z as B fragments (two token tiles x KS1 KB), then two exchange buffers of NW hidden tiles x 4 KB; the output images (32 tokens x 64 channels
+// per wave, from offset 0) alias the z fragments and exchange buffer 0, so they add nothing to the total
+template <int KS1, int HT, int CT, int NW>
+struct WideLds {
+    static constexpr int ZBYTES = 2 * KS1 * 1024, XBYTES = NW * 4 * 1024, OP = 256 + 16, IMG = 32 * OP;
+    static constexpr size_t xchg = ZBYTES, b1 = (size_t)ZBYTES + 2 * XBYTES, bytes = b1 + bias_bytes(HT, CT);
+    static_assert(NW * IMG <= ZBYTES + XBYTES, "the output images alias the z fragments and exchange buffer 0");
+};
+
+// The middle of a hidden tile, ONE text for both forms of the step below and for k_channel_mlp_wide, so that they cannot drift apart: h = 2 gelu(D1 + b1) in float32, rounded to bf16 -- with
+// D1's accumulator layout already the second product's two B operands.  Declares hb[2]; D1: the first product's accumulators; QUAD: the lane's b1 quad g (units 8 g + 4 h ..), read from LDS on the spot
 // (hidden_tile_ring) or requested earlier (hidden_tile_pinned).  A macro, not a function: through a helper the compiler scheduled the kernels that keep
 // hidden_tile_ring's form differently from the parent's listing; expanded in place their code is the parent's, instruction for instruction.
 // The tile's 16 values go four pairs in lockstep at a time (eight: the kernels at their register limit spill); TWICE the GELU -- W2 is stored halved (ops.pack_channel_mlp).
-#define RCX_MLP_HIDDEN_GELU(QUAD)                                                                                                         \
+#define RCX_MLP_HIDDEN_GELU(D1, QUAD)                                                                                                     \
     bf16x8 hb[2];                                                                                                                         \
     gelu_f32x2 gv[8];                                                                                                                     \
     _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                                                       \
         const f32x4q bb = QUAD;                                                                                                           \
-        gv[2 * g] = gelu_f32x2{d1[4 * g] + bb.x, d1[4 * g + 1] + bb.y};                                                                   \
-        gv[2 * g + 1] = gelu_f32x2{d1[4 * g + 2] + bb.z, d1[4 * g + 3] + bb.w};                                                           \
+        gv[2 * g] = gelu_f32x2{D1[4 * g] + bb.x, D1[4 * g + 1] + bb.y};                                                                   \
+        gv[2 * g + 1] = gelu_f32x2{D1[4 * g + 2] + bb.z, D1[4 * g + 3] + bb.w};                                                           \
     }                                                                                                                                     \
     {                                                                                                                                     \
         gelu_f32x2 ga[4] = {gv[0], gv[1], gv[2], gv[3]}, gb[4] = {gv[4], gv[5], gv[6], gv[7]};                                            \
@@ -143,7 +231,7 @@ __device__ __forceinline__ void hidden_tile_ring(const u32x4q* Lc, const float* 
 #pragma unroll
     for (int f = 0; f < R2; ++f) ring[f] = Lc[(KS1 + 2 * (f % CT) + f / CT) * 64 + lane];
 #endif
-    RCX_MLP_HIDDEN_GELU(*reinterpret_cast<const f32x4q*>(b1t + 8 * g + 4 * h))
+    RCX_MLP_HIDDEN_GELU(d1, *reinterpret_cast<const f32x4q*>(b1t + 8 * g + 4 * h))
 #ifdef RCX_MLP_STAMPS
 #pragma unroll
     for (int f = 0; f < R2; ++f) ring[f] = Lc[(KS1 + 2 * (f % CT) + f / CT) * 64 + lane];
@@ -199,7 +287,7 @@ __device__ __forceinline__ void hidden_tile_pinned(const u32x4q* Lc, const float
 #pragma unroll
     for (int f = 0; f < P2; ++f) ring[f] = Lc[(KS1 + 2 * (f % CT) + f / CT) * 64 + lane];
     __builtin_amdgcn_sched_barrier(0);
-    RCX_MLP_HIDDEN_GELU(bq[g])
+    RCX_MLP_HIDDEN_GELU(d1, bq[g])
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int f = P2; f < R2; ++f) ring[f] = Lc[(KS1 + 2 * (f % CT) + f / CT) * 64 + lane];
@@ -215,8 +303,6 @@ __device__ __forceinline__ void hidden_tile_pinned(const u32x4q* Lc, const float
     RCX_MLP_STAMP(3)
 }
 
-// LDS: per hidden tile ht its KS1 W1 fragments and 2 CT W2 fragments (1 KB each: 64 lanes x 16 bytes; ops.pack_channel_mlp), then b1 (32 HT floats), b2 (32 CT floats)
-
 // KS1 = ceil(C / 16) k-steps of the first product, HT = H / 32 hidden tiles, CT = ceil(C / 32) output tiles; C % 8 == 0 (a lane's 8 channels of a k-step are
 // all there or all padding).  NW waves per workgroup share the LDS weights; each takes every (grid x NW)-th 32-token tile.
 // KX / OX: C == 16 KS1 / C == 32 CT exactly -- no padding lanes, so a lane's offsets are one register plus immediates
@@ -226,22 +312,21 @@ k_channel_mlp(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf1
               int M, int C, int ntiles RCX_MLP_STAMP_ARG)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    constexpr int NF = HT * KS1 + CT * 2 * HT;
+    using L = SmallLds<KS1, HT, CT, NW, STAGED>;
+    constexpr int NF = L::NF;
     const u32x4q* const Lf = reinterpret_cast<const u32x4q*>(lds_raw);
-    const float* const Lb1 = reinterpret_cast<const float*>(lds_raw + (size_t)NF * 1024);
+    const float* const Lb1 = reinterpret_cast<const float*>(lds_raw + L::b1);
     const float* const Lb2 = Lb1 + 32 * HT;
     {
         u32x4q* Lw = reinterpret_cast<u32x4q*>(lds_raw);
         for (int i = threadIdx.x; i < NF * 64; i += 64 * NW) Lw[i] = wfrag[i];
-        float* Lb = reinterpret_cast<float*>(lds_raw + (size_t)NF * 1024);
+        float* Lb = reinterpret_cast<float*>(lds_raw + L::b1);
         for (int i = threadIdx.x; i < 32 * (HT + CT); i += 64 * NW) Lb[i] = bias[i];
     }
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    const unsigned nbytes = (unsigned)M * (unsigned)C * 2u;                  // < 2^31 (checked by the launcher): an offset with bit 31 set is out of range whatever the token
-    const __amdgpu_buffer_rsrc_t zsrc = __builtin_amdgcn_make_buffer_rsrc((void*)z, 0, nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xres, 0, nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, nbytes, 0x00020000);
+    const unsigned nbytes = (unsigned)M * (unsigned)C * 2u;
+    const __amdgpu_buffer_rsrc_t zsrc = token_rows(z, nbytes), xsrc = token_rows(xres, nbytes), ysrc = token_rows(y, nbytes);
     // the lane's part of its offsets: 8 channels of k-step ks (reads of z), 4 channels of output group (ct, g) (reads of x, stores of y); padding: bit 31
     unsigned zk[KS1], oc[CT][4];
 #pragma unroll
@@ -263,9 +348,8 @@ k_channel_mlp(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf1
         // ---- two output tiles or fewer (C <= 64): every global access is a whole-wave contiguous kilobyte, the token-on-lane layouts the products need are made in
         // LDS.  (Reading z / x and writing y a token per lane costs the CU's address path 64 cycles a request -- 32 lines touched, 16 or 8 bytes each: 77 us of the
         // 114 us this kernel took that way at 256 x 64 x 56 x 56, profiles/r05_channel_mlp.txt.)  A wave's tile: 32 tokens = 32 RB contiguous bytes.
-        constexpr int ZP = 32 * KS1 + 16, OP = 128 * CT + 16;                 // bytes per token row: bf16 z image, float32 output image (16 bytes of padding: banks)
-        constexpr int WREG = 32 * (ZP > OP ? ZP : OP);
-        unsigned char* const Lt = lds_raw + (size_t)NF * 1024 + sizeof(float) * 32 * (HT + CT) + (size_t)wave * WREG;
+        constexpr int ZP = L::ZP, OP = L::OP;                                 // bytes per token row: bf16 z image, float32 output image
+        unsigned char* const Lt = lds_raw + L::images + (size_t)wave * L::IMG;
         const unsigned RB = 2u * (unsigned)C;
         unsigned go[KS1], za[KS1], oa[KS1];                                   // request i of a tile: bytes [1024 i + 16 lane, + 16) of it -> token t, byte b of its row
         bool live[KS1];
@@ -302,10 +386,7 @@ k_channel_mlp(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf1
 #pragma unroll
             for (int i = 0; i < KS1; ++i) xq[i] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(xsrc, (int)(base + go[i]), 0, 0));
             f32x16 d2[CT];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) d2[ct][i] = 0.f;
+            RCX_MLP_ZERO(d2, CT)
             RCX_MLP_STAMP(5)
 #pragma unroll 1
             for (int ht = 0; ht < HT; ++ht) hidden_tile(ht, zb, d2);
@@ -313,23 +394,13 @@ k_channel_mlp(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf1
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + 32 * ct + 8 * g + 4 * h);
-                    *reinterpret_cast<f32x4q*>(Lt + r * OP + 4 * (32 * ct + 8 * g + 4 * h)) =
-                        f32x4q{d2[ct][4 * g] + bb.x, d2[ct][4 * g + 1] + bb.y, d2[ct][4 * g + 2] + bb.z, d2[ct][4 * g + 3] + bb.w};
-                }
+                for (int g = 0; g < 4; ++g) RCX_MLP_IMAGE_QUAD(d2[ct], Lb2 + 32 * ct + 8 * g + 4 * h, Lt + r * OP + 4 * (32 * ct + 8 * g + 4 * h))
             wave_sync();
 #pragma unroll
             for (int i = 0; i < KS1; ++i) {
                 if (!live[i]) continue;
                 const f32x4q lo = *reinterpret_cast<const f32x4q*>(Lt + oa[i]), hi = *reinterpret_cast<const f32x4q*>(Lt + oa[i] + 16);
-                const u32x4q xv = xq[i];
-                bf16x8 o;
-                o[0] = (__bf16)(lo.x + __uint_as_float(xv.x << 16)); o[1] = (__bf16)(lo.y + __uint_as_float(xv.x & 0xffff0000u));
-                o[2] = (__bf16)(lo.z + __uint_as_float(xv.y << 16)); o[3] = (__bf16)(lo.w + __uint_as_float(xv.y & 0xffff0000u));
-                o[4] = (__bf16)(hi.x + __uint_as_float(xv.z << 16)); o[5] = (__bf16)(hi.y + __uint_as_float(xv.z & 0xffff0000u));
-                o[6] = (__bf16)(hi.z + __uint_as_float(xv.w << 16)); o[7] = (__bf16)(hi.w + __uint_as_float(xv.w & 0xffff0000u));
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, o), ysrc, (int)(base + go[i]), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, rows_plus_x(lo, hi, xq[i])), ysrc, (int)(base + go[i]), 0, 0);
             }
             wave_sync();
         }
@@ -352,10 +423,7 @@ k_channel_mlp(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf1
         for (int ks = 0; ks < KS1; ++ks) zb[ks] = __builtin_bit_cast(bf16x8, zf[ks]);
         if (tile + stride < ntiles) load_z(tile + stride);                    // the next tile's channels: in flight during this tile's products
         f32x16 d2[CT];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) d2[ct][i] = 0.f;
+        RCX_MLP_ZERO(d2, CT)
 #pragma unroll 1
         for (int ht = 0; ht < HT; ++ht) hidden_tile(ht, zb, d2);
         u32x2q xr[CT][4];                                                    // the residual (requested after the products: until here its registers are the accumulators')
@@ -394,17 +462,16 @@ k_channel_mlp_stream(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
 {
     RCX_MLP_STAMP_BEGIN                                                               // (the diagnostic build: never written out for this kernel)
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    constexpr int NCH = KS1 + 2 * CT, NT = 64 * NW, PER = (NCH * 64 + NT - 1) / NT;          // fragments per chunk; 16-byte pieces of a chunk per thread (the last one ragged)
+    using L = StreamLds<KS1, HT, CT, NW, ZH>;
+    constexpr int NCH = L::NCH, NT = 64 * NW, PER = (NCH * 64 + NT - 1) / NT;                // fragments per chunk; 16-byte pieces of a chunk per thread (the last one ragged)
     constexpr bool RAG = NCH * 64 % NT != 0;
     u32x4q* const Lring = reinterpret_cast<u32x4q*>(lds_raw);                        // [2][NCH * 64]
-    float* const Lb1 = reinterpret_cast<float*>(lds_raw + (size_t)2 * NCH * 1024);
+    float* const Lb1 = reinterpret_cast<float*>(lds_raw + L::b1);
     float* const Lb2 = Lb1 + 32 * HT;
     for (int i = threadIdx.x; i < 32 * (HT + CT); i += NT) Lb1[i] = bias[i];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     const unsigned nbytes = (unsigned)M * (unsigned)C * 2u;
-    const __amdgpu_buffer_rsrc_t zsrc = __builtin_amdgcn_make_buffer_rsrc((void*)z, 0, nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xres, 0, nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t zsrc = token_rows(z, nbytes), xsrc = token_rows(xres, nbytes), ysrc = token_rows(y, nbytes);
     // chunk 0 -> ring slot 0; chunk 1 -> the registers of set 1.  In step ht (chunk ht in slot ht & 1) the requests for chunk ht + 2 go out first and land in
     // register set ht & 1, the products run, then set (ht + 1) & 1 -- chunk ht + 1, requested a whole step earlier -- is written to the other slot: the L2 round
     // trip (1.5 - 2 us under this load, longer than a step's products) has two steps to complete.  The chunk sequence is periodic, so it runs across blocks.
@@ -430,8 +497,8 @@ k_channel_mlp_stream(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
     // float32 image of 32 x 64, read back as rows -- request j of half hf = the 128-byte pieces [128 hf, + 128) of 8 token rows.
     static_assert(CT % 2 == 0, "output in halves of two tiles");
     static_assert(KS1 % ZH == 0, "column parts of whole k-steps");
-    constexpr int RB = 32 * KS1, RBH = RB / ZH, KH = KS1 / ZH, ZP = RBH + 16, OP = 256 + 16, IMG = 32 * (ZP > OP ? ZP : OP), NH = CT / 2;
-    unsigned char* const Lt = lds_raw + (size_t)2 * NCH * 1024 + sizeof(float) * 32 * (HT + CT) + (size_t)wave * IMG;
+    constexpr int RB = 32 * KS1, RBH = RB / ZH, KH = KS1 / ZH, ZP = L::ZP, OP = L::OP, NH = CT / 2;
+    unsigned char* const Lt = lds_raw + L::images + (size_t)wave * L::IMG;
     unsigned zo[KS1], za[KS1];                                                  // request i of column part q = i / KH: piece 1024 (i % KH) + 16 lane of that part
 #pragma unroll
     for (int i = 0; i < KS1; ++i) {
@@ -452,21 +519,10 @@ k_channel_mlp_stream(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
         const unsigned base = (unsigned)(32 * (block * NW + wave)) * (unsigned)RB;
         if constexpr (!ZPF) load_z(block);
         bf16x8 zb[KS1];
-#pragma unroll
-        for (int q = 0; q < ZH; ++q) {
-#pragma unroll
-            for (int i = 0; i < KH; ++i) *reinterpret_cast<u32x4q*>(Lt + za[q * KH + i]) = zq[q * KH + i];
-            wave_sync();
-#pragma unroll
-            for (int k = 0; k < KH; ++k) zb[q * KH + k] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4q*>(Lt + r * ZP + 32 * k + 16 * h));
-            wave_sync();
-        }
+        RCX_MLP_STAGE_Z(za[q * KH + i])
         if (ZPF && block + (int)gridDim.x < nblocks) load_z(block + gridDim.x);    // the next block's channels: in flight during this block
         f32x16 d2[CT];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) d2[ct][i] = 0.f;
+        RCX_MLP_ZERO(d2, CT)
         u32x4q xq[NH][4];                                                          // the residual: requested in the last step but one
 #pragma unroll 1
         for (int ht = 0; ht < HT; ht += 2) {
@@ -491,24 +547,13 @@ k_channel_mlp_stream(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
 #pragma unroll
             for (int c2 = 0; c2 < 2; ++c2)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int ct = 2 * hf + c2;
-                    const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + 32 * ct + 8 * g + 4 * h);
-                    *reinterpret_cast<f32x4q*>(Lt + r * OP + 4 * (32 * c2 + 8 * g + 4 * h)) =
-                        f32x4q{d2[ct][4 * g] + bb.x, d2[ct][4 * g + 1] + bb.y, d2[ct][4 * g + 2] + bb.z, d2[ct][4 * g + 3] + bb.w};
-                }
+                for (int g = 0; g < 4; ++g) RCX_MLP_IMAGE_QUAD(d2[2 * hf + c2], Lb2 + 32 * (2 * hf + c2) + 8 * g + 4 * h, Lt + r * OP + 4 * (32 * c2 + 8 * g + 4 * h))
             wave_sync();
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const unsigned char* src = Lt + (8 * j + ht_tok) * OP + 2 * ht_b;
                 const f32x4q lo = *reinterpret_cast<const f32x4q*>(src), hi = *reinterpret_cast<const f32x4q*>(src + 16);
-                const u32x4q xv = xq[hf][j];
-                bf16x8 o;
-                o[0] = (__bf16)(lo.x + __uint_as_float(xv.x << 16)); o[1] = (__bf16)(lo.y + __uint_as_float(xv.x & 0xffff0000u));
-                o[2] = (__bf16)(lo.z + __uint_as_float(xv.y << 16)); o[3] = (__bf16)(lo.w + __uint_as_float(xv.y & 0xffff0000u));
-                o[4] = (__bf16)(hi.x + __uint_as_float(xv.z << 16)); o[5] = (__bf16)(hi.y + __uint_as_float(xv.z & 0xffff0000u));
-                o[6] = (__bf16)(hi.z + __uint_as_float(xv.w << 16)); o[7] = (__bf16)(hi.w + __uint_as_float(xv.w & 0xffff0000u));
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, o), ysrc, (int)(128u * hf + ht_b < RB ? base + (8u * j + ht_tok) * RB + 128u * hf + ht_b : 0x80000000u), 0, 0);   // (a half past the row's channels: dropped)
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, rows_plus_x(lo, hi, xq[hf][j])), ysrc, (int)(128u * hf + ht_b < RB ? base + (8u * j + ht_tok) * RB + 128u * hf + ht_b : 0x80000000u), 0, 0);   // (a half past the row's channels: dropped)
             }
             wave_sync();
         }
@@ -533,16 +578,17 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
                    int M, int C, int nblocks RCX_MLP_STAMP_ARG)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    constexpr int NW = 8, NT = 64 * NW, NS = 3, NCH = KS1 + 2 * CT, PER = NCH * 64 / NT;   // PER: 1-KB DMA pieces of a chunk per wave
+    using L = PairLds<KS1, HT, CT>;
+    constexpr int NW = L::NW, NT = 64 * NW, NS = L::NS, NCH = L::NCH, PER = NCH * 64 / NT;   // PER: 1-KB DMA pieces of a chunk per wave
     static_assert(NCH * 64 % NT == 0 && HT >= 2, "whole pieces per wave");
-    constexpr int ZH = 4, RB = 32 * KS1, RBH = RB / ZH, KH = KS1 / ZH, ZP = RBH + 16, OP = 128 + 16, IMG = 32 * (ZP > OP ? ZP : OP);
+    constexpr int ZH = L::ZH, RB = 32 * KS1, RBH = RB / ZH, KH = KS1 / ZH, ZP = L::ZP, OP = L::OP;
     static_assert(KS1 % ZH == 0 && RBH == 128, "column parts of 64 channels: a request = 8 token rows of 128 bytes");
     u32x4q* const Lring = reinterpret_cast<u32x4q*>(lds_raw);                        // [NS][NCH * 64]
-    float* const Lb1 = reinterpret_cast<float*>(lds_raw + (size_t)NS * NCH * 1024);
+    float* const Lb1 = reinterpret_cast<float*>(lds_raw + L::b1);
     const float* const Lb2 = Lb1 + 32 * HT;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(wave);
-    unsigned char* const Lt = lds_raw + (size_t)NS * NCH * 1024 + sizeof(float) * 32 * (HT + CT) + (size_t)wv * IMG;
+    unsigned char* const Lt = lds_raw + L::images + (size_t)wv * L::IMG;
     // chunk -> ring slot: piece i of wave w = bytes [1024 (8 i + w), + 1024) of the chunk, lane-linear in LDS as in the pack.
     // PIN: the DMA instruction is issued from inline asm (M0 = the piece's LDS address, saved and restored).  The compiler's wait insertion books the builtin as
     // a FLAT access that may touch LDS and, while one is in flight -- here: always, the next chunk's -- turns EVERY wait for an LDS read into lgkmcnt(0): the full
@@ -568,9 +614,7 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
     fill(1, 1);
     for (int i = threadIdx.x; i < 32 * (HT + CT); i += NT) Lb1[i] = bias[i];
     const unsigned nbytes = (unsigned)M * (unsigned)C * 2u;
-    const __amdgpu_buffer_rsrc_t zsrc = __builtin_amdgcn_make_buffer_rsrc((void*)z, 0, nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xres, 0, nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t zsrc = token_rows(z, nbytes), xsrc = token_rows(xres, nbytes), ysrc = token_rows(y, nbytes);
     // z request i of column part q = i / KH: bytes 1024 (i % KH) + 16 lane of that part = token 8 (i % KH) + lane / 8, byte 16 (lane % 8) of its 128 bytes --
     // a lane base plus constants (no per-request address registers: they would be live through the products)
     const unsigned zo0 = (unsigned)(lane >> 3) * RB + 16u * (lane & 7), za0 = (unsigned)(lane >> 3) * ZP + 16u * (lane & 7);
@@ -591,21 +635,10 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
 #pragma unroll
             for (int i = 0; i < KS1; ++i)
                 zq[i] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(zsrc, (int)(base + zo0 + 8u * RB * (i % KH) + RBH * (i / KH)), 0, 0));
-#pragma unroll
-            for (int q = 0; q < ZH; ++q) {
-#pragma unroll
-                for (int i = 0; i < KH; ++i) *reinterpret_cast<u32x4q*>(Lt + za0 + 8 * ZP * i) = zq[q * KH + i];
-                wave_sync();
-#pragma unroll
-                for (int k = 0; k < KH; ++k) zb[q * KH + k] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4q*>(Lt + r * ZP + 32 * k + 16 * h));
-                wave_sync();
-            }
+            RCX_MLP_STAGE_Z(za0 + 8 * ZP * i)
         }
         f32x16 d2[CT];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) d2[ct][i] = 0.f;
+        RCX_MLP_ZERO(d2, CT)
         RCX_MLP_STAMP(5)
 #pragma unroll 1
         for (int ht = 0; ht < HT; ++ht) {
@@ -634,23 +667,13 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + 32 * ct + 8 * g + 4 * h);
-                *reinterpret_cast<f32x4q*>(Lt + r * OP + 4 * (8 * g + 4 * h)) =
-                    f32x4q{d2[ct][4 * g] + bb.x, d2[ct][4 * g + 1] + bb.y, d2[ct][4 * g + 2] + bb.z, d2[ct][4 * g + 3] + bb.w};
-            }
+            for (int g = 0; g < 4; ++g) RCX_MLP_IMAGE_QUAD(d2[ct], Lb2 + 32 * ct + 8 * g + 4 * h, Lt + r * OP + 4 * (8 * g + 4 * h))
             wave_sync();
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const unsigned char* src = Lt + (16 * j + ot) * OP + 2 * ob;
                 const f32x4q lo = *reinterpret_cast<const f32x4q*>(src), hi = *reinterpret_cast<const f32x4q*>(src + 16);
-                const u32x4q xv = xq[ct][j];
-                bf16x8 o;
-                o[0] = (__bf16)(lo.x + __uint_as_float(xv.x << 16)); o[1] = (__bf16)(lo.y + __uint_as_float(xv.x & 0xffff0000u));
-                o[2] = (__bf16)(lo.z + __uint_as_float(xv.y << 16)); o[3] = (__bf16)(lo.w + __uint_as_float(xv.y & 0xffff0000u));
-                o[4] = (__bf16)(hi.x + __uint_as_float(xv.z << 16)); o[5] = (__bf16)(hi.y + __uint_as_float(xv.z & 0xffff0000u));
-                o[6] = (__bf16)(hi.z + __uint_as_float(xv.w << 16)); o[7] = (__bf16)(hi.w + __uint_as_float(xv.w & 0xffff0000u));
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, o), ysrc, (int)(base + (16u * j + ot) * RB + 64u * ct + ob), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, rows_plus_x(lo, hi, xq[ct][j])), ysrc, (int)(base + (16u * j + ot) * RB + 64u * ct + ob), 0, 0);
             }
             wave_sync();
         }
@@ -662,30 +685,33 @@ k_channel_mlp_pair(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 // C = 128, H = 256 (the 28 x 28 stage of M3 / A3 and its Downsample mixer): the whole pack is 128 KB and stays RESIDENT in LDS next to per-wave images of a few
-// KB -- k_channel_mlp_pair's column parts: z staged in four parts of 32 channels, the output in pieces of OC channels of TG = 512 / OC tokens (a float32 image of
-// TG rows; the lanes of the other tokens sit the write out).  With no ring there is nothing for a workgroup's waves to meet at: after the prologue (pack -> LDS by
+// KB -- k_channel_mlp_pair's column parts: z staged in four parts of 32 channels, the output in pieces of OC = 16 channels of the tile's 32 tokens (a float32
+// image of 32 rows, written by every lane).  With no ring there is nothing for a workgroup's waves to meet at: after the prologue (pack -> LDS by
 // LDS-DMA, the biases, ONE barrier) each of the 8 waves (two per SIMD) walks its own 32-token tiles, tile t on wave slot t mod (8 gridDim.x), slots wave-major so
 // that a last partial round spreads over the CUs a wave each.  The next tile's z is in flight during the current tile; the residual is requested after the
 // products (its registers were the z fragments').  The arithmetic is hidden_tile_ring's on the same fragments in the same order, so y is bit-identical to
-// k_channel_mlp_stream's.  PRIO: a raised static priority on one wave of each SIMD's pair, as in k_channel_mlp_pair.
-template <int KS1, int HT, int CT, int OC, bool PRIO>
+// k_channel_mlp_stream's.
+// Two questions are closed (tools/bench_mlp.py, profiles/r12_channel_mlp128.txt).  Output pieces of 16 / 32 / 64 channels: 56.8 / 57.3 / 60.7 us at batch 256 and
+// 15.2 / 17.2 / 18.2 us at batch 16 (the streamed kernel this form replaced: 66.8 and 15.1) -- 16 is no slower than the streamed kernel at any token count of the
+// sweep, so there is no threshold.  A raised priority on one wave of each SIMD's pair: 57.2 against 57.3 us, no gain without a barrier to align them.
+template <int KS1, int HT, int CT>
 __global__ void __launch_bounds__(512, 2)
 k_channel_mlp_res128(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres, bf16_t* __restrict__ y, const u32x4q* __restrict__ wfrag, const float* __restrict__ bias,
                      int M, int ntiles RCX_MLP_STAMP_ARG)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    constexpr int NW = 8, NT = 64 * NW, NCH = KS1 + 2 * CT, NF = HT * NCH, PER = NF * 64 / NT;   // PER: 1-KB DMA pieces of the pack per wave
+    using L = Res128Lds<KS1, HT, CT>;
+    constexpr int NW = L::NW, NT = 64 * NW, NCH = L::NCH, NF = L::NF, PER = NF * 64 / NT;   // PER: 1-KB DMA pieces of the pack per wave
     static_assert(NF * 64 % NT == 0, "whole pieces per wave");
-    constexpr int ZH = 4, RB = 32 * KS1, RBH = RB / ZH, KH = KS1 / ZH, ZP = RBH + 16;
+    constexpr int ZH = L::ZH, RB = 32 * KS1, RBH = RB / ZH, KH = KS1 / ZH, ZP = L::ZP;
     static_assert(KS1 % ZH == 0 && RBH == 64, "column parts of 32 channels: a request = 16 token rows of 64 bytes");
-    constexpr int TG = 512 / OC, NL = OC / 8, NG = 32 / TG, NP = 32 * CT / OC, OP = 4 * OC + 16, IMG = 32 * ZP > TG * OP ? 32 * ZP : TG * OP;
-    static_assert(OC == 16 || OC == 32 || OC == 64, "an output request = TG token rows of 2 OC bytes = 1 KB");
+    constexpr int OC = L::OC, NP = 32 * CT / OC, OP = L::OP;                     // an output request = 32 token rows of 2 OC bytes = 1 KB
     const u32x4q* const Lf = reinterpret_cast<const u32x4q*>(lds_raw);
-    float* const Lb1 = reinterpret_cast<float*>(lds_raw + (size_t)NF * 1024);
+    float* const Lb1 = reinterpret_cast<float*>(lds_raw + L::b1);
     const float* const Lb2 = Lb1 + 32 * HT;
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    unsigned char* const Lt = lds_raw + (size_t)NF * 1024 + sizeof(float) * 32 * (HT + CT) + (size_t)wv * IMG;
+    unsigned char* const Lt = lds_raw + L::images + (size_t)wv * L::IMG;
     {
         // piece i of wave w = bytes [1024 (8 i + w), + 1024) of the pack, lane-linear in LDS as packed
         const u32x4q* src = wfrag + threadIdx.x;
@@ -695,14 +721,12 @@ k_channel_mlp_res128(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
             __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(src + i * NT), (__attribute__((address_space(3))) void*)(dst + i * NT), 16, 0, 0);
         for (int i = threadIdx.x; i < 32 * (HT + CT); i += NT) Lb1[i] = bias[i];
     }
-    const unsigned nbytes = (unsigned)M * (unsigned)RB;                          // < 2^31 (checked by the launcher)
-    const __amdgpu_buffer_rsrc_t zsrc = __builtin_amdgcn_make_buffer_rsrc((void*)z, 0, nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xres, 0, nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, nbytes, 0x00020000);
+    const unsigned nbytes = (unsigned)M * (unsigned)RB;
+    const __amdgpu_buffer_rsrc_t zsrc = token_rows(z, nbytes), xsrc = token_rows(xres, nbytes), ysrc = token_rows(y, nbytes);
     // z request i of column part q = i / KH: token 16 (i % KH) + lane / 4, byte 16 (lane % 4) of its 64 bytes -- a lane base plus constants
     const unsigned zo0 = (unsigned)(lane >> 2) * RB + 16u * (lane & 3), za0 = (unsigned)(lane >> 2) * ZP + 16u * (lane & 3);
-    // output request (token group k, piece p): token TG k + lane / NL, bytes 2 OC p + 16 (lane % NL) of its row
-    const unsigned ot = lane / NL, ob = 16u * (lane % NL);
+    // output request p (a piece of OC channels): token lane / 2, bytes 2 OC p + 16 (lane % 2) of its row
+    const unsigned ot = lane / 2, ob = 16u * (lane % 2);
     const int stride = NW * (int)gridDim.x;
     int tile = wv * (int)gridDim.x + (int)blockIdx.x;
     u32x4q zq[KS1];
@@ -715,65 +739,34 @@ k_channel_mlp_res128(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xr
     if (tile < ntiles) load_z(tile);
     __builtin_amdgcn_s_waitcnt(0x70);                                            // vmcnt(0) lgkmcnt(0): this wave's pieces of the pack have landed
     __syncthreads();                                                             // the only barrier: a wave without a tile leaves right after it
-    if (PRIO && !(__builtin_popcount(wv) & 1)) __builtin_amdgcn_s_setprio(1);
     RCX_MLP_STAMP_BEGIN
     for (; tile < ntiles; tile += stride) {
         const unsigned base = (unsigned)tile * 32u * RB;
         bf16x8 zb[KS1];
-#pragma unroll
-        for (int q = 0; q < ZH; ++q) {
-#pragma unroll
-            for (int i = 0; i < KH; ++i) *reinterpret_cast<u32x4q*>(Lt + za0 + 16 * ZP * i) = zq[q * KH + i];
-            wave_sync();
-#pragma unroll
-            for (int k = 0; k < KH; ++k) zb[q * KH + k] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4q*>(Lt + r * ZP + 32 * k + 16 * h));
-            wave_sync();
-        }
+        RCX_MLP_STAGE_Z(za0 + 16 * ZP * i)
         if (tile + stride < ntiles) load_z(tile + stride);                       // the next tile's channels: in flight during this tile
         f32x16 d2[CT];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) d2[ct][i] = 0.f;
+        RCX_MLP_ZERO(d2, CT)
         RCX_MLP_STAMP(5)
 #pragma unroll 1
         for (int ht = 0; ht < HT; ++ht) {
             hidden_tile_ring<KS1, CT, 4>(Lf + (size_t)ht * NCH * 64, Lb1 + 32 * ht, lane, h, zb, d2 RCX_MLP_STAMP_PASS);
             RCX_MLP_STAMP_STEP
         }
-        u32x4q xq[NG][NP];                                                       // the residual: requested after the products
+        u32x4q xq[NP];                                                           // the residual: requested after the products
 #pragma unroll
-        for (int k = 0; k < NG; ++k)
+        for (int p = 0; p < NP; ++p) xq[p] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(xsrc, (int)(base + ot * RB + 2u * OC * p + ob), 0, 0));
 #pragma unroll
-            for (int p = 0; p < NP; ++p)
-                xq[k][p] = __builtin_bit_cast(u32x4q, __builtin_amdgcn_raw_buffer_load_b128(xsrc, (int)(base + (TG * k + ot) * RB + 2u * OC * p + ob), 0, 0));
+        for (int p = 0; p < NP; ++p) {
+            // D2 + b2 (token on the lane) of the piece's channels -- output tile p / 2, register groups 2 (p % 2) and + 1 -> the float32 image
 #pragma unroll
-        for (int k = 0; k < NG; ++k)
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                if (NG == 1 || r / TG == k) {                                    // D2 + b2 of the group's tokens (token on the lane) -> the float32 image
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            if ((32 * ct + 8 * g) / OC != p) continue;
-                            const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + 32 * ct + 8 * g + 4 * h);
-                            *reinterpret_cast<f32x4q*>(Lt + (r % TG) * OP + 4 * (32 * ct + 8 * g - OC * p + 4 * h)) =
-                                f32x4q{d2[ct][4 * g] + bb.x, d2[ct][4 * g + 1] + bb.y, d2[ct][4 * g + 2] + bb.z, d2[ct][4 * g + 3] + bb.w};
-                        }
-                }
-                wave_sync();
-                const unsigned char* src = Lt + ot * OP + 2 * ob;                // -> rows: + x, rounded once
-                const f32x4q lo = *reinterpret_cast<const f32x4q*>(src), hi = *reinterpret_cast<const f32x4q*>(src + 16);
-                const u32x4q xv = xq[k][p];
-                bf16x8 o;
-                o[0] = (__bf16)(lo.x + __uint_as_float(xv.x << 16)); o[1] = (__bf16)(lo.y + __uint_as_float(xv.x & 0xffff0000u));
-                o[2] = (__bf16)(lo.z + __uint_as_float(xv.y << 16)); o[3] = (__bf16)(lo.w + __uint_as_float(xv.y & 0xffff0000u));
-                o[4] = (__bf16)(hi.x + __uint_as_float(xv.z << 16)); o[5] = (__bf16)(hi.y + __uint_as_float(xv.z & 0xffff0000u));
-                o[6] = (__bf16)(hi.z + __uint_as_float(xv.w << 16)); o[7] = (__bf16)(hi.w + __uint_as_float(xv.w & 0xffff0000u));
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, o), ysrc, (int)(base + (TG * k + ot) * RB + 2u * OC * p + ob), 0, 0);
-                wave_sync();
-            }
+            for (int g = 2 * (p & 1); g < 2 * (p & 1) + 2; ++g) RCX_MLP_IMAGE_QUAD(d2[p >> 1], Lb2 + 32 * (p >> 1) + 8 * g + 4 * h, Lt + r * OP + 4 * (8 * (g & 1) + 4 * h))
+            wave_sync();
+            const unsigned char* src = Lt + ot * OP + 2 * ob;                    // -> rows: + x, rounded once
+            const f32x4q lo = *reinterpret_cast<const f32x4q*>(src), hi = *reinterpret_cast<const f32x4q*>(src + 16);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, rows_plus_x(lo, hi, xq[p])), ysrc, (int)(base + ot * RB + 2u * OC * p + ob), 0, 0);
+            wave_sync();
+        }
     }
     RCX_MLP_STAMP(5)
     RCX_MLP_STAMP_END(wv * (int)gridDim.x + (int)blockIdx.x)
@@ -814,12 +807,11 @@ k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
     constexpr int XP = NST & 1;                                                  // exchange buffer of step s: (s + XP) & 1 -- the last step's is buffer 1
     constexpr int ZR = KS1 / 4, ZU = 8 * ZR / NW;                                // z: ZR requests per group of 8 tokens, 8 groups, ZU requests a wave
     static_assert(8 * ZR % NW == 0, "the z requests divide among the waves");
-    constexpr int RB = 32 * KS1, OP = 256 + 16, IMG = 32 * OP;                   // bytes per token row; the output image's row pitch (16 bytes of padding: banks)
-    constexpr int ZBYTES = 2 * KS1 * 1024, XBYTES = SH * 4 * 1024;
-    static_assert(NW * IMG <= ZBYTES + XBYTES, "the output images alias the z fragments and exchange buffer 0");
+    using L = WideLds<KS1, HT, CT, NW>;
+    constexpr int RB = 32 * KS1, OP = L::OP, XBYTES = L::XBYTES;                 // bytes per token row; the output image's row pitch; an exchange buffer
     u32x4q* const Lz = reinterpret_cast<u32x4q*>(lds_raw);                      // [tt][ks][lane]
-    u32x4q* const Lx = reinterpret_cast<u32x4q*>(lds_raw + ZBYTES);             // [2][hidden tile of the step][tt][q][lane]
-    float* const Lb1 = reinterpret_cast<float*>(lds_raw + ZBYTES + 2 * XBYTES);
+    u32x4q* const Lx = reinterpret_cast<u32x4q*>(lds_raw + L::xchg);            // [2][hidden tile of the step][tt][q][lane]
+    float* const Lb1 = reinterpret_cast<float*>(lds_raw + L::b1);
     const float* const Lb2 = Lb1 + 32 * HT;
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -833,10 +825,8 @@ k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
     u32x4q ring[RD];
 #pragma unroll
     for (int i = 0; i < RD; ++i) ring[i] = frag(0, i);
-    const unsigned nbytes = (unsigned)M * (unsigned)RB;                          // < 2^31 (checked by the launcher)
-    const __amdgpu_buffer_rsrc_t zsrc = __builtin_amdgcn_make_buffer_rsrc((void*)z, 0, nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xres, 0, nbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, nbytes, 0x00020000);
+    const unsigned nbytes = (unsigned)M * (unsigned)RB;
+    const __amdgpu_buffer_rsrc_t zsrc = token_rows(z, nbytes), xsrc = token_rows(xres, nbytes), ysrc = token_rows(y, nbytes);
     const unsigned base = blockIdx.x * 64u * RB;
     {
         // z -> B fragments: token group tg = tokens 8 tg .. 8 tg + 7; its request j = the 16-byte pieces 8 j + lane / 8 of the rows of tokens lane % 8 (128 contiguous
@@ -859,12 +849,8 @@ k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
     if (!(__builtin_popcount(wv) & 1)) __builtin_amdgcn_s_setprio(1);            // one wave of each SIMD's pair takes the matrix pipe first (k_channel_mlp_pair)
     constexpr int LGKM0 = 0xC07F;                                                // s_waitcnt lgkmcnt(0) alone: vmcnt 63, expcnt 7
     f32x16 d2[2][2];
-#pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2)
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) d2[c2][tt][i] = 0.f;
+    RCX_MLP_ZERO(d2[0], 2)
+    RCX_MLP_ZERO(d2[1], 2)
     // output request j of token tile tt: token 8 j + lane / 8, bytes 128 w + 16 (lane % 8) of its row
     const unsigned ot = lane >> 3, ob = 16u * (lane & 7);
     u32x4q xq[2][4];
@@ -873,10 +859,7 @@ k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
         const int sn = LAST ? 0 : s + 1;
         // ---- phase A
         f32x16 d1[2];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) d1[tt][i] = 0.f;
+        RCX_MLP_ZERO(d1, 2)
         constexpr int BD = 2;                                                   // k-steps the z fragments are read ahead of their products
         u32x4q zb[BD][2];
 #pragma unroll
@@ -900,26 +883,7 @@ k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
         u32x4q* const Lw = Lx + (size_t)((s + XP) & 1) * (XBYTES / 16) + wv * 4 * 64 + lane;
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
-            gelu_f32x2 gv[8];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4q bb = *reinterpret_cast<const f32x4q*>(b1t + 8 * g + 4 * h);
-                gv[2 * g] = gelu_f32x2{d1[tt][4 * g] + bb.x, d1[tt][4 * g + 1] + bb.y};
-                gv[2 * g + 1] = gelu_f32x2{d1[tt][4 * g + 2] + bb.z, d1[tt][4 * g + 3] + bb.w};
-            }
-            {
-                gelu_f32x2 ga[4] = {gv[0], gv[1], gv[2], gv[3]}, gb[4] = {gv[4], gv[5], gv[6], gv[7]};
-                gelu2x_batch<4>(ga);
-                gelu2x_batch<4>(gb);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { gv[i] = ga[i]; gv[4 + i] = gb[i]; }
-            }
-            bf16x8 hb[2];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                hb[g >> 1][4 * (g & 1) + 0] = (__bf16)gv[2 * g].x; hb[g >> 1][4 * (g & 1) + 1] = (__bf16)gv[2 * g].y;
-                hb[g >> 1][4 * (g & 1) + 2] = (__bf16)gv[2 * g + 1].x; hb[g >> 1][4 * (g & 1) + 3] = (__bf16)gv[2 * g + 1].y;
-            }
+            RCX_MLP_HIDDEN_GELU(d1[tt], *reinterpret_cast<const f32x4q*>(b1t + 8 * g + 4 * h))
             Lw[(2 * tt) * 64] = __builtin_bit_cast(u32x4q, hb[0]);
             Lw[(2 * tt + 1) * 64] = __builtin_bit_cast(u32x4q, hb[1]);
         }
@@ -963,29 +927,19 @@ k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
     for (int s = 0; s < NST - 1; ++s) step(s, std::false_type{});
     step(NST - 1, std::true_type{});
     // ---- epilogue (every wave has passed the last barrier: the z fragments and exchange buffer 0 are dead)
-    unsigned char* const Lt = lds_raw + (size_t)wv * IMG;
+    unsigned char* const Lt = lds_raw + (size_t)wv * L::IMG;
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) {
 #pragma unroll
         for (int c2 = 0; c2 < 2; ++c2)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + 32 * (2 * wv + c2) + 8 * g + 4 * h);
-                *reinterpret_cast<f32x4q*>(Lt + r * OP + 4 * (32 * c2 + 8 * g + 4 * h)) =
-                    f32x4q{d2[c2][tt][4 * g] + bb.x, d2[c2][tt][4 * g + 1] + bb.y, d2[c2][tt][4 * g + 2] + bb.z, d2[c2][tt][4 * g + 3] + bb.w};
-            }
+            for (int g = 0; g < 4; ++g) RCX_MLP_IMAGE_QUAD(d2[c2][tt], Lb2 + 32 * (2 * wv + c2) + 8 * g + 4 * h, Lt + r * OP + 4 * (32 * c2 + 8 * g + 4 * h))
         wave_sync();
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const unsigned char* src = Lt + (8 * j + ot) * OP + 2 * ob;
             const f32x4q lo = *reinterpret_cast<const f32x4q*>(src), hi = *reinterpret_cast<const f32x4q*>(src + 16);
-            const u32x4q xv = xq[tt][j];
-            bf16x8 o;
-            o[0] = (__bf16)(lo.x + __uint_as_float(xv.x << 16)); o[1] = (__bf16)(lo.y + __uint_as_float(xv.x & 0xffff0000u));
-            o[2] = (__bf16)(lo.z + __uint_as_float(xv.y << 16)); o[3] = (__bf16)(lo.w + __uint_as_float(xv.y & 0xffff0000u));
-            o[4] = (__bf16)(hi.x + __uint_as_float(xv.z << 16)); o[5] = (__bf16)(hi.y + __uint_as_float(xv.z & 0xffff0000u));
-            o[6] = (__bf16)(hi.z + __uint_as_float(xv.w << 16)); o[7] = (__bf16)(hi.w + __uint_as_float(xv.w & 0xffff0000u));
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, o), ysrc, (int)(base + (32u * tt + 8u * j + ot) * RB + 128u * wv + ob), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4q, rows_plus_x(lo, hi, xq[tt][j])), ysrc, (int)(base + (32u * tt + 8u * j + ot) * RB + 128u * wv + ob), 0, 0);
         }
         wave_sync();
     }
@@ -993,39 +947,18 @@ k_channel_mlp_wide(const bf16_t* __restrict__ z, const bf16_t* __restrict__ xres
 
 }  // namespace mlp
 
-// C % 8 == 0, H % 32 == 0 (the host pads the hidden layer with zero units), the weights fit the CU's LDS, M C 2 < 2^31
+// The tile counts of C channels, the one statement of the rule on this side (ops._mlp_tiles is Python's; tests/test_mlp768_cpu.py holds the two together):
+// k-steps of the first product; output tiles -- rounded up to even above 128 channels: the streamed kernels write their output in halves of two tiles, W2 / b2
+// padded with zero rows
+constexpr int mlp_ks1(int C) { return (C + 15) / 16; }
+constexpr int mlp_ct(int C) { return C > 128 ? (C + 63) / 64 * 2 : (C + 31) / 32; }
+
+// C % 8 == 0, H % 32 == 0 (the host pads the hidden layer with zero units)
 static bool mlp_shape(int C, int H, int* ks1, int* ht, int* ct)
 {
     if (C <= 0 || H <= 0 || C % 8 || H % 32) return false;
-    *ks1 = (C + 15) / 16; *ht = H / 32; *ct = (C + 31) / 32;
-    if (C > 128 && (*ct & 1)) ++*ct;              // the streamed kernels write their output in halves of two tiles: W2 / b2 padded with zero rows (ops.pack_channel_mlp)
+    *ks1 = mlp_ks1(C); *ht = H / 32; *ct = mlp_ct(C);
     return true;
-}
-
-// C = 512, H = 1024 is offered from this token count upward.  Measured crossover against the four library launches (tools/bench_mlp.py, profiles/r11_channel_mlp512.txt):
-// none in the sweep -- M = 1 568 / 3 136 / 6 272 / 12 544: 29.3 / 29.8 / 31.3 / 36.5 us fused against 53.1 / 52.7 / 53.7 / 62.6 us, so it lies below 1 024, the token
-// count tests/test_mlp_gpu.py pins as unsupported; hence 2 048, the smallest sweep point above it with margin.
-static constexpr int MLP512_MIN_TOKENS = 2048;
-// C = 512, H = 768 and C = 384, H = 768 likewise, each from the smallest point of its sweep (tools/bench_mlp.py, three runs in one job, profiles/r13_channel_mlp768.txt): no
-// crossover in either -- 4 x 4 planes, M = 512 / 1 024 / 2 048 / 4 096 / 8 192: 23.2-23.6 / 23.9-24.9 / 23.8-26.4 / 25.3-25.6 / 28.5-33.0 us fused against 51.0-53.4 /
-// 51.9-67.8 / 51.0-53.3 / 51.0-52.5 / 49.7-50.6 us for the four library launches; 7 x 7 planes, M = 784 / 1 568 / 3 136 / 6 272 / 12 544: 23.6-23.8 / 23.3-23.4 / 23.8-24.1 /
-// 24.8-27.9 / 27.3-27.9 us against 52.8-54.8 / 50.8-52.5 / 50.9-52.7 / 50.9-53.1 / 51.8-54.2.  Below the sweeps nothing was measured, so nothing is offered there.
-static constexpr int MLP512X768_MIN_TOKENS = 512;
-static constexpr int MLP384_MIN_TOKENS = 784;
-
-bool channel_mlp_applicable(int M, int C, int H, int dtype)
-{
-    int ks1, ht, ct;
-    if (dtype != 1 || M <= 0 || !mlp_shape(C, H, &ks1, &ht, &ct)) return false;
-    if ((unsigned long long)M * C * 2 >= (1ull << 31)) return false;
-    // the 7 x 7 stage: a workgroup streams all 2 MB of weights for its 64 tokens, so a few workgroups on a mostly idle chip lose to the library's N-split GEMMs
-    if (C == 512 && ht == 32) return M >= MLP512_MIN_TOKENS;
-    if (C == 512 && ht == 24) return M >= MLP512X768_MIN_TOKENS;
-    if (C == 384 && ht == 24) return M >= MLP384_MIN_TOKENS;
-    if (C == 256 && ht == 16) return true;
-    if (C == 192 && ht == 12) return true;
-    if ((C == 160 && ht == 10) || (C == 320 && ht == 20)) return true;
-    return (ks1 == 4 && ht == 4 && ct == 2) || (C == 128 && ht == 8) || (ks1 == 3 && ht == 3 && ct == 2) || (C == 96 && ht == 6) || (C == 80 && ht == 5);
 }
 
 size_t channel_mlp_pack_bytes(int C, int H)
@@ -1035,97 +968,142 @@ size_t channel_mlp_pack_bytes(int C, int H)
     return (size_t)(ht * ks1 + ct * 2 * ht) * 1024;
 }
 
-template <int KS1, int HT, int CT, bool KX, bool OX>
-static hipError_t launch_mlp(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, int ncu, hipStream_t s)
+// ---- one launcher per kernel form, instantiated per shape <CH channels, HT hidden tiles> by the table below; all of one signature (ncu: the device's compute units)
+#define RCX_MLP_LAUNCH_ARGS const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, int ncu, hipStream_t s
+typedef hipError_t (*mlp_launcher)(RCX_MLP_LAUNCH_ARGS);
+
+// C <= 96: the pack resident in LDS, one workgroup per CU
+template <int CH, int HT>
+static hipError_t launch_mlp(RCX_MLP_LAUNCH_ARGS)
 {
-    constexpr size_t lds = (size_t)(HT * KS1 + CT * 2 * HT) * 1024 + sizeof(float) * 32 * (HT + CT);
-    static_assert(lds <= 160 * 1024, "the weights must fit the LDS");
+    constexpr int KS1 = mlp_ks1(CH), CT = mlp_ct(CH);
     // one workgroup per CU shares the LDS weights: 12 waves (three per SIMD, 168 registers) where the accumulators are two output tiles, else 8 (256 registers)
     constexpr int NW = CT <= 2 ? 12 : 8, WPS = NW / 4;
     constexpr bool STAGED = CT <= 2;
-    constexpr size_t stage = STAGED ? (size_t)NW * 32 * ((32 * KS1 + 16) > (128 * CT + 16) ? (32 * KS1 + 16) : (128 * CT + 16)) : 0;
-    if ((C == 16 * KS1) != KX || (C == 32 * CT) != OX) return hipErrorInvalidConfiguration;
-    auto kfn = mlp::k_channel_mlp<KS1, HT, CT, NW, WPS, KX, OX, STAGED>;
-    static_assert(lds + stage <= 160 * 1024, "weights + the waves' images must fit the LDS");
-    RCX_SET_LDS_ONCE(kfn, lds + stage);
+    using L = mlp::SmallLds<KS1, HT, CT, NW, STAGED>;
+    static_assert(L::bytes <= 160 * 1024, "weights + the waves' images must fit the LDS");
+    if (C != CH) return hipErrorInvalidConfiguration;
+    auto kfn = mlp::k_channel_mlp<KS1, HT, CT, NW, WPS, CH == 16 * KS1, CH == 32 * CT, STAGED>;
+    RCX_SET_LDS_ONCE(kfn, L::bytes);
     const int ntiles = (M + 31) / 32;
     int grid = ncu;
     if (grid * NW > ntiles) grid = (ntiles + NW - 1) / NW;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * NW), lds + stage, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, C, ntiles RCX_MLP_STAMP_VAL);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * NW), L::bytes, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, C, ntiles RCX_MLP_STAMP_VAL);
     return hipGetLastError();
 }
 
-// C == 16 KS1 == 32 CT exactly (no padding lanes): the streamed form
-template <int KS1, int HT, int CT, int NW, int ZH = 1, bool ZPF = true>
-static hipError_t launch_mlp_stream(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, int ncu, hipStream_t s)
+// the streamed form: 4 waves, 128 tokens a workgroup
+template <int CH, int HT, int ZH = 1, bool ZPF = true>
+static hipError_t launch_mlp_stream(RCX_MLP_LAUNCH_ARGS)
 {
-    constexpr int NCH = KS1 + 2 * CT, ZP = 32 * KS1 / ZH + 16, OP = 256 + 16, IMG = 32 * (ZP > OP ? ZP : OP);
-    constexpr size_t lds = (size_t)2 * NCH * 1024 + sizeof(float) * 32 * (HT + CT) + (size_t)NW * IMG;
-    static_assert(lds <= 160 * 1024, "the ring and the waves' images must fit the LDS");
-    static_assert(CT % 2 == 0 && 32 * CT >= 16 * KS1 && 32 * (CT - 2) < 16 * KS1, "output tiles: the channel count rounded up to a multiple of 64");
-    if (C != 16 * KS1) return hipErrorInvalidConfiguration;
+    constexpr int KS1 = mlp_ks1(CH), CT = mlp_ct(CH), NW = 4;
+    using L = mlp::StreamLds<KS1, HT, CT, NW, ZH>;
+    static_assert(L::bytes <= 160 * 1024, "the ring and the waves' images must fit the LDS");
+    static_assert(CH == 16 * KS1, "no padding lanes");
+    if (C != CH) return hipErrorInvalidConfiguration;
     auto kfn = mlp::k_channel_mlp_stream<KS1, HT, CT, NW, NW / 4, ZH, ZPF>;
-    RCX_SET_LDS_ONCE(kfn, lds);
+    RCX_SET_LDS_ONCE(kfn, L::bytes);
     const int nblocks = (M + 32 * NW - 1) / (32 * NW);
     const int grid = nblocks < ncu ? nblocks : ncu;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * NW), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, C, nblocks);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * NW), L::bytes, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, C, nblocks);
     return hipGetLastError();
 }
 
-// C = 256, H = 512: 8 waves (two per SIMD), 256 tokens a workgroup
-static hipError_t launch_mlp_pair256(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, int ncu, hipStream_t s)
+// the streamed form with 8 waves (two per SIMD), 256 tokens a workgroup
+template <int CH, int HT>
+static hipError_t launch_mlp_pair(RCX_MLP_LAUNCH_ARGS)
 {
-    constexpr int KS1 = 16, HT = 16, CT = 8, NCH = KS1 + 2 * CT, IMG = 32 * (128 + 16);
-    constexpr size_t lds = (size_t)3 * NCH * 1024 + sizeof(float) * 32 * (HT + CT) + (size_t)8 * IMG;
-    static_assert(lds <= 160 * 1024, "the ring and the waves' images must fit the LDS");
-    if (C != 16 * KS1) return hipErrorInvalidConfiguration;
+    constexpr int KS1 = mlp_ks1(CH), CT = mlp_ct(CH);
+    using L = mlp::PairLds<KS1, HT, CT>;
+    static_assert(L::bytes <= 160 * 1024, "the ring and the waves' images must fit the LDS");
+    static_assert(CH == 16 * KS1, "no padding lanes");
+    if (C != CH) return hipErrorInvalidConfiguration;
     auto kfn = mlp::k_channel_mlp_pair<KS1, HT, CT, RCX_MLP_PINNED>;
-    RCX_SET_LDS_ONCE(kfn, lds);
-    const int nblocks = (M + 255) / 256;
+    RCX_SET_LDS_ONCE(kfn, L::bytes);
+    const int nblocks = (M + 32 * L::NW - 1) / (32 * L::NW);
     const int grid = nblocks < ncu ? nblocks : ncu;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(512), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, C, nblocks RCX_MLP_STAMP_VAL);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * L::NW), L::bytes, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, C, nblocks RCX_MLP_STAMP_VAL);
     return hipGetLastError();
 }
 
-// C = 128, H = 256: the pack resident in LDS, 8 free-running waves (two per SIMD) a workgroup, one persistent workgroup per CU
-static hipError_t launch_mlp_res128(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, int ncu, hipStream_t s)
+// the pack resident in LDS, 8 free-running waves (two per SIMD) a workgroup, one persistent workgroup per CU
+template <int CH, int HT>
+static hipError_t launch_mlp_res128(RCX_MLP_LAUNCH_ARGS)
 {
-    // Output pieces of 16 / 32 / 64 channels: 56.8 / 57.3 / 60.7 us at batch 256 and 15.2 / 17.2 / 18.2 us at batch 16 (the streamed kernel this form replaced: 66.8 and
-    // 15.1; tools/bench_mlp.py, profiles/r12_channel_mlp128.txt) -- 16, which writes the image with every lane, is no slower than the streamed kernel at any token
-    // count of the sweep, so there is no threshold.  A raised priority on one wave of each SIMD's pair: 57.2 against 57.3 us, no gain without a barrier to align them.
-    constexpr int KS1 = 8, HT = 8, CT = 4, NW = 8, OC = 16;
-    constexpr bool PRIO = false;
-    constexpr int ZIMG = 32 * (32 * KS1 / 4 + 16), OIMG = (512 / OC) * (4 * OC + 16), IMG = ZIMG > OIMG ? ZIMG : OIMG;
-    constexpr size_t pack = (size_t)HT * (KS1 + 2 * CT) * 1024, lds = pack + sizeof(float) * 32 * (HT + CT) + (size_t)NW * IMG;
-    static_assert(pack == 128 * 1024, "the pack of channel_mlp_pack_bytes(128, 256)");
-    static_assert(lds <= 160 * 1024, "the pack, the biases and the waves' images must fit the LDS");
-    if (C != 16 * KS1) return hipErrorInvalidConfiguration;
-    auto kfn = mlp::k_channel_mlp_res128<KS1, HT, CT, OC, PRIO>;
-    RCX_SET_LDS_ONCE(kfn, lds);
+    constexpr int KS1 = mlp_ks1(CH), CT = mlp_ct(CH);
+    using L = mlp::Res128Lds<KS1, HT, CT>;
+    static_assert(L::bytes <= 160 * 1024, "the pack, the biases and the waves' images must fit the LDS");
+    static_assert(CH == 16 * KS1, "no padding lanes");
+    if (C != CH) return hipErrorInvalidConfiguration;
+    auto kfn = mlp::k_channel_mlp_res128<KS1, HT, CT>;
+    RCX_SET_LDS_ONCE(kfn, L::bytes);
     const int ntiles = (M + 31) / 32;
-    int grid = (ntiles + NW - 1) / NW;
+    int grid = (ntiles + L::NW - 1) / L::NW;
     if (grid > ncu) grid = ncu;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * NW), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, ntiles RCX_MLP_STAMP_VAL);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64 * L::NW), L::bytes, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M, ntiles RCX_MLP_STAMP_VAL);
     return hipGetLastError();
 }
 
-// C = 512, H = 1024 | 768 and C = 384, H = 768: NW waves, 64 tokens a workgroup, the weights straight from global memory
-template <int KS1, int HT, int CT, int NW>
-static hipError_t launch_mlp_wide(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, hipStream_t s)
+// CT / 2 waves, 64 tokens a workgroup, the weights straight from global memory (ncu: unused, a workgroup per 64 tokens)
+template <int CH, int HT>
+static hipError_t launch_mlp_wide(RCX_MLP_LAUNCH_ARGS)
 {
-    constexpr size_t lds = (size_t)2 * KS1 * 1024 + (size_t)2 * NW * 4 * 1024 + sizeof(float) * 32 * (HT + CT);
-    static_assert(lds <= 160 * 1024, "the z fragments, the exchange buffers and the biases must fit the LDS");
-    if (C != 16 * KS1) return hipErrorInvalidConfiguration;
+    constexpr int KS1 = mlp_ks1(CH), CT = mlp_ct(CH), NW = CT / 2;
+    using L = mlp::WideLds<KS1, HT, CT, NW>;
+    static_assert(L::bytes <= 160 * 1024, "the z fragments, the exchange buffers and the biases must fit the LDS");
+    static_assert(CH == 16 * KS1, "no padding lanes");
+    if (C != CH) return hipErrorInvalidConfiguration;
     auto kfn = mlp::k_channel_mlp_wide<KS1, HT, CT, 8, NW>;
-    RCX_SET_LDS_ONCE(kfn, lds);
-    hipLaunchKernelGGL(kfn, dim3((unsigned)((M + 63) / 64)), dim3(64 * NW), lds, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M);
+    RCX_SET_LDS_ONCE(kfn, L::bytes);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)((M + 63) / 64)), dim3(64 * NW), L::bytes, s, (const bf16_t*)z, (const bf16_t*)x, (bf16_t*)y, (const mlp::u32x4q*)wfrag, bias, M);
     return hipGetLastError();
 }
+
+// ---- THE shapes that have a kernel: C channels, H / 32 hidden tiles, the token count a shape is offered from, its launcher.  channel_mlp_applicable and
+// channel_mlp read nothing else (a launcher refuses a C that is not its own, so a row whose two statements of C disagree fails at its first launch, loudly).
+struct MlpRow { int C, HT, min_tokens; mlp_launcher launch; };
+static constexpr MlpRow MLP_ROWS[] = {
+    {256, 16, 1, launch_mlp_pair<256, 16>},                     // M3 / A3 stage 2
+    {128, 8, 1, launch_mlp_res128<128, 8>},                     // M3 / A3 stage 1
+    // The 7 x 7 stage: a workgroup streams all 2 MB of weights for its 64 tokens, so a few workgroups on a mostly idle chip lose to the library's N-split GEMMs.
+    // Measured crossover against the four library launches (tools/bench_mlp.py, profiles/r11_channel_mlp512.txt): none in the sweep -- M = 1 568 / 3 136 / 6 272 /
+    // 12 544: 29.3 / 29.8 / 31.3 / 36.5 us fused against 53.1 / 52.7 / 53.7 / 62.6 us, so it lies below 1 024, the token count tests/test_mlp_gpu.py pins as
+    // unsupported; hence 2 048, the smallest sweep point above it with margin.
+    {512, 32, 2048, launch_mlp_wide<512, 32>},                  // M3 / A3 stage 3
+    // C = 512, H = 768 and C = 384, H = 768 likewise, each from the smallest point of its sweep (tools/bench_mlp.py, three runs in one job,
+    // profiles/r13_channel_mlp768.txt): no crossover in either -- 4 x 4 planes, M = 512 / 1 024 / 2 048 / 4 096 / 8 192: 23.2-23.6 / 23.9-24.9 / 23.8-26.4 /
+    // 25.3-25.6 / 28.5-33.0 us fused against 51.0-53.4 / 51.9-67.8 / 51.0-53.3 / 51.0-52.5 / 49.7-50.6 us for the four library launches; 7 x 7 planes, M = 784 /
+    // 1 568 / 3 136 / 6 272 / 12 544: 23.6-23.8 / 23.3-23.4 / 23.8-24.1 / 24.8-27.9 / 27.3-27.9 us against 52.8-54.8 / 50.8-52.5 / 50.9-52.7 / 50.9-53.1 /
+    // 51.8-54.2.  Below the sweeps nothing was measured, so nothing is offered there.
+    {512, 24, 512, launch_mlp_wide<512, 24>},                   // T / S / B stage 3
+    {384, 24, 784, launch_mlp_wide<384, 24>},                   // S / B stage 2, M1 / A1 stage 3
+    {192, 12, 1, launch_mlp_stream<192, 12>},                   // M1 stage 2
+    {160, 10, 1, launch_mlp_stream<160, 10>},                   // M5 / A5 stage 1
+    {320, 20, 1, launch_mlp_stream<320, 20, 2, false>},         // M5 / A5 stage 2: whole z rows would not leave room for the ring, nor the next block's z registers
+    {64, 4, 1, launch_mlp<64, 4>},                              // M3 / A3 stage 0 ...
+    {56, 4, 1, launch_mlp<56, 4>},                              // ... M2
+    {48, 3, 1, launch_mlp<48, 3>},                              // M1 stage 0 ...
+    {40, 3, 1, launch_mlp<40, 3>},                              // ... M0
+    {96, 6, 1, launch_mlp<96, 6>},
+    {80, 5, 1, launch_mlp<80, 5>},
+};
+
+// the row of (C, H) if M tokens of it have a kernel: bf16, M C 2 < 2^31 (the kernels' 32-bit byte offsets)
+static const MlpRow* mlp_row(int M, int C, int H, int dtype)
+{
+    if (dtype != 1 || M <= 0 || H <= 0 || H % 32) return nullptr;
+    if ((unsigned long long)M * C * 2 >= (1ull << 31)) return nullptr;
+    for (const MlpRow& row : MLP_ROWS)
+        if (row.C == C && row.HT == H / 32) return M >= row.min_tokens ? &row : nullptr;
+    return nullptr;
+}
+
+bool channel_mlp_applicable(int M, int C, int H, int dtype) { return mlp_row(M, C, H, dtype) != nullptr; }
 
 hipError_t channel_mlp(const void* z, const void* x, void* y, const void* wfrag, const float* bias, int M, int C, int H, int dtype, hipStream_t s)
 {
-    int ks1, ht, ct;
-    if (!channel_mlp_applicable(M, C, H, dtype) || !mlp_shape(C, H, &ks1, &ht, &ct)) return hipErrorInvalidConfiguration;
+    const MlpRow* const row = mlp_row(M, C, H, dtype);
+    if (!row) return hipErrorInvalidConfiguration;
     static std::atomic<int> cus[RCX_MAX_DEVICES];                     // compute units of each device, asked once
     int dev = 0, ncu = 256;
     if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < RCX_MAX_DEVICES) {
@@ -1136,24 +1114,7 @@ hipError_t channel_mlp(const void* z, const void* x, void* y, const void* wfrag,
             cus[dev].store(ncu, std::memory_order_relaxed);
         }
     }
-    if (C == 512 && ht == 32) return launch_mlp_wide<32, 32, 16, 8>(z, x, y, wfrag, bias, M, C, s);                 // M3 / A3 stage 3
-    if (C == 512 && ht == 24) return launch_mlp_wide<32, 24, 16, 8>(z, x, y, wfrag, bias, M, C, s);                 // T / S / B stage 3
-    if (C == 384 && ht == 24) return launch_mlp_wide<24, 24, 12, 6>(z, x, y, wfrag, bias, M, C, s);                    // S / B stage 2, M1 / A1 stage 3
-    if (C == 256 && ht == 16) return launch_mlp_pair256(z, x, y, wfrag, bias, M, C, ncu, s);                         // M3 / A3 stage 2
-    if (C == 192 && ht == 12) return launch_mlp_stream<12, 12, 6, 4>(z, x, y, wfrag, bias, M, C, ncu, s);           // M1 stage 2
-    if (C == 160 && ht == 10) return launch_mlp_stream<10, 10, 6, 4>(z, x, y, wfrag, bias, M, C, ncu, s);           // M5 / A5 stage 1
-    if (C == 320 && ht == 20) return launch_mlp_stream<20, 20, 10, 4, 2, false>(z, x, y, wfrag, bias, M, C, ncu, s); // M5 / A5 stage 2
-    if (ks1 == 4 && ht == 4) return C == 64 ? launch_mlp<4, 4, 2, true, true>(z, x, y, wfrag, bias, M, C, ncu, s)            // M3 / A3 stage 0 ...
-                                            : launch_mlp<4, 4, 2, false, false>(z, x, y, wfrag, bias, M, C, ncu, s);         // ... M2 (56 channels)
-    if (ks1 == 8 && ht == 8) {
-        if (C != 128) return hipErrorInvalidConfiguration;
-        return launch_mlp_res128(z, x, y, wfrag, bias, M, C, ncu, s);                                               // M3 / A3 stage 1
-    }
-    if (ks1 == 3 && ht == 3) return C == 48 ? launch_mlp<3, 3, 2, true, false>(z, x, y, wfrag, bias, M, C, ncu, s)            // M1 stage 0 ...
-                                            : launch_mlp<3, 3, 2, false, false>(z, x, y, wfrag, bias, M, C, ncu, s);         // ... M0 (40 channels)
-    if (ks1 == 6 && ht == 6) return C == 96 ? launch_mlp<6, 6, 3, true, true>(z, x, y, wfrag, bias, M, C, ncu, s) : hipErrorInvalidConfiguration;
-    if (ks1 == 5 && ht == 5) return C == 80 ? launch_mlp<5, 5, 3, true, false>(z, x, y, wfrag, bias, M, C, ncu, s) : hipErrorInvalidConfiguration;
-    return hipErrorInvalidConfiguration;
+    return row->launch(z, x, y, wfrag, bias, M, C, ncu, s);
 }
 
 }  // namespace rcx

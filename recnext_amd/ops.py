@@ -675,6 +675,15 @@ def channel_mlp_supported(m, c, hidden, dtype):
     return channel_mlp_hidden(m, c, hidden, dtype) > 0
 
 
+def _mlp_tiles(c, hidden):
+    """(KS1, HT, CT) of a channel mixer of C channels and `hidden` (a multiple of 32) units: k-steps of the first product, hidden tiles, output tiles -- the
+    rule of rcx_mlp.hip's mlp_ks1 / mlp_ct (tests/test_mlp768_cpu.py holds the two together through rcx_channel_mlp_pack_bytes)."""
+    ks1, ht, ct = -(-c // 16), hidden // 32, -(-c // 32)
+    if c > 128 and ct % 2:                  # the streamed kernels write y in halves of two output tiles: one more tile of zero rows
+        ct += 1
+    return ks1, ht, ct
+
+
 def pack_channel_mlp(w1, b1, w2, b2, hidden_to=None):
     """The two BN-folded 1x1 convs of a channel mixer -> (wfrag, bias, H) for channel_mlp: w1 (H0, C[, 1, 1]), b1 (H0) | None, w2 (C, H0[, 1, 1]), b2 (C) | None;
     hidden_to: the padded hidden width H (channel_mlp_hidden; default the next multiple of 32).
@@ -694,9 +703,7 @@ def pack_channel_mlp(w1, b1, w2, b2, hidden_to=None):
     hp = -(-h0 // 32) * 32 if hidden_to is None else int(hidden_to)
     if hp % 32 or hp < h0:
         raise ValueError(f"hidden_to={hidden_to} must be a multiple of 32 and at least {h0}")
-    ks1, ht, ct = -(-c // 16), hp // 32, -(-c // 32)
-    if c > 128 and ct % 2:                  # the streamed kernels write y in halves of two output tiles: one more tile of zero rows (rcx_mlp.hip mlp_shape)
-        ct += 1
+    ks1, ht, ct = _mlp_tiles(c, hp)
     w1p = torch.zeros(32 * ht, 16 * ks1, dtype=torch.bfloat16, device=dev)
     w1p[:h0, :c] = w1.to(torch.bfloat16)
     f1 = w1p.view(ht, 32, ks1, 2, 8).permute(0, 2, 3, 1, 4)                    # [ht, ks, h, m, j]
@@ -735,9 +742,7 @@ def channel_mlp(z, x, wfrag, bias, hidden):
     lib = _lib.load()
     if wfrag.dtype != torch.bfloat16 or wfrag.numel() * 2 != lib.rcx_channel_mlp_pack_bytes(c, hidden) or not wfrag.is_contiguous():
         raise ValueError("wfrag is not the pack of pack_channel_mlp for this (C, H)")
-    ct = -(-c // 32)
-    ct += 1 if c > 128 and ct % 2 else 0
-    _check_pack(bias, torch.float32, hidden + 32 * ct, x.device, "bias")     # the kernel copies 32 (H/32 + CT) floats into LDS unconditionally
+    _check_pack(bias, torch.float32, hidden + 32 * _mlp_tiles(c, hidden)[2], x.device, "bias")     # the kernel copies 32 (H/32 + CT) floats into LDS unconditionally
     _check_pack(wfrag, torch.bfloat16, wfrag.numel(), x.device, "wfrag")
     if z.device != x.device:
         raise ValueError("z and x must be on the same device")

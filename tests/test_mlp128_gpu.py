@@ -3,32 +3,17 @@ each walking its own 32-token tiles, one barrier after the prologue.  Against th
 test_mlp_gpu.py::test_fused_channel_mlp_against_float64_and_the_gemm_path, at the shapes where this form can go wrong: waves without a tile, fewer tiles than
 waves, ragged last tiles, several workgroups, a padded hidden layer, and more tiles than the grid has wave slots (waves that loop)."""
 import functools
-import math
 
 import pytest
 import torch
 
 from tests import guard
+from tests.mlp_common import check, dev, operands, reference
 
 pytestmark = pytest.mark.gpu
 
 C = 128
 NW = 8                                                   # waves of a workgroup; one persistent workgroup per compute unit
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def _reference(z, x, w1, b1, w2, b2):
-    """float64 on the CPU: the operands as the kernel sees them (bf16 values), exact erf GELU, no intermediate rounding."""
-    z64, x64 = z.double().cpu(), x.double().cpu()
-    n, c, h, w = z64.shape
-    zz = z64.permute(0, 2, 3, 1).reshape(-1, c)
-    hid = zz @ w1.double().cpu().t() + b1.double().cpu()
-    hid = 0.5 * hid * (1.0 + torch.erf(hid / math.sqrt(2.0)))
-    out = hid @ w2.double().cpu().t() + b2.double().cpu()
-    return x64 + out.reshape(n, h, w, c).permute(0, 3, 1, 2)
 
 
 def _looping_case():
@@ -55,12 +40,7 @@ def _operands(which):
     """The case's operands, pack and plain result: made once, shared by the tests, never modified."""
     from recnext_amd import ops
     n, hid, h, w = _case(which)
-    g = torch.Generator(device="cpu").manual_seed(C * 1000 + hid + h + 7 * w)
-    rb = lambda *s, sc=1.0: (torch.randn(*s, generator=g) * sc).to(torch.bfloat16)
-    z = rb(n, C, h, w).to(dev()).contiguous(memory_format=torch.channels_last)
-    x = rb(n, C, h, w).to(dev()).contiguous(memory_format=torch.channels_last)
-    w1, b1 = rb(hid, C, sc=(2.0 / C) ** 0.5).to(dev()), rb(hid, sc=0.3).to(dev())
-    w2, b2 = rb(C, hid, sc=(1.0 / hid) ** 0.5).to(dev()), rb(C, sc=0.3).to(dev())
+    z, x, w1, b1, w2, b2 = operands(n, C, hid, h, w, seed=C * 1000 + hid + h + 7 * w)
     hp = ops.channel_mlp_hidden(n * h * w, C, hid, torch.bfloat16)
     assert hp == 256                                     # 240 is padded with zero units
     wfrag, bias, hp2 = ops.pack_channel_mlp(w1, b1, w2, b2, hidden_to=hp)
@@ -76,11 +56,8 @@ def test_resident_channel_mlp_against_float64_and_the_gemm_path(which):
     z, x, w1, b1, w2, b2, wfrag, bias, hp, y = _operands(which)
     assert y.shape == x.shape and y.dtype == torch.bfloat16 and y.is_contiguous(memory_format=torch.channels_last)
     assert torch.equal(y, ops.channel_mlp(z, x, wfrag, bias, hp)), "not deterministic"
-    ref = _reference(z, x, w1, b1, w2, b2)
-    err = (y.double().cpu() - ref).abs()
-    tol = 1e-2 + 1e-2 * ref.abs()
-    print(f"\n{(n, C, hid, h, w)}: worst err / tol {float((err / tol).max()):.3f}, max |ref| {float(ref.abs().max()):.2f}")
-    assert bool((err <= tol).all())
+    ref = reference(z, x, w1, b1, w2, b2)
+    err = check(y, ref, (n, C, hid, h, w))
     zz = z.permute(0, 2, 3, 1).reshape(-1, C)
     lib = torch.nn.functional.linear(torch.nn.functional.gelu(torch.nn.functional.linear(zz, w1, b1)), w2, b2)
     lib = x + lib.view(n, h, w, C).permute(0, 3, 1, 2)

@@ -1,26 +1,12 @@
 """The 256-channel channel mixer (C = 256, H = 512: the 14 x 14 stage of RecNeXt-M3 / A3, two waves per SIMD, 256 tokens a workgroup) against the float64
 formula at the bar of tests/test_mlp_gpu.py: the bench shape (one round), more tokens than one round (the workgroups loop), ragged token counts, fewer tokens
 than one workgroup, the hidden layer 480 padded to 512, and repeated launches that must agree bit for bit."""
-import math
-
 import pytest
 import torch
 
+from tests.mlp_common import check, operands, reference
+
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def _operands(n, c, hid, h, w, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    rb = lambda *s, sc=1.0: (torch.randn(*s, generator=g) * sc).to(torch.bfloat16)
-    z = rb(n, c, h, w).to(dev()).contiguous(memory_format=torch.channels_last)
-    x = rb(n, c, h, w).to(dev()).contiguous(memory_format=torch.channels_last)
-    w1, b1 = rb(hid, c, sc=(2.0 / c) ** 0.5).to(dev()), rb(hid, sc=0.3).to(dev())
-    w2, b2 = rb(c, hid, sc=(1.0 / hid) ** 0.5).to(dev()), rb(c, sc=0.3).to(dev())
-    return z, x, w1, b1, w2, b2
 
 
 def _run(z, x, w1, b1, w2, b2):
@@ -31,16 +17,6 @@ def _run(z, x, w1, b1, w2, b2):
     assert hp == 512
     wfrag, bias, _ = ops.pack_channel_mlp(w1, b1, w2, b2, hidden_to=hp)
     return ops.channel_mlp(z, x, wfrag, bias, hp), (wfrag, bias, hp)
-
-
-def _reference(z, x, w1, b1, w2, b2):
-    """float64 on the CPU from the bf16 operands, exact erf GELU, no intermediate rounding (as tests/test_mlp_gpu.py)."""
-    z64, x64 = z.double().cpu(), x.double().cpu()
-    n, c, h, w = z64.shape
-    hid = z64.permute(0, 2, 3, 1).reshape(-1, c) @ w1.double().cpu().t() + b1.double().cpu()
-    hid = 0.5 * hid * (1.0 + torch.erf(hid / math.sqrt(2.0)))
-    out = hid @ w2.double().cpu().t() + b2.double().cpu()
-    return x64 + out.reshape(n, h, w, c).permute(0, 3, 1, 2)
 
 
 # (n, c, hidden, h, w): M = n h w tokens; one workgroup = 256 tokens, one wave = 32
@@ -54,20 +30,16 @@ CASES = [(256, 256, 512, 14, 14),        # the bench shape: 50 176 tokens = 196 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c)))
 def test_channel_mlp_256_against_float64(case):
     n, c, hid, h, w = case
-    ops_in = _operands(n, c, hid, h, w, seed=c * 1000 + hid + h + n)
+    ops_in = operands(n, c, hid, h, w, seed=c * 1000 + hid + h + n)
     y, _ = _run(*ops_in)
     assert y.shape == ops_in[1].shape and y.dtype == torch.bfloat16 and y.is_contiguous(memory_format=torch.channels_last)
-    ref = _reference(*ops_in)
-    err = (y.double().cpu() - ref).abs()
-    tol = 1e-2 + 1e-2 * ref.abs()
-    print(f"\n{case}: worst err / tol {float((err / tol).max()):.3f}, mean |err| {float(err.mean()):.2e}")
-    assert bool((err <= tol).all())
+    check(y, reference(*ops_in), case)
 
 
 @pytest.mark.parametrize("case", [(256, 256, 512, 14, 14), (3, 256, 512, 14, 14)], ids=lambda c: "x".join(map(str, c)))
 def test_channel_mlp_256_is_deterministic(case):
     n, c, hid, h, w = case
-    z, x, w1, b1, w2, b2 = _operands(n, c, hid, h, w, seed=5)
+    z, x, w1, b1, w2, b2 = operands(n, c, hid, h, w, seed=5)
     y, (wfrag, bias, hp) = _run(z, x, w1, b1, w2, b2)
     from recnext_amd import ops
     for _ in range(8):

@@ -1,29 +1,14 @@
 """The 512-channel channel mixer of the 7 x 7 stage in one launch (rcx_mlp.hip k_channel_mlp_wide: C = 512, H = 1024, offered from a token count M_min upward)
 against the float64 formula on the same bf16 operands and against the four-launch library chain it replaces -- the assertions of
 test_mlp_gpu.py::test_fused_channel_mlp_against_float64_and_the_gemm_path on shapes chosen from M_min, which is probed, not hard-coded."""
-import math
-
 import pytest
 import torch
+
+from tests.mlp_common import check, dev, operands, reference
 
 pytestmark = pytest.mark.gpu
 
 C, HID = 512, 1024
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def _reference(z, x, w1, b1, w2, b2):
-    """float64 on the CPU: the operands as the kernel sees them (bf16 values), exact erf GELU, no intermediate rounding."""
-    z64, x64 = z.double().cpu(), x.double().cpu()
-    n, c, h, w = z64.shape
-    zz = z64.permute(0, 2, 3, 1).reshape(-1, c)
-    hid = zz @ w1.double().cpu().t() + b1.double().cpu()
-    hid = 0.5 * hid * (1.0 + torch.erf(hid / math.sqrt(2.0)))
-    out = hid @ w2.double().cpu().t() + b2.double().cpu()
-    return x64 + out.reshape(n, h, w, c).permute(0, 3, 1, 2)
 
 
 def _m_min():
@@ -51,17 +36,6 @@ def _cases():
     return {"smallest": (na, C, HID, 7, 7), "ragged": (nb, C, HID, 5, 9), "hidden960": (na + 1, C, 960, 7, 7)}
 
 
-def _operands(case):
-    n, c, hid, h, w = case
-    g = torch.Generator(device="cpu").manual_seed(c * 1000 + hid + h)
-    rb = lambda *s, sc=1.0: (torch.randn(*s, generator=g) * sc).to(torch.bfloat16)
-    z = rb(n, c, h, w).to(dev()).contiguous(memory_format=torch.channels_last)
-    x = rb(n, c, h, w).to(dev()).contiguous(memory_format=torch.channels_last)
-    w1, b1 = rb(hid, c, sc=(2.0 / c) ** 0.5).to(dev()), rb(hid, sc=0.3).to(dev())
-    w2, b2 = rb(c, hid, sc=(1.0 / hid) ** 0.5).to(dev()), rb(c, sc=0.3).to(dev())
-    return z, x, w1, b1, w2, b2
-
-
 @pytest.mark.parametrize("which", ["smallest", "ragged", "hidden960"])
 def test_wide_channel_mlp_against_float64_and_the_gemm_path(which):
     from recnext_amd import ops
@@ -73,7 +47,7 @@ def test_wide_channel_mlp_against_float64_and_the_gemm_path(which):
         assert m - h * w < _m_min() <= m
     if which == "ragged":
         assert m % 64 and m % 32
-    z, x, w1, b1, w2, b2 = _operands(case)
+    z, x, w1, b1, w2, b2 = operands(n, c, hid, h, w, seed=c * 1000 + hid + h)
     hp = ops.channel_mlp_hidden(m, c, hid, torch.bfloat16)
     assert hp == 1024
     wfrag, bias, hp2 = ops.pack_channel_mlp(w1, b1, w2, b2, hidden_to=hp)
@@ -84,11 +58,8 @@ def test_wide_channel_mlp_against_float64_and_the_gemm_path(which):
     if which == "ragged":                                # exchange-buffer and barrier hazards would show as a launch that differs
         for _ in range(40):
             assert torch.equal(y, ops.channel_mlp(z, x, wfrag, bias, hp)), "not deterministic over repeated launches"
-    ref = _reference(z, x, w1, b1, w2, b2)
-    err = (y.double().cpu() - ref).abs()
-    tol = 1e-2 + 1e-2 * ref.abs()
-    print(f"\n{case}: worst err / tol {float((err / tol).max()):.3f}, max |ref| {float(ref.abs().max()):.2f}")
-    assert bool((err <= tol).all())
+    ref = reference(z, x, w1, b1, w2, b2)
+    err = check(y, ref, case)
     zz = z.permute(0, 2, 3, 1).reshape(-1, c)
     lib = torch.nn.functional.linear(torch.nn.functional.gelu(torch.nn.functional.linear(zz, w1, b1)), w2, b2)
     lib = x + lib.view(n, h, w, c).permute(0, 3, 1, 2)

@@ -35,3 +35,13 @@ def test_pack_channel_mlp_round_trips(c, hp, ks1, ht, ct, hidden):
                 w2_back.view(ct, 32, ht, 32)[:, :, :, ops._mlp_acc_unit(8 * q + j, h)] = f2[:, :, q, h, :, j].permute(1, 2, 0).float()
     assert torch.equal(2.0 * w2_back[:c, :hidden], w2.float()) and not bool(w2_back[:, hidden:].any())
     assert torch.equal(bias[:hidden], b1.float()) and not bool(bias[hidden:hp].any()) and torch.equal(bias[hp:hp + c], b2.float())
+
+
+def test_tile_rule_is_the_librarys():
+    """ops._mlp_tiles (Python) and mlp_shape (rcx_mlp.hip) state the same (KS1, HT, CT) rule: the pack they imply has the size the library reports."""
+    from recnext_amd import _lib, ops
+    lib = _lib.load()
+    for c in range(8, 641, 8):
+        for hidden in (32, 96, 256, 768, 1024):
+            ks1, ht, ct = ops._mlp_tiles(c, hidden)
+            assert (ht * ks1 + 2 * ct * ht) * 1024 == lib.rcx_channel_mlp_pack_bytes(c, hidden), (c, hidden)

@@ -1,27 +1,12 @@
 """The fused channel mixer (rcx_channel_mlp_fwd: x + W2 gelu(W1 z + b1) + b2 in one launch) against the float64 formula on the same bf16 inputs and
 weights, and against the library path it replaces (two GEMMs + GELU + add in bf16).  Reference: model/recnext.py:125-132, :157-158, :169-171."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
+from tests.mlp_common import check, dev, operands, reference
+
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def _reference(z, x, w1, b1, w2, b2):
-    """float64 on the CPU: the operands as the kernel sees them (bf16 values), exact erf GELU, no intermediate rounding."""
-    z64, x64 = z.double().cpu(), x.double().cpu()
-    n, c, h, w = z64.shape
-    zz = z64.permute(0, 2, 3, 1).reshape(-1, c)
-    hid = zz @ w1.double().cpu().t() + b1.double().cpu()
-    hid = 0.5 * hid * (1.0 + torch.erf(hid / math.sqrt(2.0)))
-    out = hid @ w2.double().cpu().t() + b2.double().cpu()
-    return x64 + out.reshape(n, h, w, c).permute(0, 3, 1, 2)
 
 
 @pytest.mark.parametrize("case", [(2, 64, 128, 56, 56), (3, 128, 256, 28, 28), (2, 64, 120, 9, 11), (1, 48, 96, 56, 56), (2, 40, 80, 13, 7), (2, 56, 112, 28, 28),
@@ -31,12 +16,7 @@ def _reference(z, x, w1, b1, w2, b2):
 def test_fused_channel_mlp_against_float64_and_the_gemm_path(case):
     from recnext_amd import ops
     n, c, hid, h, w = case
-    g = torch.Generator(device="cpu").manual_seed(c * 1000 + hid + h)
-    rb = lambda *s, sc=1.0: (torch.randn(*s, generator=g) * sc).to(torch.bfloat16)
-    z = rb(n, c, h, w).to(dev()).contiguous(memory_format=torch.channels_last)
-    x = rb(n, c, h, w).to(dev()).contiguous(memory_format=torch.channels_last)
-    w1, b1 = rb(hid, c, sc=(2.0 / c) ** 0.5).to(dev()), rb(hid, sc=0.3).to(dev())
-    w2, b2 = rb(c, hid, sc=(1.0 / hid) ** 0.5).to(dev()), rb(c, sc=0.3).to(dev())
+    z, x, w1, b1, w2, b2 = operands(n, c, hid, h, w, seed=c * 1000 + hid + h)
     hp = ops.channel_mlp_hidden(n * h * w, c, hid, torch.bfloat16)
     assert hp >= hid and hp % 32 == 0 and hp - hid < 64
     wfrag, bias, hp2 = ops.pack_channel_mlp(w1, b1, w2, b2, hidden_to=hp)
@@ -44,11 +24,8 @@ def test_fused_channel_mlp_against_float64_and_the_gemm_path(case):
     y = ops.channel_mlp(z, x, wfrag, bias, hp)
     assert y.shape == x.shape and y.dtype == torch.bfloat16 and y.is_contiguous(memory_format=torch.channels_last)
     assert torch.equal(y, ops.channel_mlp(z, x, wfrag, bias, hp)), "not deterministic"
-    ref = _reference(z, x, w1, b1, w2, b2)
-    err = (y.double().cpu() - ref).abs()
-    tol = 1e-2 + 1e-2 * ref.abs()                                    # north_star's bf16 bar
-    print(f"\n{case}: worst err / tol {float((err / tol).max()):.3f}, max |ref| {float(ref.abs().max()):.2f}")
-    assert bool((err <= tol).all())
+    ref = reference(z, x, w1, b1, w2, b2)
+    err = check(y, ref, case)
     # the path it replaces, all in bf16 (four launches; it rounds the hidden layer twice and the output twice): the fused kernel, which rounds the hidden
     # layer once (after the GELU) and the output once, is at least as close to the float64 result
     zz = z.permute(0, 2, 3, 1).reshape(-1, c)

@@ -4,20 +4,17 @@ which a step can go wrong: one token, a full tile and a one-token tile, one toke
 has, a padded hidden width, the aliased call (z is x) and 40 repeated launches.  Every result is checked against the float64 formula on the same bf16 operands
 at test_mlp_gpu.py's bar; the pinned form keeps hidden_tile_ring's float32 operations and their order, so that bar's margins hold."""
 import functools
-import math
 
 import pytest
 import torch
+
+from tests.mlp_common import check, dev, operands, reference
 
 pytestmark = pytest.mark.gpu
 
 # caller -> (C, hidden, padded-from hidden, tokens of a workgroup's block)
 KERNELS = {"small64": (64, 128, 120, 384), "stream192": (192, 384, 360, 128), "pair256": (256, 512, 480, 256), "res128": (128, 256, 240, 256)}
 CASES = ("one", "tile_and_one", "block_and_one", "looping", "padded")
-
-
-def dev():
-    return torch.device("cuda:0")
 
 
 def _plane(kernel, case):
@@ -38,41 +35,18 @@ def _plane(kernel, case):
     return n, 56, 57, hid
 
 
-def _reference(z, x, w1, b1, w2, b2):
-    """float64 on the CPU: the operands as the kernel sees them (bf16 values), exact erf GELU, no intermediate rounding."""
-    z64, x64 = z.double().cpu(), x.double().cpu()
-    n, c, h, w = z64.shape
-    zz = z64.permute(0, 2, 3, 1).reshape(-1, c)
-    hid = zz @ w1.double().cpu().t() + b1.double().cpu()
-    hid = 0.5 * hid * (1.0 + torch.erf(hid / math.sqrt(2.0)))
-    out = hid @ w2.double().cpu().t() + b2.double().cpu()
-    return x64 + out.reshape(n, h, w, c).permute(0, 3, 1, 2)
-
-
 @functools.lru_cache(maxsize=None)
 def _operands(kernel, case):
     """The case's operands, pack and plain result: made once, shared by the tests, never modified."""
     from recnext_amd import ops
     c = KERNELS[kernel][0]
     n, h, w, hid = _plane(kernel, case)
-    g = torch.Generator(device="cpu").manual_seed(c * 1000 + hid + 7 * h + w)
-    rb = lambda *s, sc=1.0: (torch.randn(*s, generator=g) * sc).to(torch.bfloat16)
-    z = rb(n, c, h, w).to(dev()).contiguous(memory_format=torch.channels_last)
-    x = rb(n, c, h, w).to(dev()).contiguous(memory_format=torch.channels_last)
-    w1, b1 = rb(hid, c, sc=(2.0 / c) ** 0.5).to(dev()), rb(hid, sc=0.3).to(dev())
-    w2, b2 = rb(c, hid, sc=(1.0 / hid) ** 0.5).to(dev()), rb(c, sc=0.3).to(dev())
+    z, x, w1, b1, w2, b2 = operands(n, c, hid, h, w, seed=c * 1000 + hid + 7 * h + w)
     hp = ops.channel_mlp_hidden(n * h * w, c, hid, torch.bfloat16)
     assert hp == KERNELS[kernel][1]                      # the padded case runs the same kernel on zero units
     wfrag, bias, hp2 = ops.pack_channel_mlp(w1, b1, w2, b2, hidden_to=hp)
     assert hp2 == hp
     return z, x, w1, b1, w2, b2, wfrag, bias, hp
-
-
-def _check(y, ref, what):
-    err = (y.double().cpu() - ref).abs()
-    tol = 1e-2 + 1e-2 * ref.abs()                        # test_mlp_gpu.py's bar
-    print(f"\n{what}: worst err / tol {float((err / tol).max()):.3f}, max |ref| {float(ref.abs().max()):.2f}")
-    assert bool((err <= tol).all())
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -82,7 +56,7 @@ def test_ring_step_against_float64(kernel, case):
     z, x, w1, b1, w2, b2, wfrag, bias, hp = _operands(kernel, case)
     y = ops.channel_mlp(z, x, wfrag, bias, hp)
     assert y.shape == x.shape and y.dtype == torch.bfloat16 and y.is_contiguous(memory_format=torch.channels_last)
-    _check(y, _reference(z, x, w1, b1, w2, b2), f"{kernel} {case} {tuple(z.shape)}")
+    check(y, reference(z, x, w1, b1, w2, b2), f"{kernel} {case} {tuple(z.shape)}")
 
 
 @pytest.mark.parametrize("kernel", list(KERNELS))
@@ -91,7 +65,7 @@ def test_ring_step_aliased_call(kernel):
     from recnext_amd import ops
     z, _, w1, b1, w2, b2, wfrag, bias, hp = _operands(kernel, "block_and_one")
     y = ops.channel_mlp(z, z, wfrag, bias, hp)
-    _check(y, _reference(z, z, w1, b1, w2, b2), f"{kernel} aliased {tuple(z.shape)}")
+    check(y, reference(z, z, w1, b1, w2, b2), f"{kernel} aliased {tuple(z.shape)}")
 
 
 @pytest.mark.parametrize("kernel", list(KERNELS))
