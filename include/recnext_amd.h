@@ -405,6 +405,25 @@ int rcx_ls_share_fwd(const void* x, void* r, void* t, const float* w_rep, const 
                      long long src_pixel_stride, int B, int H, int W, int C, int split, int dtype, void* stream);
 
 /*
+ * Downsample.token_mixer of the LSNet-style RecNeXt-T / S / B and of their share-channel variants (lsnet/model/recattn.py:254-263,
+ * lsnet/model/recattn_share_channel.py:223-232): the grouped 5x5 stride-2 ConvNorm with groups = gcd(Cin, Cout), eval mode, the BatchNorm folded
+ * into the pack, in one launch without a workspace:
+ *     y = conv2d(x, w, bias, kernel 5, stride 2, padding 2, groups)        Ho = ceil(H / 2), Wo = ceil(W / 2)
+ * x: N x H x W x Cin and y: N x Ho x Wo x Cout, NHWC of `dtype` (float32, bf16 or f16), aligned to one element (wider alignment is used where
+ * x has it).  With ci = Cin / groups and co = Cout / groups, wpack is float32 (k, k, ci, Cout):
+ *     wpack[((ky*k + kx)*ci + j)*Cout + o] = weight[o][j][ky][kx]
+ * bias: float32 (Cout) or NULL.  float32 arithmetic; each output is one thread's fmaf chain over (ky, kx, j) from the bias, rounded once at its
+ * store: bitwise repeatable, and the tiling depends on (H, W, Cin, Cout, groups, dtype) alone, so an image's result does not depend on the batch.
+ * Supported (rcx_grouped_conv2d_supported: 1 / 0): k = 5, stride = 2, groups >= 1 dividing Cin and Cout, ci and co each 1 .. 4 (the registered
+ * models use 1 -> 2, 2 -> 3 and 3 -> 4), any N, H, W >= 1, fewer than 2^31 elements in x and in y; else RCX_ERR_UNSUPPORTED.  RCX_ERR_BAD_ARG
+ * for a NULL x / y / wpack, a non-positive extent, an unknown dtype, a misaligned pointer or a y that aliases x or a pack.  Both are decided
+ * before any HIP call.
+ */
+int rcx_grouped_conv2d_supported(int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype);
+int rcx_grouped_conv2d_fwd(const void* x, void* y, const float* wpack, const float* bias, int N, int H, int W, int Cin, int Cout, int groups,
+                           int k, int stride, int dtype, void* stream);
+
+/*
  * Backward of rcx_linear_attention_fwd(the gradients engine.py:48-64 needs through RecAttn2d, model/recattn.py:16-28 / :39-51):
  *   given gout = dL/dout (B x n x C), writes gq = dL/dqpre, gk = dL/dkpre, gv = dL/dv (all B x n x C, `dtype`); dL/dpe = gout is the
  *   caller's.  float32 arithmetic, deterministic (fixed summation order).  C/heads at most 64.

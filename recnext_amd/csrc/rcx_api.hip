@@ -1253,6 +1253,30 @@ int rcx_ls_la3_tiled_fwd(const void* x, void* r, void* t, const float* w_rep, co
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_ls_la3_tiled_fwd");
 }
 
+int rcx_grouped_conv2d_supported(int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype)
+{
+    return rcx::ls_down_applicable(N, H, W, Cin, Cout, groups, k, stride, dtype) ? 1 : 0;
+}
+
+int rcx_grouped_conv2d_fwd(const void* x, void* y, const float* wpack, const float* bias, int N, int H, int W, int Cin, int Cout, int groups, int k,
+                           int stride, int dtype, void* stream)
+{
+    if (!x || !y || !wpack) return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_fwd: null pointer");
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || groups <= 0)
+        return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_fwd: non-positive extent N=%d H=%d W=%d Cin=%d Cout=%d groups=%d", N, H, W, Cin, Cout, groups);
+    if (!known_dtype(dtype)) return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_fwd: unknown dtype %d", dtype);
+    if (y == x || (const void*)wpack == x || (const void*)wpack == y || (bias && ((const void*)bias == x || (const void*)bias == y)))
+        return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_fwd: y must alias neither x nor a pack");
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2;
+    if ((size_t)x % es || (size_t)y % es || (size_t)wpack % 4 || (size_t)bias % 4)
+        return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_fwd: x and y must be aligned to one element (%zu bytes), the packs to 4 bytes", es);
+    if (!rcx::ls_down_applicable(N, H, W, Cin, Cout, groups, k, stride, dtype))
+        return fail(RCX_ERR_UNSUPPORTED, "rcx_grouped_conv2d_fwd: Cin=%d, Cout=%d, groups=%d, k=%d, stride=%d: k = 5, stride = 2, groups dividing Cin and Cout, "
+                                         "1 .. 4 channels a group in and out, fewer than 2^31 elements in x and in y", Cin, Cout, groups, k, stride);
+    hipError_t e = rcx::ls_down_fwd(x, y, wpack, bias, N, H, W, Cin, Cout, groups, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rcx_grouped_conv2d_fwd");
+}
+
 int rcx_ls_share_supported(int B, int H, int W, int C, int split, int n_src, int dtype)
 {
     return rcx::ls_share_applicable(B, H, W, C, split, n_src, split, dtype) ? 1 : 0;

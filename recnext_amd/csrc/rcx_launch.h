@@ -210,6 +210,10 @@ constexpr int kLsShareMaxSrc = 8;
 bool ls_share_applicable(int B, int H, int W, int C, int split, int n_src, long long stride, int dtype);
 hipError_t ls_share_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const void* const* srcs, int n_src, long long stride,
                         int B, int H, int W, int C, int split, int dtype, hipStream_t s);
+// rcx_lsdown.hip: Downsample.token_mixer of the T / S / B families, the grouped 5x5 stride-2 conv (1 .. 4 channels a group in and out), one launch
+bool ls_down_applicable(int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype);
+hipError_t ls_down_fwd(const void* x, void* y, const float* wpack, const float* bias, int N, int H, int W, int Cin, int Cout, int groups, int dtype,
+                       hipStream_t s);
 hipError_t recattn_qkcore(const float* d, const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe, float* out, void* workspace,
                           int B, int Hp, int Wp, int C, int heads, hipStream_t s);
 

@@ -11,7 +11,9 @@ depthwise conv and the library's ``RecAttn2d`` on a contiguous slice remain for 
 form (``_token_half_train``): BatchNorms on batch statistics under autograd, nothing folded, the depthwise convs and the attention cores with HIP
 forward and backward kernels -- ``RecAttn2d``'s own training branch at stages 0-2 (the 96-wide heads of S / B's stage 2 on the wide core,
 ``rcx_linear_attention_wide_*``) and ``LinearAttention3.forward`` at stage 3 (q / k of s/2 and v of s channels: the wide core) -- and library GEMMs
-for the 1x1 projections.  A CPU tensor raises.  The stem, Downsample's grouped conv and the classifier are PyTorch-ROCm library operators.
+for the 1x1 projections.  A CPU tensor raises.  Downsample's grouped 5x5 stride-2 conv (:254-263) is ONE HIP launch (``ops.grouped_conv2d``) in an
+inference forward after ``models.use_hip_downsample`` (opt-in; ``speed.build_inference_model`` calls it); in training, where a gradient is needed and
+on a CPU tensor it stays the library's conv.  The stem and the classifier are PyTorch-ROCm library operators.
 
 RecAttn2d's ``stage -> LinearAttention1 | 2`` label (:119) is cosmetic: the two are the same function (the reference asserts it, :481-501).
 """
@@ -287,15 +289,58 @@ class MetaNeXtBlock(nn.Module):
 
 
 class Downsample(nn.Module):
+    """:254-263.  After ``models.use_hip_downsample`` an inference forward runs ``token_mixer`` -- the grouped 5x5 stride-2 ConvNorm with
+    gcd(Cin, Cout) groups -- as ONE HIP launch (``ops.grouped_conv2d``) on a float32 pack folded by ``_folded``, the same for the ConvNorm and its
+    ``replace_batchnorm``ed nn.Conv2d.  Decided per call (``_hip_conv``); everything else keeps the library operators."""
+
     def __init__(self, in_channels, out_channels, mlp_ratio=2, act_layer=nn.GELU, kernel_size=5, stage=0, drop_path=0):
         super().__init__()
         self.token_mixer = ConvNorm(in_channels, out_channels, kernel_size=kernel_size, padding=(kernel_size - 1) // 2, stride=2,
                                     groups=math.gcd(in_channels, out_channels))
         self.channel_mixer = mlp(out_channels, out_channels * mlp_ratio, act_layer=act_layer)
         self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
+        self._hip = False                       # set by models.use_hip_downsample; a plain attribute, so the state_dict keys stay
+        self._pack_key = None
+        self._pack = None
+
+    def _conv(self):
+        """token_mixer's nn.Conv2d if token_mixer is still this family's ConvNorm or its fused nn.Conv2d, else None (a replaced child)."""
+        tm = self.token_mixer
+        if isinstance(tm, nn.Conv2d):
+            return tm
+        if isinstance(tm, _ConvNorm) and isinstance(tm.conv, nn.Conv2d) and isinstance(tm.norm, nn.BatchNorm2d):
+            return tm.conv
+        return None
+
+    def _hip_conv(self, x):
+        """Whether this call takes the HIP launch: rerouted, eval mode, a GPU tensor, no gradient wanted anywhere, no autocast, and a kernel for the shape."""
+        if not self.__dict__.get("_hip") or self.training or not x.is_cuda or x.dim() != 4 or torch.is_autocast_enabled():
+            return False
+        conv = self._conv()
+        if conv is None or conv.kernel_size != (5, 5) or conv.stride != (2, 2) or conv.padding != (2, 2) or conv.dilation != (1, 1) \
+                or conv.padding_mode != "zeros" or conv.in_channels != x.shape[1]:
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.token_mixer.parameters())):
+            return False
+        n, _, h, w = x.shape
+        return ops.grouped_conv2d_supported(n, h, w, conv.in_channels, conv.out_channels, conv.groups, 5, 2, x.dtype)
+
+    def packed_params(self):
+        """(wpack, bias): the folded token_mixer as ops.grouped_conv2d takes it, rebuilt when a parameter or buffer changes."""
+        tm = self.token_mixer
+        key = tuple((t.data_ptr(), t._version, t.dtype, t.device) for t in list(tm.parameters()) + list(tm.buffers()))
+        if key != self.__dict__.get("_pack_key"):              # (a whole-model pickle from before the reroute has no such attribute)
+            with torch.no_grad():
+                w, b = _folded(tm)
+                self._pack = (ops.pack_grouped_weight(w), None if b is None else b.detach().float().contiguous())
+            self._pack_key = key
+        return self._pack
 
     def forward(self, x):
-        x = self.token_mixer(x)
+        if self._hip_conv(x):
+            x = ops.grouped_conv2d(x, *self.packed_params(), self._conv().groups)
+        else:
+            x = self.token_mixer(x)
         fused = self.__dict__.get("_fused_mlp")
         if fused is not None and not self.training and fused.usable(self.channel_mixer, x, x):
             return fused(x, x)

@@ -248,15 +248,21 @@ def fold_token_mixer_norms(net):
 
 @torch.no_grad()
 def use_hip_downsample(net):
-    """Run each Downsample's depthwise 7x7 stride-2 conv (C -> 2C) on HIP: in eval mode fused with
-    the BatchNorm after it into one kernel, in a training step with a HIP backward and the norm on batch statistics.
+    """Run each Downsample's strided conv on HIP.  M / A families: the depthwise 7x7 stride-2 conv (C -> 2C), in eval
+    mode fused with the BatchNorm after it into one kernel, in a training step with a HIP backward and the norm on batch statistics.  T / S / B
+    families (``lsmodels.Downsample``, the share-channel models' too): the grouped 5x5 stride-2 ConvNorm as one launch (``ops.grouped_conv2d``) in an
+    inference forward; training and forwards that need a gradient keep the library conv.
     ``token_mixer`` and ``norm`` remain the Downsample's direct children (same state_dict keys as the reference, so checkpoints
     load and save unchanged in either order); only the forward is rerouted.  Returns the number of layers rerouted."""
+    from . import lsmodels
     from .dwconv import DownsampleDwConv
     n = 0
     for m in net.modules():
         if isinstance(m, Downsample) and m._hip is None and isinstance(m.token_mixer, nn.Conv2d) and isinstance(m.norm, nn.BatchNorm2d):
             object.__setattr__(m, "_hip", DownsampleDwConv(m.token_mixer, m.norm))
+            n += 1
+        elif isinstance(m, lsmodels.Downsample) and not m.__dict__.get("_hip") and m._conv() is not None:
+            m._hip = True
             n += 1
     return n
 

@@ -1021,3 +1021,8 @@ def recconv2d_input_backward(gy, wpack, wflip, level, k, mode="bilinear", dtype=
                                          _stream(gy.device))
     _lib.check(rc, "rcx_recconv2d_bwd_input")
     return gx
+
+
+# Downsample.token_mixer of the T / S / B families: grouped_conv2d_supported, pack_grouped_weight, grouped_conv2d.  Written in recnext_amd/lsdown.py
+# (with their guard-band cases in tests/test_ls_down_gpu.py) and part of this module's interface.
+from .lsdown import grouped_conv2d, grouped_conv2d_supported, pack_grouped_weight            # noqa: E402, F401

@@ -30,7 +30,7 @@ def build_inference_model(name, device, dtype=torch.bfloat16, token_mixer=None, 
 
     ``fold_mixer_norm`` additionally absorbs the BatchNorm after each HIP token mixer into the mixer's last
     conv (same function, one kernel less per block); it is a no-op for other token mixers.  ``hip_downsample``
-    runs the three strided depthwise Downsample convs (+ their BatchNorm) on the HIP kernels as well.  ``pad_hidden`` lets the
+    runs the three strided Downsample convs (M / A: depthwise 7x7 + BatchNorm; T / S / B: the grouped 5x5) on the HIP kernels as well.  ``pad_hidden`` lets the
     channel mixers' GEMMs run at a zero-padded hidden width (``models.pad_mlp_hidden``: RecNeXt-A's 120 / 240 / 480 -> 128 / 256 / 512).
     ``fused_mlp`` (bf16): ``x + channel_mixer(.)`` of the blocks rcx_channel_mlp_fwd has a kernel for as one HIP launch (``models.use_fused_mlp``).
     ``fused_stem`` (bf16): the stem's two convs and GELU as one HIP launch (``models.use_fused_stem``).
@@ -133,6 +133,7 @@ def main(argv=None):
     ap.add_argument("--dtype", default="bf16", choices=sorted(DTYPES))
     ap.add_argument("--gpus", default=1, type=int, help="ranks (one per GPU); --batch-size is per GPU")
     ap.add_argument("--graph", action="store_true", help="replay the forward as one HIP graph (small batches are bound by the host's launches)")
+    ap.add_argument("--no-hip-downsample", action="store_true", help="keep the Downsample convs on the library (the comparison run)")
     ap.add_argument("--t0", default=T0, type=float)
     ap.add_argument("--t1", default=T1, type=float)
     args = ap.parse_args(argv)
@@ -146,7 +147,7 @@ def main(argv=None):
     ranks = rdist.init("cuda")
     device = str(ranks.device)
     dtype = DTYPES[args.dtype]
-    net = build_inference_model(args.model, device, dtype)
+    net = build_inference_model(args.model, device, dtype, hip_downsample=not args.no_hip_downsample)
     rdist.barrier(ranks)
     with torch.no_grad():                 # speed_gpu.py:40 switches autograd off for the whole process; scoped here
         rate = throughput(args.model, net, device, args.batch_size, args.resolution, dtype, args.t0, args.t1, ranks=ranks, graph=args.graph)
