@@ -424,6 +424,27 @@ int rcx_grouped_conv2d_fwd(const void* x, void* y, const float* wpack, const flo
                            int k, int stride, int dtype, void* stream);
 
 /*
+ * Backward of rcx_grouped_conv2d_fwd: the gradients engine.py's training step (loss.backward() under autocast) needs through Downsample.token_mixer of
+ * the T / S / B families (lsnet/model/recattn.py:254-263, recattn_share_channel.py:223-232), whose BatchNorm stays the caller's operator:
+ *     gx[n,iy,ix,g*ci+j] = sum_{ky,kx,u} wpack[((ky*k+kx)*ci+j)*Cout + g*co+u] * gy[n,(iy+2-ky)/2,(ix+2-kx)/2,g*co+u]   (quotients integral, in the plane)
+ *     gwpack[((ky*k+kx)*ci+j)*Cout + o] = sum_{n,oy,ox} gy[n,oy,ox,o] * x[n,2*oy+ky-2,2*ox+kx-2,g*ci+j],    gb[o] = sum_{n,oy,ox} gy[n,oy,ox,o]
+ * x and gx: N x H x W x Cin, gy: N x Ho x Wo x Cout, NHWC of `dtype`, aligned to one element; gy is read in its own type (no float32 copy).  wpack:
+ * the forward's float32 pack; gwpack: float32 in the same (k, k, ci, Cout) layout; gb: float32 (Cout).  gx may be NULL (no input gradient wanted);
+ * gwpack and gb may be NULL (frozen weights), gb alone too; not all three.  What is given is overwritten, never accumulated into.  float32
+ * arithmetic, no atomics: a gx element is one thread's fmaf chain in the order (ky, kx, u), rounded once at its store, under a tiling that depends on
+ * (H, W, Cin, Cout, groups, dtype) alone (an image's gx does not depend on its batch); gwpack / gb are summed in two stages through the workspace,
+ * P partials of (25 ci + 1) Cout floats, P a function of the arguments (N among them), so repeat launches are bit-identical.
+ * workspace: rcx_grouped_conv2d_bwd_workspace_bytes(...) bytes, aligned to 4, needed when gwpack or gb is given (0 for an unsupported problem).
+ * Supported (rcx_grouped_conv2d_bwd_supported: 1 / 0): what rcx_grouped_conv2d_supported takes; else RCX_ERR_UNSUPPORTED.  RCX_ERR_BAD_ARG for a NULL
+ * x / gy / wpack, three NULL outputs, a non-positive extent, an unknown dtype, a misaligned pointer, or an output or the workspace aliasing an input or
+ * each other; RCX_ERR_WORKSPACE for a workspace smaller than the query.  All decided before any HIP call.
+ */
+int rcx_grouped_conv2d_bwd_supported(int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype);
+size_t rcx_grouped_conv2d_bwd_workspace_bytes(int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype);
+int rcx_grouped_conv2d_bwd(const void* x, const void* gy, const float* wpack, void* gx, float* gwpack, float* gb, void* workspace, size_t workspace_bytes,
+                           int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype, void* stream);
+
+/*
  * Backward of rcx_linear_attention_fwd(the gradients engine.py:48-64 needs through RecAttn2d, model/recattn.py:16-28 / :39-51):
  *   given gout = dL/dout (B x n x C), writes gq = dL/dqpre, gk = dL/dkpre, gv = dL/dv (all B x n x C, `dtype`); dL/dpe = gout is the
  *   caller's.  float32 arithmetic, deterministic (fixed summation order).  C/heads at most 64.

@@ -80,6 +80,9 @@ SIGNATURES = {
     "rcx_ls_la3_tiled_fwd": (_i, [_vp] * 12 + [_sz] + [_i] * 7 + [_vp]),
     "rcx_grouped_conv2d_supported": (_i, [_i] * 9),
     "rcx_grouped_conv2d_fwd": (_i, [_vp] * 4 + [_i] * 9 + [_vp]),
+    "rcx_grouped_conv2d_bwd_supported": (_i, [_i] * 9),
+    "rcx_grouped_conv2d_bwd_workspace_bytes": (_sz, [_i] * 9),
+    "rcx_grouped_conv2d_bwd": (_i, [_vp] * 7 + [_sz] + [_i] * 9 + [_vp]),
     "rcx_ls_share_supported": (_i, [_i] * 7),
     "rcx_ls_share_fwd": (_i, [_vp] * 6 + [_i, ctypes.c_longlong] + [_i] * 6 + [_vp]),
     "rcx_linear_attention_bwd": (_i, [_vp] * 7 + [_i] * 5 + [_vp]),

@@ -1277,6 +1277,49 @@ int rcx_grouped_conv2d_fwd(const void* x, void* y, const float* wpack, const flo
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_grouped_conv2d_fwd");
 }
 
+int rcx_grouped_conv2d_bwd_supported(int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype)
+{
+    return rcx::ls_down_bwd_applicable(N, H, W, Cin, Cout, groups, k, stride, dtype) ? 1 : 0;
+}
+
+size_t rcx_grouped_conv2d_bwd_workspace_bytes(int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype)
+{
+    return rcx::ls_down_bwd_workspace_bytes(N, H, W, Cin, Cout, groups, k, stride, dtype);
+}
+
+int rcx_grouped_conv2d_bwd(const void* x, const void* gy, const float* wpack, void* gx, float* gwpack, float* gb, void* workspace, size_t workspace_bytes,
+                           int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype, void* stream)
+{
+    if (!x || !gy || !wpack) return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_bwd: null pointer");
+    if (!gx && !gwpack && !gb) return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_bwd: null pointer for every output (gx, gwpack and gb)");
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || groups <= 0)
+        return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_bwd: non-positive extent N=%d H=%d W=%d Cin=%d Cout=%d groups=%d", N, H, W, Cin, Cout, groups);
+    if (!known_dtype(dtype)) return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_bwd: unknown dtype %d", dtype);
+    {
+        const void* in[3] = {x, gy, wpack};
+        const void* out[4] = {gx, gwpack, gb, workspace};
+        for (int i = 0; i < 4; ++i) {
+            if (!out[i]) continue;
+            for (int j = 0; j < 3; ++j)
+                if (out[i] == in[j]) return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_bwd: gx, gwpack, gb and the workspace must alias no input");
+            for (int j = i + 1; j < 4; ++j)
+                if (out[i] == out[j]) return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_bwd: gx, gwpack, gb and the workspace must not alias each other");
+        }
+    }
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2;
+    if ((size_t)x % es || (size_t)gy % es || (size_t)gx % es || (size_t)wpack % 4 || (size_t)gwpack % 4 || (size_t)gb % 4 || (size_t)workspace % 4)
+        return fail(RCX_ERR_BAD_ARG, "rcx_grouped_conv2d_bwd: x, gy and gx must be aligned to one element (%zu bytes), the packs, gb and the workspace to 4 bytes", es);
+    if (!rcx::ls_down_bwd_applicable(N, H, W, Cin, Cout, groups, k, stride, dtype))
+        return fail(RCX_ERR_UNSUPPORTED, "rcx_grouped_conv2d_bwd: Cin=%d, Cout=%d, groups=%d, k=%d, stride=%d: k = 5, stride = 2, groups dividing Cin and Cout, "
+                                         "1 .. 4 channels a group in and out, fewer than 2^31 elements in x and in gy", Cin, Cout, groups, k, stride);
+    if (gwpack || gb) {
+        const size_t need = rcx_grouped_conv2d_bwd_workspace_bytes(N, H, W, Cin, Cout, groups, k, stride, dtype);
+        if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace ? workspace_bytes : (size_t)0);
+    }
+    hipError_t e = rcx::ls_down_bwd(x, gy, wpack, gx, gwpack, gb, workspace, N, H, W, Cin, Cout, groups, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rcx_grouped_conv2d_bwd");
+}
+
 int rcx_ls_share_supported(int B, int H, int W, int C, int split, int n_src, int dtype)
 {
     return rcx::ls_share_applicable(B, H, W, C, split, n_src, split, dtype) ? 1 : 0;

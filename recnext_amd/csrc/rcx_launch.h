@@ -214,6 +214,11 @@ hipError_t ls_share_fwd(const void* x, void* r, void* t, const float* w_rep, con
 bool ls_down_applicable(int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype);
 hipError_t ls_down_fwd(const void* x, void* y, const float* wpack, const float* bias, int N, int H, int W, int Cin, int Cout, int groups, int dtype,
                        hipStream_t s);
+// rcx_lsdownbwd.hip: its backward: the input gradient as a gather (one launch), the weight / bias gradient in two stages through the workspace
+bool ls_down_bwd_applicable(int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype);
+size_t ls_down_bwd_workspace_bytes(int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype);
+hipError_t ls_down_bwd(const void* x, const void* gy, const float* wpack, void* gx, float* gw, float* gb, void* workspace, int N, int H, int W, int Cin,
+                       int Cout, int groups, int dtype, hipStream_t s);
 hipError_t recattn_qkcore(const float* d, const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe, float* out, void* workspace,
                           int B, int Hp, int Wp, int C, int heads, hipStream_t s);
 

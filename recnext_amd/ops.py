@@ -1026,3 +1026,5 @@ def recconv2d_input_backward(gy, wpack, wflip, level, k, mode="bilinear", dtype=
 # Downsample.token_mixer of the T / S / B families: grouped_conv2d_supported, pack_grouped_weight, grouped_conv2d.  Written in recnext_amd/lsdown.py
 # (with their guard-band cases in tests/test_ls_down_gpu.py) and part of this module's interface.
 from .lsdown import grouped_conv2d, grouped_conv2d_supported, pack_grouped_weight            # noqa: E402, F401
+# ... and the conv's backward for a training step (rcx_grouped_conv2d_bwd; guard-band cases in tests/test_ls_down_bwd_gpu.py)
+from .lsdown import GroupedConv2dFn, grouped_conv2d_backward, grouped_conv2d_backward_supported, unpack_grouped_weight_grad      # noqa: E402, F401

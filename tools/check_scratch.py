@@ -4,7 +4,8 @@ when a kernel the DEFAULT dispatch reaches has a private segment (registers spil
 instantiations for bf16 / float32 activations of the fused kernels (k_recconv_cpt without TRAIN, k_recconv_cpl14, k_recconv_cpl7b) and the
 tiled step kernels (k_upadd_cpt, k_down5_cpt, k_down7m2_cpt), and every instantiation of the input adjoint (k_recconv_adj_cpl14,
 k_recconv_adj_cpl7), and RecAttn2d's wide-head attention kernels (k_recattn_short_w, k_recattn_kv_w, k_recattn_out_w: every instantiation), and the
-channel mixer's kernels (k_channel_mlp, k_channel_mlp_stream, k_channel_mlp_pair, k_channel_mlp_res128, k_channel_mlp_wide; the 320-channel stream kernel is reported only); the
+channel mixer's kernels (k_channel_mlp, k_channel_mlp_stream, k_channel_mlp_pair, k_channel_mlp_res128, k_channel_mlp_wide; the 320-channel stream kernel is reported only), and the
+backward of the T / S / B grouped Downsample conv (k_ls_down_gx, k_ls_down_gw: every instantiation); the
 training-forward and float16 instantiations and the other matrix-core attention kernels (rcx_qkcore's 32-wide and padded heads) are reported only.
 usage: check_scratch.py file.s [file.s ...]"""
 import re
@@ -63,6 +64,10 @@ for (path, r), name in zip(rows, names):
     elif re.search(r"\dk_lt_(rep|kv|out|conv)I", r["name"]):
         gated = True                                       # the tiled T / S / B token half: every instantiation (by the mangled name: the
         m = re.search(r"k_lt_\w+<[^(]*>", name)                        # kernels of an anonymous namespace lose theirs to the cut above)
+        short = short or (m.group(0) if m else name)
+    elif re.search(r"\dk_ls_down_g[xw]I", r["name"]):
+        gated = True                                       # the grouped Downsample conv's backward: every instantiation
+        m = re.search(r"k_ls_down_g[xw]<[^(]*>", name)
         short = short or (m.group(0) if m else name)
     elif re.match(r"mlp::k_channel_mlp(_pair|_stream|_res128|_wide)?<", short):
         # the channel mixer: every instantiation but the 320-channel stream kernel (ZPF off), whose 15 spilled registers sit outside its hidden-tile loop
