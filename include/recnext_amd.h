@@ -330,6 +330,25 @@ size_t rcx_stem_pack_bytes(int CM, int CO);
 int rcx_stem_fwd(const void* x, void* y, const void* w1frag, const float* b1, const void* w2frag, const float* b2, int N, int H, int W, int CM, int CO, int dtype, void* stream);
 
 /*
+ * RecNextStem of the LSNet-style RecNeXt-T / S / B and their share-channel forms, inference (lsnet/model/recattn.py:208-223; three 3x3 stride-2 ConvNorms
+ * BN-folded, 3 -> C/4 -> C/2 -> C, nn.GELU after the first two and, where final_act = 1 (depth[0] == 0: T and S), after the third):
+ *     y = act3(conv3(gelu(conv2(gelu(conv1(x) + b1)) + b2)) + b3)
+ *   x : N x H x W x 3 bf16 (NHWC, 2-byte aligned);  y : N x H3 x W3 x C bf16 (NHWC), the planes ceil(/2) three times;  C = 64 (T) | 128 (S / B).
+ *   w1frag, b1, w2frag, b2 : as rcx_stem_fwd's with CM = C/4, CO = C/2;  w3frag : the third conv's (C, C/2, 3, 3) weight as matrix-core fragments in the same
+ *   order;  b3 : C float32.  rcx_stem3_pack_bytes(C, conv) = bytes of conv 1 | 2 | 3's fragments (recnext_amd/ops.py::pack_stem3 builds all six).
+ *   workspace : rcx_stem3_workspace_bytes(N, H, W, C) bytes, the N x H2 x W2 x C/2 bf16 intermediate -- written once by the first launch (conv1 + GELU + conv2 +
+ *   GELU; the N x H1 x W1 x C/4 intermediate exists only as tiles in LDS) and read once by the second (conv3).  y, workspace and the packs 16-byte aligned;
+ *   y and the workspace overlap neither x nor each other.
+ * Float32 sums in a fixed order, each intermediate rounded to bf16 once (as the library path does); an image's output does not depend on N or on its place in
+ * the batch.  rcx_stem3_supported() says whether the shape has a kernel; else RCX_ERR_UNSUPPORTED and the caller keeps the conv library.
+ */
+int rcx_stem3_supported(int N, int H, int W, int C, int final_act, int dtype);
+size_t rcx_stem3_pack_bytes(int C, int conv);
+size_t rcx_stem3_workspace_bytes(int N, int H, int W, int C);
+int rcx_stem3_fwd(const void* x, void* y, const void* w1frag, const float* b1, const void* w2frag, const float* b2, const void* w3frag, const float* b3,
+                  void* workspace, size_t workspace_bytes, int N, int H, int W, int C, int final_act, int dtype, void* stream);
+
+/*
  * The token half of a block of the LSNet-style RecNeXt-T / S / B (lsnet/model/recattn.py:226-251, eval mode, every BatchNorm folded):
  *     r = RepVGGDW(x) = dw3x3(x) + dw1x1(x) + x                (:8-34; ONE biased depthwise 3x3 conv: lk + zero-padded sk + identity at the centre tap)
  *     t = cat(mixer(r[..., :split]), r[..., split:])            (:226-237, PartialChannelOperation; no slice copy, no concatenation)

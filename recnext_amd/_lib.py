@@ -59,6 +59,10 @@ SIGNATURES = {
     "rcx_stem_supported": (_i, [_i] * 6),
     "rcx_stem_pack_bytes": (_sz, [_i] * 2),
     "rcx_stem_fwd": (_i, [_vp] * 6 + [_i] * 6 + [_vp]),
+    "rcx_stem3_supported": (_i, [_i] * 6),
+    "rcx_stem3_pack_bytes": (_sz, [_i] * 2),
+    "rcx_stem3_workspace_bytes": (_sz, [_i] * 4),
+    "rcx_stem3_fwd": (_i, [_vp] * 9 + [_sz] + [_i] * 6 + [_vp]),
     "rcx_channel_mlp_supported": (_i, [_i] * 4),
     "rcx_channel_mlp_pack_bytes": (_sz, [_i] * 2),
     "rcx_channel_mlp_fwd": (_i, [_vp] * 5 + [_i] * 4 + [_vp]),

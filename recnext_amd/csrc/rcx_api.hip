@@ -1109,6 +1109,66 @@ int rcx_stem_fwd(const void* x, void* y, const void* w1frag, const float* b1, co
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_stem_fwd");
 }
 
+// The T / S / B stem (lsnet/model/recattn.py:208-223): front launch (rcx_stem.hip) into the workspace, tail launch (rcx_conv3s2.hip) out of it.
+namespace {
+bool stem3_shape(int N, int H, int W, int C, int final_act, int dtype)
+{
+    if (dtype != RCX_DTYPE_BF16 || N <= 0 || H <= 0 || W <= 0 || (C != 64 && C != 128) || (final_act != 0 && final_act != 1)) return false;
+    if ((unsigned long long)H * W * 6 >= (1ull << 31)) return false;
+    const long long h2 = ((H + 1) / 2 + 1) / 2, w2 = ((W + 1) / 2 + 1) / 2;
+    return (long long)N * h2 * w2 <= 0x7fffffffLL / 64;                              // tile and pixel counts of both launches stay ints
+}
+bool any_misaligned(std::initializer_list<const void*> ps)
+{
+    for (const void* p : ps)
+        if ((size_t)p & 15) return true;
+    return false;
+}
+bool overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    return (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
+}
+}  // namespace
+
+int rcx_stem3_supported(int N, int H, int W, int C, int final_act, int dtype) { return stem3_shape(N, H, W, C, final_act, dtype) ? 1 : 0; }
+
+size_t rcx_stem3_pack_bytes(int C, int conv)
+{
+    if (C != 64 && C != 128) return 0;
+    if (conv == 1) return 2048;                                                      // K = 27 padded to 32, C / 4 <= 32 channels padded to 32
+    if (conv == 2) return (size_t)(C / 64) * 9 * ((C / 4 + 15) / 16) * 1024;          // C / 2 = 32 | 64 output channels, C / 4 = 16 | 32 input channels
+    if (conv == 3) return (size_t)(C / 32) * 9 * (C / 32) * 1024;                     // C output channels, C / 2 input channels
+    return 0;
+}
+
+size_t rcx_stem3_workspace_bytes(int N, int H, int W, int C)
+{
+    if (N <= 0 || H <= 0 || W <= 0 || (C != 64 && C != 128)) return 0;
+    return (size_t)N * (size_t)(((H + 1) / 2 + 1) / 2) * (size_t)(((W + 1) / 2 + 1) / 2) * (size_t)(C / 2) * 2;
+}
+
+int rcx_stem3_fwd(const void* x, void* y, const void* w1frag, const float* b1, const void* w2frag, const float* b2, const void* w3frag, const float* b3,
+                  void* workspace, size_t workspace_bytes, int N, int H, int W, int C, int final_act, int dtype, void* stream)
+{
+    if (!x || !y || !w1frag || !b1 || !w2frag || !b2 || !w3frag || !b3 || !workspace) return fail(RCX_ERR_BAD_ARG, "rcx_stem3_fwd: null pointer");
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(RCX_ERR_BAD_ARG, "non-positive extent N=%d H=%d W=%d C=%d", N, H, W, C);
+    if (!known_dtype(dtype)) return fail(RCX_ERR_BAD_ARG, "unknown dtype %d", dtype);
+    if (final_act != 0 && final_act != 1) return fail(RCX_ERR_BAD_ARG, "rcx_stem3_fwd: final_act must be 0 or 1, got %d", final_act);
+    if (((size_t)x & 1) || any_misaligned({y, workspace, w1frag, b1, w2frag, b2, w3frag, b3}))
+        return fail(RCX_ERR_BAD_ARG, "rcx_stem3_fwd: y, workspace and the six packs must be 16-byte aligned, x 2-byte aligned");
+    if (!stem3_shape(N, H, W, C, final_act, dtype))
+        return fail(RCX_ERR_UNSUPPORTED, "rcx_stem3_fwd: no kernel for C=%d dtype %d (bf16; C = 64 | 128; one image of x below 2^31 bytes)", C, dtype);
+    const size_t need = rcx_stem3_workspace_bytes(N, H, W, C), xbytes = (size_t)N * H * W * 6;
+    const size_t ybytes = (size_t)N * (size_t)((((H + 1) / 2 + 1) / 2 + 1) / 2) * (size_t)((((W + 1) / 2 + 1) / 2 + 1) / 2) * (size_t)C * 2;
+    if (overlap(y, ybytes, x, xbytes) || overlap(workspace, workspace_bytes, x, xbytes) || overlap(workspace, workspace_bytes, y, ybytes))
+        return fail(RCX_ERR_BAD_ARG, "rcx_stem3_fwd: y and the workspace must overlap neither x nor each other");
+    if (workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "rcx_stem3_fwd: needs a workspace of %zu bytes, got %zu", need, workspace_bytes);
+    hipError_t e = rcx::stem_front_fwd(x, workspace, w1frag, b1, w2frag, b2, N, H, W, C / 4, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "rcx_stem3_fwd (front)");
+    e = rcx::conv3s2_fwd(workspace, y, w3frag, b3, N, ((H + 1) / 2 + 1) / 2, ((W + 1) / 2 + 1) / 2, C / 2, final_act, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rcx_stem3_fwd (tail)");
+}
+
 int rcx_channel_mlp_supported(int M, int C, int H, int dtype) { return rcx::channel_mlp_applicable(M, C, H, dtype) ? 1 : 0; }
 
 size_t rcx_channel_mlp_pack_bytes(int C, int H) { return rcx::channel_mlp_pack_bytes(C, H); }
@@ -1137,15 +1197,6 @@ int rcx_ls_la3_supported(int B, int H, int W, int C, int split, int heads, int d
 {
     return rcx::ls_la3_applicable(B, H, W, C, split, heads, dtype) ? 1 : 0;
 }
-
-namespace {
-bool any_misaligned(std::initializer_list<const void*> ps)
-{
-    for (const void* p : ps)
-        if ((size_t)p & 15) return true;
-    return false;
-}
-}  // namespace
 
 int rcx_ls_recattn_fwd(const void* x, void* r, void* t, const float* w_rep, const float* b_rep, const float* w_down_kkc, const float* b_down,
                        const float* wqT, const float* bq, const float* wkT, const float* bk, const float* w_pe_kkc, const float* b_pe,

@@ -178,6 +178,10 @@ hipError_t recattn_down_qkcore(const void* x, const float* wdn, const float* bdn
 bool stem_applicable(int N, int H, int W, int CM, int CO, int dtype);
 size_t stem_pack_bytes(int CM, int CO);
 hipError_t stem_fwd(const void* x, void* y, const void* w1frag, const float* b1, const void* w2frag, const float* b2, int N, int H, int W, int CM, int CO, int dtype, hipStream_t s);
+// the T / S / B stem (three convs): rcx_stem.hip's kernel with a GELU in its output epilogue (CM = 16 | 32 -> 32 | 64 channels), then rcx_conv3s2.hip (-> 64 | 128)
+int stem_device_cus();
+hipError_t stem_front_fwd(const void* x, void* y, const void* w1frag, const float* b1, const void* w2frag, const float* b2, int N, int H, int W, int CM, hipStream_t s);
+hipError_t conv3s2_fwd(const void* x, void* y, const void* wfrag, const float* bias, int N, int H, int W, int CIN, int act, hipStream_t s);
 // rcx_mlp.hip: the channel mixer + residual of a block in one launch (bf16)
 bool channel_mlp_applicable(int M, int C, int H, int dtype);
 size_t channel_mlp_pack_bytes(int C, int H);

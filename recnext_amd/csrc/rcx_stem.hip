@@ -15,6 +15,8 @@
 //      and another 1.1 k in the x requests queued behind it: profiles/r09_stem_timeline.txt).
 // -DRCX_STEM_STAMPS is the diagnostic build of this file alone (tools/stem_timeline.py): s_memtime at the phase boundaries, summed per wave into a buffer of its own.
 // Numerics: float32 accumulation, the intermediate rounded to bf16 once (as the library path does), exact GELU (rcx_gelu.h).
+// The same kernel with a GELU after the second conv's bias as well (template flag GO; CM = 16 | 32) is the front launch of the T / S / B stem, whose third conv is
+// rcx_conv3s2.hip (stem_front_fwd below; lsnet/model/recattn.py:208-223).
 #include "rcx_common.h"
 #include "rcx_launch.h"
 #include "rcx_gelu.h"
@@ -63,8 +65,9 @@ __device__ __forceinline__ void wave_sync()
 }
 
 // CM = channels of the intermediate, KC = CM rounded up to a multiple of 16 (the k-steps of a tap), M1 = ceil(CM / 32) tiles of the first product, MT = output tiles,
-// XW = x rows move as 8-byte pieces (W % 4 == 0 and an 8-byte aligned x: every piece lies wholly inside or outside a row of the image), else as single bf16
-template <int CM, int KC, int MT, bool XW>
+// XW = x rows move as 8-byte pieces (W % 4 == 0 and an 8-byte aligned x: every piece lies wholly inside or outside a row of the image), else as single bf16,
+// GO = an exact GELU after the second conv's bias as well (the front of the T / S / B stem, rcx_conv3s2.hip; the M / A stem has none)
+template <int CM, int KC, int MT, bool XW, bool GO = false>
 __global__ void __launch_bounds__(256)
 k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __restrict__ w1frag, const float* __restrict__ b1, const u32x4q* __restrict__ w2frag,
        const float* __restrict__ b2, int N, int H, int W, int H1, int W1, int H2, int W2, int CO, int tiles_x, int tiles_y, int y16 RCX_STAMP_ARG)
@@ -231,8 +234,14 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
         for (int g = 0; g < 4; ++g) {
             const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + 32 * mt + 8 * g + 4 * h);
             bf16x4 o;
-            o[0] = (__bf16)(d0[4 * g + 0] + d1[4 * g + 0] + bb.x); o[1] = (__bf16)(d0[4 * g + 1] + d1[4 * g + 1] + bb.y);
-            o[2] = (__bf16)(d0[4 * g + 2] + d1[4 * g + 2] + bb.z); o[3] = (__bf16)(d0[4 * g + 3] + d1[4 * g + 3] + bb.w);
+            if constexpr (GO) {
+                const gelu_f32x2 a = gelu2(gelu_f32x2{d0[4 * g + 0] + d1[4 * g + 0] + bb.x, d0[4 * g + 1] + d1[4 * g + 1] + bb.y});
+                const gelu_f32x2 b = gelu2(gelu_f32x2{d0[4 * g + 2] + d1[4 * g + 2] + bb.z, d0[4 * g + 3] + d1[4 * g + 3] + bb.w});
+                o[0] = (__bf16)a.x; o[1] = (__bf16)a.y; o[2] = (__bf16)b.x; o[3] = (__bf16)b.y;
+            } else {
+                o[0] = (__bf16)(d0[4 * g + 0] + d1[4 * g + 0] + bb.x); o[1] = (__bf16)(d0[4 * g + 1] + d1[4 * g + 1] + bb.y);
+                o[2] = (__bf16)(d0[4 * g + 2] + d1[4 * g + 2] + bb.z); o[3] = (__bf16)(d0[4 * g + 3] + d1[4 * g + 3] + bb.w);
+            }
             *reinterpret_cast<u32x2q*>(Ly + 64 * r + 8 * ((2 * g + h) ^ ((r >> 1) & 7))) = __builtin_bit_cast(u32x2q, o);
         }
         wave_sync();
@@ -288,7 +297,8 @@ size_t stem_pack_bytes(int CM, int CO)
     return (size_t)mt * 9 * (kc / 16) * 1024;
 }
 
-template <int CM, int KC>
+// GO: see k_stem; ONLY = the one MT the caller has (0: all three) -- the T / S / B front needs one per channel set
+template <int CM, int KC, bool GO = false, int ONLY = 0>
 static hipError_t launch_stem(const void* x, void* y, const void* w1, const float* b1, const void* w2frag, const float* b2, int N, int H, int W, int CO, int MT, int ncu, hipStream_t s)
 {
     const int H1 = (H + 1) / 2, W1 = (W + 1) / 2, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2, tx = (W2 + 7) / 8, ty = (H2 + 7) / 8;
@@ -304,27 +314,32 @@ static hipError_t launch_stem(const void* x, void* y, const void* w1, const floa
     const long long grid = ntiles < ncu * per_cu ? ntiles : ncu * per_cu;          // persistent: the weights go to LDS once per workgroup
 #define RCX_STEM_GO(MT_, XW_)                                                                                                              \
     {                                                                                                                                      \
-        auto kfn = stem::k_stem<CM, KC, MT_, XW_>;                                                                                         \
+        auto kfn = stem::k_stem<CM, KC, MT_, XW_, GO>;                                                                                     \
         RCX_SET_LDS_ONCE(kfn, lds);                                                                                                        \
         hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(256), lds, s, (const bf16_t*)x, (bf16_t*)y, (const stem::u32x4q*)w1, b1, (const stem::u32x4q*)w2frag, b2, \
                            N, H, W, H1, W1, H2, W2, CO, tx, ty, y16 RCX_STAMP_VAL);                                                        \
         return hipGetLastError();                                                                                                          \
     }
-    if (MT == 1 && xw) RCX_STEM_GO(1, true)
-    if (MT == 2 && xw) RCX_STEM_GO(2, true)
-    if (MT == 3 && xw) RCX_STEM_GO(3, true)
-    if (MT == 1) RCX_STEM_GO(1, false)
-    if (MT == 2) RCX_STEM_GO(2, false)
-    if (MT == 3) RCX_STEM_GO(3, false)
+    if constexpr (ONLY == 0 || ONLY == 1) {
+        if (MT == 1 && xw) RCX_STEM_GO(1, true)
+        if (MT == 1) RCX_STEM_GO(1, false)
+    }
+    if constexpr (ONLY == 0 || ONLY == 2) {
+        if (MT == 2 && xw) RCX_STEM_GO(2, true)
+        if (MT == 2) RCX_STEM_GO(2, false)
+    }
+    if constexpr (ONLY == 0 || ONLY == 3) {
+        if (MT == 3 && xw) RCX_STEM_GO(3, true)
+        if (MT == 3) RCX_STEM_GO(3, false)
+    }
 #undef RCX_STEM_GO
     return hipErrorInvalidConfiguration;
 }
 
-hipError_t stem_fwd(const void* x, void* y, const void* w1, const float* b1, const void* w2frag, const float* b2, int N, int H, int W, int CM, int CO, int dtype, hipStream_t s)
+// compute units of the current device, asked once per device (the persistent grids of this file and of rcx_conv3s2.hip)
+int stem_device_cus()
 {
-    int kc, mt;
-    if (!stem_applicable(N, H, W, CM, CO, dtype) || !stem_shape(CM, CO, &kc, &mt)) return hipErrorInvalidConfiguration;
-    static std::atomic<int> cus[RCX_MAX_DEVICES];                     // compute units of each device, asked once
+    static std::atomic<int> cus[RCX_MAX_DEVICES];
     int dev = 0, ncu = 256;
     if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < RCX_MAX_DEVICES) {
         ncu = cus[dev].load(std::memory_order_relaxed);
@@ -334,6 +349,14 @@ hipError_t stem_fwd(const void* x, void* y, const void* w1, const float* b1, con
             cus[dev].store(ncu, std::memory_order_relaxed);
         }
     }
+    return ncu;
+}
+
+hipError_t stem_fwd(const void* x, void* y, const void* w1, const float* b1, const void* w2frag, const float* b2, int N, int H, int W, int CM, int CO, int dtype, hipStream_t s)
+{
+    int kc, mt;
+    if (!stem_applicable(N, H, W, CM, CO, dtype) || !stem_shape(CM, CO, &kc, &mt)) return hipErrorInvalidConfiguration;
+    const int ncu = stem_device_cus();
     switch (CM) {
         case 20: return launch_stem<20, 32>(x, y, w1, b1, w2frag, b2, N, H, W, CO, mt, ncu, s);
         case 24: return launch_stem<24, 32>(x, y, w1, b1, w2frag, b2, N, H, W, CO, mt, ncu, s);
@@ -342,6 +365,16 @@ hipError_t stem_fwd(const void* x, void* y, const void* w1, const float* b1, con
         case 40: return launch_stem<40, 48>(x, y, w1, b1, w2frag, b2, N, H, W, CO, mt, ncu, s);
         default: return hipErrorInvalidConfiguration;
     }
+}
+
+// The front of the T / S / B stem (lsnet/model/recattn.py:208-223): y = gelu(conv2(gelu(conv1(x) + b1)) + b2), (CM, CO) = (16, 32) for T and (32, 64) for S / B;
+// rcx_conv3s2.hip takes y through the third conv.  The same kernel as above with the GELU in its output epilogue; the packs are ops.pack_stem's.
+hipError_t stem_front_fwd(const void* x, void* y, const void* w1, const float* b1, const void* w2frag, const float* b2, int N, int H, int W, int CM, hipStream_t s)
+{
+    if (N <= 0 || H <= 0 || W <= 0 || (unsigned long long)H * W * 6 >= (1ull << 31)) return hipErrorInvalidConfiguration;
+    if (CM == 16) return launch_stem<16, 16, true, 1>(x, y, w1, b1, w2frag, b2, N, H, W, 32, 1, stem_device_cus(), s);
+    if (CM == 32) return launch_stem<32, 32, true, 2>(x, y, w1, b1, w2frag, b2, N, H, W, 64, 2, stem_device_cus(), s);
+    return hipErrorInvalidConfiguration;
 }
 
 }  // namespace rcx

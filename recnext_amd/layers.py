@@ -214,3 +214,45 @@ class FusedStem:
             self._pack = ops.pack_stem(*ts)
             self._key = key
         return ops.stem(x, *self._pack, self.conv1.out_channels, self.conv2.out_channels)
+
+
+class FusedStem3:
+    """The T / S / B RecNextStem's [conv, GELU, conv, GELU, conv, GELU | Identity] (3x3 stride-2 convs, BatchNorms folded) as TWO HIP launches (ops.stem3; inference, bf16,
+    channels_last): the C/4-channel intermediate never reaches memory.  Not a Module: it reads the three convs' own parameters (state_dict untouched) and rebuilds
+    its packs when one changes."""
+
+    def __init__(self, conv1, conv2, conv3, final_act):
+        self.convs, self.final_act = (conv1, conv2, conv3), bool(final_act)
+        self._key, self._pack = None, None
+
+    def _params(self):
+        return [t for c in self.convs for t in (c.weight, c.bias)]
+
+    def supported(self, x):
+        from . import ops
+        n, c, h, w = x.shape
+        c1, c2, c3 = (m.out_channels for m in self.convs)
+        return x.is_cuda and x.dtype == torch.bfloat16 and c == 3 and (4 * c1, 2 * c2) == (c3, c3) and ops.stem3_supported(n, h, w, c3, self.final_act, x.dtype)
+
+    def usable(self, seq, x):
+        """As FusedStem.usable: the stem must still be these three convs with exact GELUs between them and the last entry what it was, on x's device, x channels_last
+        with no gradient wanted."""
+        if len(seq) != 6 or any(seq[2 * i] is not m for i, m in enumerate(self.convs)) or not _is_exact_gelu(seq[1]) or not _is_exact_gelu(seq[3]):
+            return False
+        if not (_is_exact_gelu(seq[5]) if self.final_act else type(seq[5]) is nn.Identity):
+            return False
+        if any(m.weight.device != x.device for m in self.convs) or _needs_grad(x, *self._params()):
+            return False
+        return x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and self.supported(x)
+
+    def packs(self):
+        return [] if self._pack is None else [p for p in self._pack if torch.is_tensor(p)]
+
+    def __call__(self, x):
+        from . import ops
+        ts = self._params()
+        key = tuple(None if t is None else (t.data_ptr(), t._version, t.dtype, t.device) for t in ts)
+        if key != self._key:
+            self._pack = ops.pack_stem3(*ts)
+            self._key = key
+        return ops.stem3(x, *self._pack, self.convs[2].out_channels, self.final_act)

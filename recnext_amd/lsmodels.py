@@ -13,7 +13,9 @@ forward and backward kernels -- ``RecAttn2d``'s own training branch at stages 0-
 ``rcx_linear_attention_wide_*``) and ``LinearAttention3.forward`` at stage 3 (q / k of s/2 and v of s channels: the wide core) -- and library GEMMs
 for the 1x1 projections.  A CPU tensor raises.  Downsample's grouped 5x5 stride-2 conv (:254-263) is ONE HIP launch (``ops.grouped_conv2d``) in an
 inference forward after ``models.use_hip_downsample`` (opt-in; ``speed.build_inference_model`` calls it); in training, where a gradient is needed and
-on a CPU tensor it stays the library's conv.  The stem and the classifier are PyTorch-ROCm library operators.
+on a CPU tensor it stays the library's conv.  The stem's three convs and their GELUs are TWO HIP launches (``ops.stem3``) in a bf16 inference forward after
+``models.use_fused_stem`` (``speed.build_inference_model`` calls it); in training, in float32 / fp16, where a gradient is needed and on a CPU tensor the stem stays
+the library's.  The classifier is a PyTorch-ROCm library operator.
 
 RecAttn2d's ``stage -> LinearAttention1 | 2`` label (:119) is cosmetic: the two are the same function (the reference asserts it, :481-501).
 """
@@ -355,6 +357,9 @@ class RecNextStem(nn.Module):
                                   ConvNorm(out_channels // 2, out_channels, **kw), act_layer() if additional_activation else nn.Identity())
 
     def forward(self, x):
+        fused = self.__dict__.get("_fused_stem")
+        if fused is not None and not self.training and fused.usable(self.stem, x):
+            return fused(x)                             # two launches (models.use_fused_stem)
         return self.stem(x)
 
 

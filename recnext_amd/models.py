@@ -284,18 +284,28 @@ def use_linear_pointwise(net):
 
 def use_fused_stem(net):
     """Inference-only, after ``replace_batchnorm``: evaluate RecNextStem ([3x3 stride-2 conv + bias, exact GELU, 3x3 stride-2 conv + bias]) as ONE HIP launch where
-    rcx_stem_fwd has a kernel (bf16 on a GPU; decided per call) -- the 112 x 112 intermediate never reaches memory.  The convs, their parameters and the state_dict
+    rcx_stem_fwd has a kernel (bf16 on a GPU; decided per call) -- the 112 x 112 intermediate never reaches memory -- and the T / S / B ``lsmodels.RecNextStem``
+    ([conv, GELU, conv, GELU, conv, GELU | Identity]) as the two launches of rcx_stem3_fwd likewise.  The convs, their parameters and the state_dict
     are untouched.  Returns the number of stems given the fused path (0 or 1)."""
-    from .layers import FusedStem
+    from .layers import FusedStem, FusedStem3, _is_exact_gelu
+    from .lsmodels import RecNextStem as LsStem
+
+    def stem_conv(m):
+        return isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.stride == (2, 2) and m.padding == (1, 1) and m.groups == 1 and m.dilation == (1, 1)
+
     n = 0
     for m in net.modules():
-        if isinstance(m, RecNextStem) and m.__dict__.get("_fused_stem") is None:
-            seq = m.stem
-            if len(seq) == 3 and all(isinstance(seq[i], nn.Conv2d) and seq[i].kernel_size == (3, 3) and seq[i].stride == (2, 2) and seq[i].padding == (1, 1)
-                                     and seq[i].groups == 1 and seq[i].dilation == (1, 1) for i in (0, 2)) \
-                    and isinstance(seq[1], nn.GELU) and getattr(seq[1], "approximate", "none") == "none" and seq[0].in_channels == 3:
+        if not isinstance(m, (RecNextStem, LsStem)) or m.__dict__.get("_fused_stem") is not None:
+            continue
+        seq = m.stem
+        if isinstance(m, RecNextStem):
+            if len(seq) == 3 and stem_conv(seq[0]) and stem_conv(seq[2]) and _is_exact_gelu(seq[1]) and seq[0].in_channels == 3:
                 object.__setattr__(m, "_fused_stem", FusedStem(seq[0], seq[2]))
                 n += 1
+        elif len(seq) == 6 and all(stem_conv(seq[i]) and seq[i].bias is not None for i in (0, 2, 4)) and _is_exact_gelu(seq[1]) and _is_exact_gelu(seq[3]) \
+                and (_is_exact_gelu(seq[5]) or type(seq[5]) is nn.Identity) and seq[0].in_channels == 3:
+            object.__setattr__(m, "_fused_stem", FusedStem3(seq[0], seq[2], seq[4], _is_exact_gelu(seq[5])))
+            n += 1
     return n
 
 

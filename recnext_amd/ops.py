@@ -758,6 +758,21 @@ def stem_supported(n, h, w, cm, co, dtype):
     return dtype == torch.bfloat16 and _lib.load().rcx_stem_supported(int(n), int(h), int(w), int(cm), int(co), _DT[dtype]) > 0
 
 
+def _pack_conv3x3_frags(w, b):
+    """A dense 3x3 conv's (CO, CI, 3, 3) weight as bf16 matrix-core fragments and its bias zero padded to a multiple of 32: fragment (mt, ks) with ks = tap (KC / 16) + cg
+    (KC = CI rounded up to 16): lane (h, m), element j = w[32 mt + m][16 cg + 8 h + j][tap] (zeros past CO / CI)."""
+    co, ci = w.shape[0], w.shape[1]
+    dev = w.device
+    kc, mt = -(-ci // 16) * 16, -(-co // 32)
+    wp = torch.zeros(32 * mt, kc, 9, dtype=torch.bfloat16, device=dev)
+    wp[:co, :ci] = w.detach().reshape(co, ci, 9).to(torch.bfloat16)
+    f = wp.view(mt, 32, kc // 16, 2, 8, 9).permute(0, 5, 2, 3, 1, 4)                         # [mt, tap, cg, h, m, j]
+    bp = torch.zeros(32 * mt, dtype=torch.float32, device=dev)
+    if b is not None:
+        bp[:co] = b.detach().float()
+    return f.reshape(-1).contiguous(), bp
+
+
 def pack_stem(w1, b1, w2, b2):
     """The stem's two BN-folded 3x3 stride-2 convs -> (w1p, b1p, w2frag, b2p) for stem(): w1 (CM, 3, 3, 3), b1 (CM), w2 (CO, CM, 3, 3), b2 (CO).
 
@@ -767,7 +782,6 @@ def pack_stem(w1, b1, w2, b2):
     if tuple(w1.shape) != (cm, 3, 3, 3) or tuple(w2.shape) != (co, cm, 3, 3):
         raise ValueError(f"stem weights must be (CM, 3, 3, 3) and (CO, CM, 3, 3), got {tuple(w1.shape)} and {tuple(w2.shape)}")
     dev = w1.device
-    kc, mt = -(-cm // 16) * 16, -(-co // 32)
     m1 = -(-cm // 32)
     # first conv: K = (dy, dx, c) = 27 padded to 32; fragment (m1, ks), lane (h, m), element j = w1[32 m1 + m][k = 16 ks + 8 h + j]
     w1k = torch.zeros(32 * m1, 32, dtype=torch.bfloat16, device=dev)
@@ -776,13 +790,7 @@ def pack_stem(w1, b1, w2, b2):
     b1p = torch.zeros(32 * m1, dtype=torch.float32, device=dev)
     if b1 is not None:
         b1p[:cm] = b1.detach().float()
-    wp = torch.zeros(32 * mt, kc, 9, dtype=torch.bfloat16, device=dev)
-    wp[:co, :cm] = w2.detach().reshape(co, cm, 9).to(torch.bfloat16)
-    f = wp.view(mt, 32, kc // 16, 2, 8, 9).permute(0, 5, 2, 3, 1, 4)                         # [mt, tap, cg, h, m, j]
-    w2frag = f.reshape(-1).contiguous()
-    b2p = torch.zeros(32 * mt, dtype=torch.float32, device=dev)
-    if b2 is not None:
-        b2p[:co] = b2.detach().float()
+    w2frag, b2p = _pack_conv3x3_frags(w2, b2)
     return w1p, b1p, w2frag, b2p
 
 
@@ -1028,3 +1036,5 @@ def recconv2d_input_backward(gy, wpack, wflip, level, k, mode="bilinear", dtype=
 from .lsdown import grouped_conv2d, grouped_conv2d_supported, pack_grouped_weight            # noqa: E402, F401
 # ... and the conv's backward for a training step (rcx_grouped_conv2d_bwd; guard-band cases in tests/test_ls_down_bwd_gpu.py)
 from .lsdown import GroupedConv2dFn, grouped_conv2d_backward, grouped_conv2d_backward_supported, unpack_grouped_weight_grad      # noqa: E402, F401
+# The T / S / B stem (rcx_stem3_fwd): stem3_supported, pack_stem3, stem3.  Written in recnext_amd/lsstem.py (guard-band cases in tests/test_ls_stem_gpu.py).
+from .lsstem import pack_stem3, stem3, stem3_supported                                       # noqa: E402, F401

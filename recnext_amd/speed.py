@@ -33,7 +33,8 @@ def build_inference_model(name, device, dtype=torch.bfloat16, token_mixer=None, 
     runs the three strided Downsample convs (M / A: depthwise 7x7 + BatchNorm; T / S / B: the grouped 5x5) on the HIP kernels as well.  ``pad_hidden`` lets the
     channel mixers' GEMMs run at a zero-padded hidden width (``models.pad_mlp_hidden``: RecNeXt-A's 120 / 240 / 480 -> 128 / 256 / 512).
     ``fused_mlp`` (bf16): ``x + channel_mixer(.)`` of the blocks rcx_channel_mlp_fwd has a kernel for as one HIP launch (``models.use_fused_mlp``).
-    ``fused_stem`` (bf16): the stem's two convs and GELU as one HIP launch (``models.use_fused_stem``).
+    ``fused_stem`` (bf16): the stem's convs and GELUs on the HIP kernels (``models.use_fused_stem``): M / A's two convs as one launch, T / S / B's three (the
+    share-channel models' too) as two.
     """
     torch.manual_seed(seed)
     net = models.create_model(name, num_classes=1000, token_mixer=token_mixer)
@@ -134,6 +135,7 @@ def main(argv=None):
     ap.add_argument("--gpus", default=1, type=int, help="ranks (one per GPU); --batch-size is per GPU")
     ap.add_argument("--graph", action="store_true", help="replay the forward as one HIP graph (small batches are bound by the host's launches)")
     ap.add_argument("--no-hip-downsample", action="store_true", help="keep the Downsample convs on the library (the comparison run)")
+    ap.add_argument("--no-fused-stem", action="store_true", help="keep the stem's convs and GELUs on the library (the comparison run)")
     ap.add_argument("--t0", default=T0, type=float)
     ap.add_argument("--t1", default=T1, type=float)
     args = ap.parse_args(argv)
@@ -147,7 +149,7 @@ def main(argv=None):
     ranks = rdist.init("cuda")
     device = str(ranks.device)
     dtype = DTYPES[args.dtype]
-    net = build_inference_model(args.model, device, dtype, hip_downsample=not args.no_hip_downsample)
+    net = build_inference_model(args.model, device, dtype, hip_downsample=not args.no_hip_downsample, fused_stem=not args.no_fused_stem)
     rdist.barrier(ranks)
     with torch.no_grad():                 # speed_gpu.py:40 switches autograd off for the whole process; scoped here
         rate = throughput(args.model, net, device, args.batch_size, args.resolution, dtype, args.t0, args.t1, ranks=ranks, graph=args.graph)
