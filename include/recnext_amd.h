@@ -491,6 +491,43 @@ int rcx_linear_attention_wide_fwd(const void* qpre, const void* kpre, const void
 int rcx_linear_attention_wide_bwd(const void* qpre, const void* kpre, const void* v, const void* gout, void* gq, void* gk, void* gv,
                                   int B, int n, int Cqk, int Cv, int heads, int dtype, void* stream);
 
+/*
+ * nn.BatchNorm2d of the training step on a dense NHWC tensor, forward and backward: the `bn` of every ConvNorm (lsnet/model/recattn.py:130-146) as
+ * engine.py:38-71 runs it (model.train(), loss.backward() under autocast), and its eval-mode form with gradients flowing, which the detection and
+ * segmentation backbones use (frozen statistics).  x, y, gy, gx: N x H x W x C of `dtype` (float32, bf16 or f16), R = N H W rows of C contiguous channels,
+ * aligned to one element; weight, bias, every statistic and every parameter gradient: float32 (C), aligned to 4 bytes.  All arithmetic is float32.
+ *   rcx_batchnorm_train_fwd   save_mean[c] = mean_r x[r,c], save_invstd[c] = 1 / sqrt(var_r x[r,c] + eps) (biased variance),
+ *                             y = (x - save_mean) * save_invstd * weight + bias, rounded once at the store; with running_mean / running_var (both or
+ *                             neither; in-out): running = (1 - momentum) * running + momentum * stat, the variance unbiased (R / (R - 1)), as nn.BatchNorm2d.
+ *   rcx_batchnorm_frozen_fwd  y = (x - mean) / sqrt(var + eps) * weight + bias from given statistics, one launch; save_invstd (C) or NULL receives
+ *                             1 / sqrt(var + eps) as the kernel formed it, for rcx_batchnorm_bwd.
+ *   rcx_batchnorm_bwd         with xhat = (x - mean) * invstd from the forward's saved float32 statistics:
+ *                               gweight = sum_r gy * xhat, gbias = sum_r gy                                          (both forms)
+ *                               gx = weight * invstd * (gy - sum gy / R - xhat * sum(gy * xhat) / R)                   (batch_stats = 1)
+ *                               gx = weight * invstd * gy                                                            (batch_stats = 0: frozen statistics)
+ *                             gx may be NULL, or the pair (gweight, gbias): not all three, and not one of the pair alone.  With batch_stats = 0 and no
+ *                             pair the reduction is not launched and no workspace is needed.  gy is read in x's dtype.  Outputs are overwritten.
+ * The sums are never sum x and sum x^2: a thread sums (x - p) and (x - p)^2 against its first element p, threads are combined pairwise (Chan) through LDS
+ * in a fixed tree, one partial a workgroup goes to the workspace and the P partials of a channel are combined in index order by a launch of its own.
+ * No atomics and no waiting between workgroups.  16-byte accesses are used where C is a multiple of 8 (16-bit) / 4 (float32) and every pointer is
+ * aligned to 16 bytes, an element-wide path otherwise (the two need not agree bit for bit); P and the tiling depend on (R, C, dtype) and that choice
+ * alone, so repeat launches are bit-identical.
+ * workspace: rcx_batchnorm_workspace_bytes(...) bytes (0 for an unsupported problem), aligned to 4, for rcx_batchnorm_train_fwd and for every
+ * rcx_batchnorm_bwd that reduces.  rcx_batchnorm_supported: 1 / 0, a rule on (N H W, C, dtype) alone.
+ * RCX_ERR_BAD_ARG: a NULL required pointer, one running pointer (or one of gweight / gbias) without the other, a non-positive extent, R = 1 with batch
+ * statistics, an unknown dtype, a misaligned pointer, an output or the workspace overlapping an input or each other; RCX_ERR_UNSUPPORTED: 2^31 or more
+ * elements; RCX_ERR_WORKSPACE: a workspace smaller than the query.  All decided before any HIP call.
+ */
+int rcx_batchnorm_supported(int N, int H, int W, int C, int dtype);
+size_t rcx_batchnorm_workspace_bytes(int N, int H, int W, int C, int dtype);
+int rcx_batchnorm_train_fwd(const void* x, void* y, const float* weight, const float* bias, float* running_mean, float* running_var, float* save_mean,
+                            float* save_invstd, void* workspace, size_t workspace_bytes, int N, int H, int W, int C, float momentum, float eps, int dtype,
+                            void* stream);
+int rcx_batchnorm_frozen_fwd(const void* x, void* y, const float* weight, const float* bias, const float* mean, const float* var, float* save_invstd, float eps,
+                             int N, int H, int W, int C, int dtype, void* stream);
+int rcx_batchnorm_bwd(const void* x, const void* gy, const float* weight, const float* mean, const float* invstd, void* gx, float* gweight, float* gbias,
+                      void* workspace, size_t workspace_bytes, int N, int H, int W, int C, int batch_stats, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

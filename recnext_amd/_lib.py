@@ -93,6 +93,11 @@ SIGNATURES = {
     "rcx_linear_attention_wide_supported": (_i, [_i] * 6),
     "rcx_linear_attention_wide_fwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),
     "rcx_linear_attention_wide_bwd": (_i, [_vp] * 7 + [_i] * 6 + [_vp]),
+    "rcx_batchnorm_supported": (_i, [_i] * 5),
+    "rcx_batchnorm_workspace_bytes": (_sz, [_i] * 5),
+    "rcx_batchnorm_train_fwd": (_i, [_vp] * 9 + [_sz] + [_i] * 4 + [ctypes.c_float] * 2 + [_i, _vp]),
+    "rcx_batchnorm_frozen_fwd": (_i, [_vp] * 7 + [ctypes.c_float] + [_i] * 5 + [_vp]),
+    "rcx_batchnorm_bwd": (_i, [_vp] * 9 + [_sz] + [_i] * 6 + [_vp]),
 }
 
 _lib = None

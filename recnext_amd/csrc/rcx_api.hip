@@ -1451,4 +1451,101 @@ int rcx_linear_attention_wide_bwd(const void* qpre, const void* kpre, const void
     return e == hipSuccess ? 0 : hip_fail(e, "rcx_linear_attention_wide_bwd");
 }
 
+// nn.BatchNorm2d on a dense NHWC tensor (rcx_bn.hip): batch statistics, frozen statistics and their backward
+namespace {
+struct Span { const void* p; size_t n; };
+
+// the checks the three BatchNorm entries share, in the order the header gives: extents, dtype, alignment (x-like tensors to one element, everything else
+// to a float), size, then every output against every input and every other output
+int check_bn(const char* fn, int N, int H, int W, int C, int dtype, std::initializer_list<const void*> elems, std::initializer_list<const void*> floats,
+             std::initializer_list<Span> ins, std::initializer_list<Span> outs)
+{
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(RCX_ERR_BAD_ARG, "%s: non-positive extent N=%d H=%d W=%d C=%d", fn, N, H, W, C);
+    if (!known_dtype(dtype)) return fail(RCX_ERR_BAD_ARG, "%s: unknown dtype %d", fn, dtype);
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2;
+    for (const void* p : elems)
+        if ((size_t)p % es) return fail(RCX_ERR_BAD_ARG, "%s: x-like tensors must be aligned to one element (%zu bytes)", fn, es);
+    for (const void* p : floats)
+        if ((size_t)p % 4) return fail(RCX_ERR_BAD_ARG, "%s: weight, bias, the statistics, the parameter gradients and the workspace must be aligned to 4 bytes", fn);
+    if (!rcx::batchnorm_applicable(N, H, W, C, dtype))
+        return fail(RCX_ERR_UNSUPPORTED, "%s: N=%d H=%d W=%d C=%d: 2^31 or more elements", fn, N, H, W, C);
+    for (auto o = outs.begin(); o != outs.end(); ++o) {
+        if (!o->p) continue;
+        for (const Span& i : ins)
+            if (i.p && overlap(o->p, o->n, i.p, i.n)) return fail(RCX_ERR_BAD_ARG, "%s: an output or the workspace aliases an input", fn);
+        for (auto q = o + 1; q != outs.end(); ++q)
+            if (q->p && overlap(o->p, o->n, q->p, q->n)) return fail(RCX_ERR_BAD_ARG, "%s: the outputs and the workspace must not alias each other", fn);
+    }
+    return 0;
+}
+}  // namespace
+
+// what the kernels take: fewer than 2^31 elements.  Which of these shapes a model routes here is the binding's rule (recnext_amd/batchnorm.py)
+int rcx_batchnorm_supported(int N, int H, int W, int C, int dtype)
+{
+    return rcx::batchnorm_applicable(N, H, W, C, dtype) ? 1 : 0;
+}
+
+size_t rcx_batchnorm_workspace_bytes(int N, int H, int W, int C, int dtype)
+{
+    if (!rcx::batchnorm_applicable(N, H, W, C, dtype)) return 0;
+    return rcx::batchnorm_workspace_bytes(N * H * W, C, dtype);
+}
+
+int rcx_batchnorm_train_fwd(const void* x, void* y, const float* weight, const float* bias, float* running_mean, float* running_var, float* save_mean,
+                            float* save_invstd, void* workspace, size_t workspace_bytes, int N, int H, int W, int C, float momentum, float eps, int dtype,
+                            void* stream)
+{
+    const char* fn = "rcx_batchnorm_train_fwd";
+    if (!x || !y || !weight || !bias || !save_mean || !save_invstd) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (!running_mean != !running_var) return fail(RCX_ERR_BAD_ARG, "%s: running_mean and running_var come together or not at all", fn);
+    if (N > 0 && H > 0 && W > 0 && (long long)N * H * W == 1)
+        return fail(RCX_ERR_BAD_ARG, "%s: batch statistics need more than one value per channel (N=%d H=%d W=%d)", fn, N, H, W);
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2, xb = (size_t)N * H * W * C * es, cb = (size_t)C * 4;
+    if (int rc = check_bn(fn, N, H, W, C, dtype, {x, y}, {weight, bias, running_mean, running_var, save_mean, save_invstd, workspace},
+                          {{x, xb}, {weight, cb}, {bias, cb}},
+                          {{y, xb}, {running_mean, cb}, {running_var, cb}, {save_mean, cb}, {save_invstd, cb}, {workspace, workspace_bytes}}))
+        return rc;
+    const size_t need = rcx::batchnorm_workspace_bytes(N * H * W, C, dtype);
+    if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes, got %zu", fn, need, workspace ? workspace_bytes : (size_t)0);
+    hipError_t e = rcx::batchnorm_train_fwd(x, y, weight, bias, running_mean, running_var, save_mean, save_invstd, workspace, N * H * W, C, momentum, eps, dtype,
+                                            (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, fn);
+}
+
+int rcx_batchnorm_frozen_fwd(const void* x, void* y, const float* weight, const float* bias, const float* mean, const float* var, float* save_invstd, float eps,
+                             int N, int H, int W, int C, int dtype, void* stream)
+{
+    const char* fn = "rcx_batchnorm_frozen_fwd";
+    if (!x || !y || !weight || !bias || !mean || !var) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2, xb = (size_t)N * H * W * C * es, cb = (size_t)C * 4;
+    if (int rc = check_bn(fn, N, H, W, C, dtype, {x, y}, {weight, bias, mean, var, save_invstd}, {{x, xb}, {weight, cb}, {bias, cb}, {mean, cb}, {var, cb}},
+                          {{y, xb}, {save_invstd, cb}}))
+        return rc;
+    hipError_t e = rcx::batchnorm_frozen_fwd(x, y, weight, bias, mean, var, save_invstd, N * H * W, C, eps, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, fn);
+}
+
+int rcx_batchnorm_bwd(const void* x, const void* gy, const float* weight, const float* mean, const float* invstd, void* gx, float* gweight, float* gbias,
+                      void* workspace, size_t workspace_bytes, int N, int H, int W, int C, int batch_stats, int dtype, void* stream)
+{
+    const char* fn = "rcx_batchnorm_bwd";
+    if (!x || !gy || !weight || !mean || !invstd) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (!gx && !gweight && !gbias) return fail(RCX_ERR_BAD_ARG, "%s: null pointer for every output (gx, gweight and gbias)", fn);
+    if (!gweight != !gbias) return fail(RCX_ERR_BAD_ARG, "%s: gweight and gbias come together or not at all", fn);
+    if (batch_stats != 0 && batch_stats != 1) return fail(RCX_ERR_BAD_ARG, "%s: batch_stats must be 0 or 1, got %d", fn, batch_stats);
+    if (batch_stats && N > 0 && H > 0 && W > 0 && (long long)N * H * W == 1)
+        return fail(RCX_ERR_BAD_ARG, "%s: batch statistics need more than one value per channel (N=%d H=%d W=%d)", fn, N, H, W);
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2, xb = (size_t)N * H * W * C * es, cb = (size_t)C * 4;
+    if (int rc = check_bn(fn, N, H, W, C, dtype, {x, gy, gx}, {weight, mean, invstd, gweight, gbias, workspace},
+                          {{x, xb}, {gy, xb}, {weight, cb}, {mean, cb}, {invstd, cb}}, {{gx, xb}, {gweight, cb}, {gbias, cb}, {workspace, workspace_bytes}}))
+        return rc;
+    if (batch_stats || gweight) {                                                  // the frozen form without parameter gradients launches no reduction
+        const size_t need = rcx::batchnorm_workspace_bytes(N * H * W, C, dtype);
+        if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes, got %zu", fn, need, workspace ? workspace_bytes : (size_t)0);
+    }
+    hipError_t e = rcx::batchnorm_bwd(x, gy, weight, mean, invstd, gx, gweight, gbias, workspace, N * H * W, C, batch_stats != 0, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, fn);
+}
+
 }  // extern "C"

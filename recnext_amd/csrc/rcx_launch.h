@@ -223,7 +223,17 @@ bool ls_down_bwd_applicable(int N, int H, int W, int Cin, int Cout, int groups, 
 size_t ls_down_bwd_workspace_bytes(int N, int H, int W, int Cin, int Cout, int groups, int k, int stride, int dtype);
 hipError_t ls_down_bwd(const void* x, const void* gy, const float* wpack, void* gx, float* gw, float* gb, void* workspace, int N, int H, int W, int Cin,
                        int Cout, int groups, int dtype, hipStream_t s);
-hipError_t recattn_qkcore(const float* d, const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe, float* out, void* workspace,
+// rcx_bn.hip: nn.BatchNorm2d on a dense NHWC tensor of R = N H W rows: batch statistics (two-stage, through the workspace) + apply, the frozen-statistics
+// apply alone, and their backward
+bool batchnorm_applicable(long long N, long long H, long long W, long long C, int dtype);
+size_t batchnorm_workspace_bytes(int R, int C, int dtype);
+hipError_t batchnorm_train_fwd(const void* x, void* y, const float* weight, const float* bias, float* run_mean, float* run_var, float* save_mean,
+                               float* save_invstd, void* workspace, int R, int C, float momentum, float eps, int dtype, hipStream_t s);
+hipError_t batchnorm_frozen_fwd(const void* x, void* y, const float* weight, const float* bias, const float* mean, const float* var, float* save_invstd,
+                                int R, int C, float eps, int dtype, hipStream_t s);
+hipError_t batchnorm_bwd(const void* x, const void* gy, const float* weight, const float* mean, const float* invstd, void* gx, float* gweight, float* gbias,
+                         void* workspace, int R, int C, bool batch_stats, int dtype, hipStream_t s);
+hipError_t recattn_qkcore(const float* d,const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe, float* out, void* workspace,
                           int B, int Hp, int Wp, int C, int heads, hipStream_t s);
 
 hipError_t linattn_core_bwd(const void* qpre, const void* kpre, const void* v, const void* gout, void* gq, void* gk, void* gv,

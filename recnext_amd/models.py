@@ -267,6 +267,25 @@ def use_hip_downsample(net):
     return n
 
 
+def use_hip_batchnorm(net, all_shapes=False):
+    """Run every plain ``nn.BatchNorm2d`` of ``net`` (a model of ``models``, ``lsmodels`` or ``lsshare``) on the HIP BatchNorm in a training step, and in
+    eval mode where a gradient flows (frozen statistics): each module whose type is exactly ``nn.BatchNorm2d`` becomes a ``batchnorm.HipBatchNorm2d``
+    by a change of class in place.  The module object, its Parameters and buffers stay the very same objects, so state_dict keys, strict loads in
+    either order, optimizers, packs keyed by parameter address, ``Downsample._hip_path``'s identity check and ``GraphedInference`` stay valid, and
+    ``SyncBatchNorm.convert_sync_batchnorm`` still converts the modules.  A call takes the HIP path only for the shapes the routing rule keeps
+    (``batchnorm.batch_norm_routed``: those measured faster than the library's BatchNorm); ``all_shapes`` routes every shape the kernels take.
+    Opt-in: nothing calls it by default.  Returns the number of modules changed (0 on a second call)."""
+    from .batchnorm import HipBatchNorm2d
+    n = 0
+    for m in net.modules():
+        if type(m) is nn.BatchNorm2d:
+            m.__class__ = HipBatchNorm2d
+            if all_shapes:
+                m.hip_all_shapes = True
+            n += 1
+    return n
+
+
 def use_linear_pointwise(net):
     """Inference-only plumbing: evaluate the (BN-folded) 1x1 convs of every channel mixer through the GEMM library
     (bias in the epilogue) instead of the conv library (bias as a separate kernel).  Returns the number replaced."""

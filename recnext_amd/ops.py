@@ -1038,3 +1038,5 @@ from .lsdown import grouped_conv2d, grouped_conv2d_supported, pack_grouped_weigh
 from .lsdown import GroupedConv2dFn, grouped_conv2d_backward, grouped_conv2d_backward_supported, unpack_grouped_weight_grad      # noqa: E402, F401
 # The T / S / B stem (rcx_stem3_fwd): stem3_supported, pack_stem3, stem3.  Written in recnext_amd/lsstem.py (guard-band cases in tests/test_ls_stem_gpu.py).
 from .lsstem import pack_stem3, stem3, stem3_supported                                       # noqa: E402, F401
+# nn.BatchNorm2d of a training step (rcx_batchnorm_*): written in recnext_amd/batchnorm.py (guard-band cases in tests/test_batchnorm_gpu.py)
+from .batchnorm import BatchNormFn, batch_norm_backward, batch_norm_frozen, batch_norm_routed, batch_norm_supported, batch_norm_train      # noqa: E402, F401

@@ -2,7 +2,8 @@
 """Training step (forward + backward + AdamW) of RecNeXt-T / S / B at 224x224: the HIP token half vs the operator chain (tests/ls_eager.py).
 
 engine.py-style step under bf16 autocast, channels_last, synthetic data; one GPU (development tool, not bench.py).  One JSON line per (model, path)
-with the sha256 of the kernel sources it ran on.
+with the sha256 of the kernel sources it ran on.  --hip-batchnorm reroutes every nn.BatchNorm2d of the model to the HIP BatchNorm
+(models.use_hip_batchnorm) before the step; with it, --models also takes the M / A names (recnext_m3 ...) on the HIP token mixers.
 """
 import argparse
 import json
@@ -12,7 +13,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from recnext_amd import lsmodels
+from recnext_amd import lsmodels, models
 from recnext_amd.build import source_fingerprint
 from tests.ls_eager import eager_token_mixer
 
@@ -22,14 +23,17 @@ ap.add_argument("--batch", type=int, default=128)
 ap.add_argument("--steps", type=int, default=8)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--which", default="hip,eager")
+ap.add_argument("--hip-batchnorm", action="store_true", help="reroute every nn.BatchNorm2d to the HIP BatchNorm (models.use_hip_batchnorm): the shapes its routing rule keeps")
+ap.add_argument("--hip-batchnorm-all", action="store_true", help="... and every shape the kernels take, the rule set aside")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 sha = source_fingerprint()
 for name in args.models.split(","):
     for which in args.which.split(","):
         torch.manual_seed(0)
-        net = lsmodels.create_model(name, token_mixer=None if which == "hip" else eager_token_mixer)
+        net = models.create_model(name) if which == "hip" else lsmodels.create_model(name, token_mixer=eager_token_mixer)
         net = net.to(dev).to(memory_format=torch.channels_last).train()
+        routed = models.use_hip_batchnorm(net, all_shapes=args.hip_batchnorm_all) if (args.hip_batchnorm or args.hip_batchnorm_all) else 0
         opt = torch.optim.AdamW(net.parameters(), lr=1e-3)
         x = torch.randn(args.batch, 3, 224, 224, device=dev).contiguous(memory_format=torch.channels_last)
         y = torch.randint(0, 1000, (args.batch,), device=dev)
@@ -52,7 +56,7 @@ for name in args.models.split(","):
         e.record()
         torch.cuda.synchronize()
         ms = s.elapsed_time(e) / args.steps
-        print(json.dumps({"model": name, "token_mixers": which, "batch": args.batch, "steps": args.steps, "ms_per_step": round(ms, 2),
+        print(json.dumps({"model": name, "token_mixers": which, "hip_batchnorm": routed, "all_shapes": bool(args.hip_batchnorm_all), "batch": args.batch, "steps": args.steps, "ms_per_step": round(ms, 2),
                           "images_per_s": round(args.batch / ms * 1e3, 1), "loss": round(float(loss), 4), "library_sources_sha256": sha}), flush=True)
         del net, opt
         torch.cuda.empty_cache()
