@@ -528,6 +528,44 @@ int rcx_batchnorm_frozen_fwd(const void* x, void* y, const float* weight, const 
 int rcx_batchnorm_bwd(const void* x, const void* gy, const float* weight, const float* mean, const float* invstd, void* gx, float* gweight, float* gbias,
                       void* workspace, size_t workspace_bytes, int N, int H, int W, int C, int batch_stats, int dtype, void* stream);
 
+/*
+ * RepVGGDW of the training step as one operator, forward and backward (lsnet/model/recattn.py:8-15: r = lk(x) + sk(x) + x, lk a depthwise 3x3 ConvNorm,
+ * sk a depthwise 1x1 ConvNorm, both BatchNorms on batch statistics, so nothing can be folded).  x, gx: N x H x W x C of `dtype` (float32, bf16 or f16),
+ * R = N H W rows of C contiguous channels, aligned to one element; r and g = dL/dr: the same extents in float32; every parameter, statistic and parameter
+ * gradient float32, aligned to 4 bytes: w3, gw3 (C,1,3,3); all others (C).  Zero padding, biased variances, all arithmetic float32.
+ *   u  = sum_d w3[d] x(p + d) + b3           ia = 1 / sqrt(var u + eps_a)          ib = 1 / sqrt(w1^2 var x + eps_b)
+ *   rcx_repdw_train_fwd  r = gamma_a (u - mean u) ia + beta_a + gamma_b w1 (x - mean x) ib + beta_b + x; saves mean x, var x, mean u, ia; with the four
+ *                        running buffers (all or none; in-out), as nn.BatchNorm2d with the unbiased variance:
+ *                          lk mean <- (1 - ma) old + ma mean u              lk var <- (1 - ma) old + ma var u R / (R - 1)
+ *                          sk mean <- (1 - mb) old + mb (w1 mean x + b1)    sk var <- (1 - mb) old + mb w1^2 var x R / (R - 1)
+ *                        Three launches: statistics of x and u in one pass, finalize, apply.
+ *   rcx_repdw_train_bwd  from x and the four saved statistics (u is formed again, never stored), uhat = (u - mean u) ia, S0 = sum g, Su = sum g uhat,
+ *                        Sx = sum g (x - mean x):
+ *                          gbeta_a = gbeta_b = S0, ggamma_a = Su, ggamma_b = w1 ib Sx, gw1 = gamma_b eps_b ib^3 Sx, gb3 = gb1 = 0 (exactly)
+ *                          gu = gamma_a ia (g - S0 / R - uhat Su / R),   gw3[d] = sum_p gu(p) x(p + d)
+ *                          gx(q) = sum_d w3[d] gu(q - d) + gamma_b w1 ib (g - S0 / R - (x - mean x) w1^2 ib^2 Sx / R) + g
+ *                        gx may be NULL, or the eight parameter gradients together: not both, and none of the eight alone.  Four launches (sums,
+ *                        finalize, gx with per-workgroup tap partials, their reduction), three without the parameter gradients.  Outputs are overwritten.
+ * Statistics are pivoted (n, mean, M2) partials combined pairwise in a fixed tree and then in index order, as rcx_batchnorm_*: never sum x and sum x^2,
+ * no atomics, no waiting between workgroups; 16-byte accesses where C is a multiple of 8 (16-bit) / 4 (float32) and every pointer is aligned to 16
+ * bytes, an element-wide path otherwise; the tiling depends on (N H W, C, dtype) and that choice alone, so repeat launches are bit-identical.
+ * workspace: rcx_repdw_train_workspace_bytes(...) bytes (0 for an unsupported problem), aligned to 4, for both entries.
+ * rcx_repdw_train_supported: 1 / 0, a rule on (N H W, C, dtype) alone.
+ * RCX_ERR_BAD_ARG: a NULL required pointer, some but not all of the running buffers (or of the parameter gradients), a non-positive extent, R = 1, an
+ * unknown dtype, a misaligned pointer, an output or the workspace overlapping an input or each other; RCX_ERR_UNSUPPORTED: 2^31 or more elements;
+ * RCX_ERR_WORKSPACE: a workspace smaller than the query.  All decided before any HIP call.
+ */
+int rcx_repdw_train_supported(int N, int H, int W, int C, int dtype);
+size_t rcx_repdw_train_workspace_bytes(int N, int H, int W, int C, int dtype);
+int rcx_repdw_train_fwd(const void* x, float* r, const float* w3, const float* b3, const float* gamma_a, const float* beta_a, const float* w1, const float* b1,
+                        const float* gamma_b, const float* beta_b, float* lk_running_mean, float* lk_running_var, float* sk_running_mean, float* sk_running_var,
+                        float* save_mean_x, float* save_var_x, float* save_mean_u, float* save_invstd_u, void* workspace, size_t workspace_bytes,
+                        int N, int H, int W, int C, float momentum_a, float eps_a, float momentum_b, float eps_b, int dtype, void* stream);
+int rcx_repdw_train_bwd(const void* x, const float* g, const float* w3, const float* b3, const float* gamma_a, const float* w1, const float* gamma_b,
+                        const float* mean_x, const float* var_x, const float* mean_u, const float* invstd_u, void* gx, float* gw3, float* gb3, float* ggamma_a,
+                        float* gbeta_a, float* gw1, float* gb1, float* ggamma_b, float* gbeta_b, void* workspace, size_t workspace_bytes,
+                        int N, int H, int W, int C, float eps_b, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

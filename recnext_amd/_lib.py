@@ -98,6 +98,10 @@ SIGNATURES = {
     "rcx_batchnorm_train_fwd": (_i, [_vp] * 9 + [_sz] + [_i] * 4 + [ctypes.c_float] * 2 + [_i, _vp]),
     "rcx_batchnorm_frozen_fwd": (_i, [_vp] * 7 + [ctypes.c_float] + [_i] * 5 + [_vp]),
     "rcx_batchnorm_bwd": (_i, [_vp] * 9 + [_sz] + [_i] * 6 + [_vp]),
+    "rcx_repdw_train_supported": (_i, [_i] * 5),
+    "rcx_repdw_train_workspace_bytes": (_sz, [_i] * 5),
+    "rcx_repdw_train_fwd": (_i, [_vp] * 19 + [_sz] + [_i] * 4 + [ctypes.c_float] * 4 + [_i, _vp]),
+    "rcx_repdw_train_bwd": (_i, [_vp] * 21 + [_sz] + [_i] * 4 + [ctypes.c_float] + [_i, _vp]),
 }
 
 _lib = None

@@ -1548,4 +1548,70 @@ int rcx_batchnorm_bwd(const void* x, const void* gy, const float* weight, const 
     return e == hipSuccess ? 0 : hip_fail(e, fn);
 }
 
+// RepVGGDW of a training step as one operator (rcx_repdw.hip).  What it takes is what the BatchNorm kernels take: fewer than 2^31 elements.
+int rcx_repdw_train_supported(int N, int H, int W, int C, int dtype)
+{
+    return rcx::batchnorm_applicable(N, H, W, C, dtype) ? 1 : 0;
+}
+
+size_t rcx_repdw_train_workspace_bytes(int N, int H, int W, int C, int dtype)
+{
+    if (!rcx::batchnorm_applicable(N, H, W, C, dtype)) return 0;
+    return rcx::repdw_train_workspace_bytes(N * H * W, C, dtype);
+}
+
+int rcx_repdw_train_fwd(const void* x, float* r, const float* w3, const float* b3, const float* gamma_a, const float* beta_a, const float* w1, const float* b1,
+                        const float* gamma_b, const float* beta_b, float* lk_running_mean, float* lk_running_var, float* sk_running_mean, float* sk_running_var,
+                        float* save_mean_x, float* save_var_x, float* save_mean_u, float* save_invstd_u, void* workspace, size_t workspace_bytes,
+                        int N, int H, int W, int C, float momentum_a, float eps_a, float momentum_b, float eps_b, int dtype, void* stream)
+{
+    const char* fn = "rcx_repdw_train_fwd";
+    if (!x || !r || !w3 || !b3 || !gamma_a || !beta_a || !w1 || !b1 || !gamma_b || !beta_b || !save_mean_x || !save_var_x || !save_mean_u || !save_invstd_u)
+        return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    const int nrun = !!lk_running_mean + !!lk_running_var + !!sk_running_mean + !!sk_running_var;
+    if (nrun != 0 && nrun != 4) return fail(RCX_ERR_BAD_ARG, "%s: the four running buffers come together or not at all", fn);
+    if (N > 0 && H > 0 && W > 0 && (long long)N * H * W == 1)
+        return fail(RCX_ERR_BAD_ARG, "%s: batch statistics need more than one value per channel (N=%d H=%d W=%d)", fn, N, H, W);
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2, xb = (size_t)N * H * W * C * es, rb = (size_t)N * H * W * C * 4, cb = (size_t)C * 4;
+    if (int rc = check_bn(fn, N, H, W, C, dtype, {x},
+                          {r, w3, b3, gamma_a, beta_a, w1, b1, gamma_b, beta_b, lk_running_mean, lk_running_var, sk_running_mean, sk_running_var, save_mean_x,
+                           save_var_x, save_mean_u, save_invstd_u, workspace},
+                          {{x, xb}, {w3, 9 * cb}, {b3, cb}, {gamma_a, cb}, {beta_a, cb}, {w1, cb}, {b1, cb}, {gamma_b, cb}, {beta_b, cb}},
+                          {{r, rb}, {lk_running_mean, cb}, {lk_running_var, cb}, {sk_running_mean, cb}, {sk_running_var, cb}, {save_mean_x, cb}, {save_var_x, cb},
+                           {save_mean_u, cb}, {save_invstd_u, cb}, {workspace, workspace_bytes}}))
+        return rc;
+    const size_t need = rcx::repdw_train_workspace_bytes(N * H * W, C, dtype);
+    if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes, got %zu", fn, need, workspace ? workspace_bytes : (size_t)0);
+    hipError_t e = rcx::repdw_train_fwd(x, r, w3, b3, gamma_a, beta_a, w1, b1, gamma_b, beta_b, lk_running_mean, lk_running_var, sk_running_mean, sk_running_var,
+                                        save_mean_x, save_var_x, save_mean_u, save_invstd_u, workspace, N, H, W, C, momentum_a, eps_a, momentum_b, eps_b, dtype,
+                                        (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, fn);
+}
+
+int rcx_repdw_train_bwd(const void* x, const float* g, const float* w3, const float* b3, const float* gamma_a, const float* w1, const float* gamma_b,
+                        const float* mean_x, const float* var_x, const float* mean_u, const float* invstd_u, void* gx, float* gw3, float* gb3, float* ggamma_a,
+                        float* gbeta_a, float* gw1, float* gb1, float* ggamma_b, float* gbeta_b, void* workspace, size_t workspace_bytes,
+                        int N, int H, int W, int C, float eps_b, int dtype, void* stream)
+{
+    const char* fn = "rcx_repdw_train_bwd";
+    if (!x || !g || !w3 || !b3 || !gamma_a || !w1 || !gamma_b || !mean_x || !var_x || !mean_u || !invstd_u) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    const int npar = !!gw3 + !!gb3 + !!ggamma_a + !!gbeta_a + !!gw1 + !!gb1 + !!ggamma_b + !!gbeta_b;
+    if (!gx && !npar) return fail(RCX_ERR_BAD_ARG, "%s: null pointer for every output (gx and the parameter gradients)", fn);
+    if (npar != 0 && npar != 8) return fail(RCX_ERR_BAD_ARG, "%s: the eight parameter gradients come together or not at all", fn);
+    if (N > 0 && H > 0 && W > 0 && (long long)N * H * W == 1)
+        return fail(RCX_ERR_BAD_ARG, "%s: batch statistics need more than one value per channel (N=%d H=%d W=%d)", fn, N, H, W);
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2, xb = (size_t)N * H * W * C * es, rb = (size_t)N * H * W * C * 4, cb = (size_t)C * 4;
+    if (int rc = check_bn(fn, N, H, W, C, dtype, {x, gx},
+                          {g, w3, b3, gamma_a, w1, gamma_b, mean_x, var_x, mean_u, invstd_u, gw3, gb3, ggamma_a, gbeta_a, gw1, gb1, ggamma_b, gbeta_b, workspace},
+                          {{x, xb}, {g, rb}, {w3, 9 * cb}, {b3, cb}, {gamma_a, cb}, {w1, cb}, {gamma_b, cb}, {mean_x, cb}, {var_x, cb}, {mean_u, cb}, {invstd_u, cb}},
+                          {{gx, xb}, {gw3, 9 * cb}, {gb3, cb}, {ggamma_a, cb}, {gbeta_a, cb}, {gw1, cb}, {gb1, cb}, {ggamma_b, cb}, {gbeta_b, cb},
+                           {workspace, workspace_bytes}}))
+        return rc;
+    const size_t need = rcx::repdw_train_workspace_bytes(N * H * W, C, dtype);
+    if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes, got %zu", fn, need, workspace ? workspace_bytes : (size_t)0);
+    hipError_t e = rcx::repdw_train_bwd(x, g, w3, b3, gamma_a, w1, gamma_b, mean_x, var_x, mean_u, invstd_u, gx, gw3, gb3, ggamma_a, gbeta_a, gw1, gb1, ggamma_b,
+                                        gbeta_b, workspace, N, H, W, C, eps_b, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, fn);
+}
+
 }  // extern "C"

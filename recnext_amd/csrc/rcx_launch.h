@@ -233,6 +233,16 @@ hipError_t batchnorm_frozen_fwd(const void* x, void* y, const float* weight, con
                                 int R, int C, float eps, int dtype, hipStream_t s);
 hipError_t batchnorm_bwd(const void* x, const void* gy, const float* weight, const float* mean, const float* invstd, void* gx, float* gweight, float* gbias,
                          void* workspace, int R, int C, bool batch_stats, int dtype, hipStream_t s);
+// rcx_repdw.hip: RepVGGDW of a training step (lk 3x3 depthwise + BatchNorm, sk 1x1 depthwise + BatchNorm, + x; both on batch statistics) as one operator
+size_t repdw_train_workspace_bytes(int R, int C, int dtype);
+hipError_t repdw_train_fwd(const void* x, float* out, const float* w3, const float* b3, const float* gamma_a, const float* beta_a, const float* w1, const float* b1,
+                           const float* gamma_b, const float* beta_b, float* lk_rm, float* lk_rv, float* sk_rm, float* sk_rv, float* mean_x, float* var_x,
+                           float* mean_u, float* invstd_u, void* workspace, int N, int H, int W, int C, float mom_a, float eps_a, float mom_b, float eps_b,
+                           int dtype, hipStream_t s);
+hipError_t repdw_train_bwd(const void* x, const float* g, const float* w3, const float* b3, const float* gamma_a, const float* w1, const float* gamma_b,
+                           const float* mean_x, const float* var_x, const float* mean_u, const float* invstd_u, void* gx, float* gw3, float* gb3, float* ggamma_a,
+                           float* gbeta_a, float* gw1, float* gb1, float* ggamma_b, float* gbeta_b, void* workspace, int N, int H, int W, int C, float eps_b,
+                           int dtype, hipStream_t s);
 hipError_t recattn_qkcore(const float* d,const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe, float* out, void* workspace,
                           int B, int Hp, int Wp, int C, int heads, hipStream_t s);
 

@@ -286,6 +286,25 @@ def use_hip_batchnorm(net, all_shapes=False):
     return n
 
 
+def use_fused_rep_train(net, all_shapes=False):
+    """Run every unfused ``RepVGGDW`` of ``net`` (the T / S / B models of ``lsmodels`` and the share-channel models of ``lsshare``) as one HIP operator
+    in a training step: ``ops.RepDwFn`` (``recnext_amd/repdw.py``), three launches forward and at most four backward in place of the operator chain of
+    ``lsmodels._rep_train``.  The call sets a plain attribute on the module and nothing else: state_dict keys, Parameters, buffers and module objects
+    are untouched, strict loads work in either order.  A marked module takes the operator when the tensor is a GPU tensor of float32 / bfloat16 /
+    float16 with more than one value a channel, both convs have float32 weights and biases, both norms are exactly ``nn.BatchNorm2d`` or
+    ``HipBatchNorm2d`` in training mode, affine with float32 parameters, float32 running buffers (or none) and a float momentum, and the shape is one
+    the routing rule keeps (``repdw.repdw_train_routed``; ``all_shapes`` routes every shape the kernels take); both ``num_batches_tracked`` are then
+    bumped by one.  Everything else -- eval-mode or frozen norms, SyncBatchNorm, ``momentum=None``, 16-bit parameters, the fused ``nn.Conv2d`` form,
+    CPU -- keeps the chain unchanged.  Opt-in: nothing calls it by default.  Returns the number of modules newly marked (0 on a second call)."""
+    from . import lsmodels
+    n = 0
+    for m in net.modules():
+        if isinstance(m, lsmodels.RepVGGDW):
+            n += 0 if m.__dict__.get("_fused_rep_train") else 1
+            m._fused_rep_train = "all" if all_shapes else "measured"
+    return n
+
+
 def use_linear_pointwise(net):
     """Inference-only plumbing: evaluate the (BN-folded) 1x1 convs of every channel mixer through the GEMM library
     (bias in the epilogue) instead of the conv library (bias as a separate kernel).  Returns the number replaced."""

@@ -1040,3 +1040,5 @@ from .lsdown import GroupedConv2dFn, grouped_conv2d_backward, grouped_conv2d_bac
 from .lsstem import pack_stem3, stem3, stem3_supported                                       # noqa: E402, F401
 # nn.BatchNorm2d of a training step (rcx_batchnorm_*): written in recnext_amd/batchnorm.py (guard-band cases in tests/test_batchnorm_gpu.py)
 from .batchnorm import BatchNormFn, batch_norm_backward, batch_norm_frozen, batch_norm_routed, batch_norm_supported, batch_norm_train      # noqa: E402, F401
+# RepVGGDW of a training step as one operator (rcx_repdw_train_*): written in recnext_amd/repdw.py (guard-band cases in tests/test_repdw_gpu.py)
+from .repdw import RepDwFn, repdw_train, repdw_train_backward, repdw_train_routed, repdw_train_supported      # noqa: E402, F401
