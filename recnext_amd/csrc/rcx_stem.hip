@@ -8,6 +8,9 @@
 //   A. conv1 + bias + GELU for the 17 x 17 pixels of the intermediate the tile needs, ALSO on the matrix cores (K = 27 taps padded to 32; the im2col operand gathered
 //      from the x tile in LDS: a pixel's inputs are three runs of nine contiguous bf16), rounded to bf16 into LDS (zeros outside the intermediate's plane:
 //      the second conv's padding).  (A first version ran it on the vector pipe, a pixel per thread with the weights as scalar operands: 488 us, no faster than the library.)
+//      A wave's pixel tiles are software-pipelined (round 23): the LDS reads of the next one go out before the GELU of this one, its products are issued between the
+//      two halves of that GELU (each half four pairs in lockstep), the biases sit in registers, and the last two of the ten pixel tiles are shared by the waves of a
+//      pair (both multiply, each takes every other channel group through the GELU): 2.5 epilogues a wave instead of 3 | 3 | 2 | 2.  Same operations, same bits.
 //   B. conv2 as an implicit GEMM on the matrix cores: D (32 out channels x 32 pixels) = sum over (tap, 16-channel group) of W2 fragment x h1 fragment, the h1
 //      fragment read straight from the LDS tile at the tap's offset (8 consecutive channels of one pixel = 16 bytes), the W2 fragments packed on the host
 //      (ops.pack_stem); + b2 -> bf16 -> the wave's own 32 pixel x 32 channel image in LDS -> y, 16 bytes a lane with a pixel's 64 bytes contiguous across four lanes
@@ -67,8 +70,9 @@ __device__ __forceinline__ void wave_sync()
 // CM = channels of the intermediate, KC = CM rounded up to a multiple of 16 (the k-steps of a tap), M1 = ceil(CM / 32) tiles of the first product, MT = output tiles,
 // XW = x rows move as 8-byte pieces (W % 4 == 0 and an 8-byte aligned x: every piece lies wholly inside or outside a row of the image), else as single bf16,
 // GO = an exact GELU after the second conv's bias as well (the front of the T / S / B stem, rcx_conv3s2.hip; the M / A stem has none)
+// (two waves per SIMD wherever the LDS footprint lets two workgroups share a compute unit, KC <= 32: the registers must then fit 256)
 template <int CM, int KC, int MT, bool XW, bool GO = false>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256, KC <= 32 ? 2 : 1)
 k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __restrict__ w1frag, const float* __restrict__ b1, const u32x4q* __restrict__ w2frag,
        const float* __restrict__ b2, int N, int H, int W, int H1, int W1, int H2, int W2, int CO, int tiles_x, int tiles_y, int y16 RCX_STAMP_ARG)
 {
@@ -80,17 +84,32 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
     const u32x4q* const Lf1 = Lf + NF * 64;
     unsigned char* const Lh = lds_raw + (size_t)(NF + 2 * M1) * 1024;                // h1 tile [17 x 17][PIX]
     unsigned char* const Lx = Lh + (size_t)32 * NPT * PIX;                           // x tile [38][XP]
-    float* const Lb1 = reinterpret_cast<float*>(Lx + (size_t)XROWS * XP);           // [32 M1] then b2 [32 MT]
-    float* const Lb2 = Lb1 + 32 * M1;
-    unsigned char* const Ly = reinterpret_cast<unsigned char*>(Lb2 + 32 * MT) + (size_t)(threadIdx.x >> 6) * YIMG;      // this wave's output image: [32 pixels][32 channels] bf16
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    unsigned char* const Ly = Lx + (size_t)XROWS * XP + (size_t)wave * YIMG;         // this wave's output image: [32 pixels][32 channels] bf16
     {                                                                                // the weights: once per workgroup (it walks tiles blockIdx.x, + gridDim.x, ...)
         u32x4q* Lw = reinterpret_cast<u32x4q*>(lds_raw);
         for (int i = threadIdx.x; i < NF * 64; i += 256) Lw[i] = w2frag[i];
         for (int i = threadIdx.x; i < 2 * M1 * 64; i += 256) Lw[NF * 64 + i] = w1frag[i];
-        for (int i = threadIdx.x; i < 32 * M1; i += 256) Lb1[i] = b1[i];
-        for (int i = threadIdx.x; i < 32 * MT; i += 256) Lb2[i] = b2[i];
     }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    // the biases a lane adds, in registers for the whole walk (they depend on neither the pixel tile, the tile nor the image): of the first product's channel groups
+    // g (channels 32 m1 + 8 g + 4 h ..+3 below KC), and of the (output tile, pixel tile) pairs pr = wave + 4 pi this wave takes in phase B.  Both packs are padded to 32s.
+    constexpr int NPR = (2 * MT + 3) / 4;
+    f32x4q b1r[M1][4], b2r[NPR][4];
+#pragma unroll
+    for (int m1 = 0; m1 < M1; ++m1)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float* const bp = b1 + 32 * m1 + 8 * g + 4 * h;
+            b1r[m1][g] = 32 * m1 + 8 * g < KC ? f32x4q{bp[0], bp[1], bp[2], bp[3]} : f32x4q{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+    for (int pi = 0; pi < NPR; ++pi)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int pr = wave + 4 * pi;
+            const float* const bp = b2 + 32 * ((pr < 2 * MT ? pr : 0) >> 1) + 8 * g + 4 * h;
+            b2r[pi][g] = f32x4q{bp[0], bp[1], bp[2], bp[3]};
+        }
     const unsigned xbytes = (unsigned)H * (unsigned)W * 6u;                          // one image of x (3 channels, bf16); checked < 2^31 by the launcher
     // the x tile of a tile: rows 32 ty - 3 + i of the image, bytes 6 (32 tx - 4) .. + 216 of each (zeros outside the image: the first conv's padding).  The tile starts
     // a pixel left of the first one read so that, with XW, its rows are 27 aligned 8-byte pieces of the image: piece e of the tile (row e / 27) lands at LDS byte 8 e,
@@ -137,9 +156,9 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
     const int ntiles = N * tiles_x * tiles_y;
     if ((int)blockIdx.x < ntiles) request_x(blockIdx.x);
 #ifdef RCX_STEM_STAMPS
-    unsigned long long tsum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
-    RCX_STAMP(9)
-    tsum[9] = 0;
+    unsigned long long tsum[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;      // ten phases (tools/stem_timeline.py names them) and the tiles walked
+    RCX_STAMP(10)
+    tsum[10] = 0;
 #endif
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int n = tile / (tiles_x * tiles_y), tr = tile - n * tiles_x * tiles_y, ty = tr / tiles_x, tx = tr - ty * tiles_x;
@@ -160,54 +179,128 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
             const int kk = 16 * ks + 8 * h + jj, dy = (kk * 57) >> 9;
             koff[ks][jj] = kk < 27 ? (unsigned)(dy * XP + 2 * (kk - 9 * dy)) : 0u;         // (k = 27 .. 31: zero weights; any input of the pixel's own window will do)
         }
-    for (int pt = wave; pt < NPT; pt += 4) {
+    bf16x8 w1f[2 * M1];                                                             // the W1 fragments: the same for the wave's three pixel tiles
+#pragma unroll
+    for (int q = 0; q < 2 * M1; ++q) w1f[q] = __builtin_bit_cast(bf16x8, Lf1[q * 64 + lane]);
+    // The ten pixel tiles in three rounds: wave w takes pixel tiles w and w + 4 whole; the last two, 8 and 9, are each gathered and multiplied by BOTH waves of a pair
+    // (w >> 1), and each wave of the pair takes every other channel group of it through bias, GELU and the write: 2.5 epilogues a wave instead of 3 | 3 | 2 | 2.
+    static_assert(NPT == 10, "three rounds of pixel tiles: 4 + 4 + 2");
+    int pp[3];
+    bool pin[3];
+    const unsigned char* pxp[3];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        const int pt = t < 2 ? wave + 4 * t : 8 + (wave >> 1);
         const int p = 32 * pt + r, pc = p < R * R ? p : R * R - 1, i = pc / R, j = pc - i * R;
         const int r1 = 16 * ty - 1 + i, c1 = 16 * tx - 1 + j;
-        const bool inside = p < R * R && r1 >= 0 && r1 < H1 && c1 >= 0 && c1 < W1;
-        const unsigned char* const xp = Lx + (2 * i) * XP + 12 * j + 6;
+        pp[t] = p;
+        pin[t] = p < R * R && r1 >= 0 && r1 < H1 && c1 >= 0 && c1 < W1;
+        pxp[t] = Lx + (2 * i) * XP + 12 * j + 6;
+    }
+    // a pixel tile in three pieces, so that the next one's LDS reads and products are in flight under this one's GELU:
+    auto gather = [&](const unsigned char* xp, unsigned (&v)[16]) {                  // the 16 im2col inputs of this lane: requests only
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) v[8 * ks + jj] = *reinterpret_cast<const unsigned short*>(xp + koff[ks][jj]);
+    };
+    auto products = [&](const unsigned (&v)[16], f32x16 (&d)[M1]) {                  // (waits for the inputs) pack, then the 2 M1 products
         bf16x8 bfr[2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            unsigned short v[8];
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) v[jj] = *reinterpret_cast<const unsigned short*>(xp + koff[ks][jj]);
-            const u32x4q pk = {(unsigned)v[0] | ((unsigned)v[1] << 16), (unsigned)v[2] | ((unsigned)v[3] << 16), (unsigned)v[4] | ((unsigned)v[5] << 16), (unsigned)v[6] | ((unsigned)v[7] << 16)};
+            const unsigned* const w = v + 8 * ks;
+            const u32x4q pk = {w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16)};
             bfr[ks] = __builtin_bit_cast(bf16x8, pk);
         }
-        RCX_STAMP(2)
 #pragma unroll
         for (int m1 = 0; m1 < M1; ++m1) {
-            f32x16 d;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) d[q] = 0.f;
-            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Lf1[(2 * m1 + 0) * 64 + lane]), bfr[0], d, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Lf1[(2 * m1 + 1) * 64 + lane]), bfr[1], d, 0, 0, 0);
-#ifdef RCX_STEM_STAMPS
-            asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, d[15]))));       // the products have landed
-            RCX_STAMP(3)
-#endif
-            // + b1, gelu, bf16 -> the h1 tile (pixels outside the intermediate's plane: zeros, the second conv's padding; channels past CM: zero weights and bias)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int c0 = 32 * m1 + 8 * g + 4 * h;
-                if (32 * m1 + 8 * g < KC) {
-                    const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb1 + c0);
-                    const gelu_f32x2 a = gelu2(gelu_f32x2{d[4 * g] + bb.x, d[4 * g + 1] + bb.y}), b = gelu2(gelu_f32x2{d[4 * g + 2] + bb.z, d[4 * g + 3] + bb.w});
-                    bf16x4 o;
-                    o[0] = (__bf16)(inside ? a.x : 0.f); o[1] = (__bf16)(inside ? a.y : 0.f); o[2] = (__bf16)(inside ? b.x : 0.f); o[3] = (__bf16)(inside ? b.y : 0.f);
-                    *reinterpret_cast<u32x2q*>(Lh + (size_t)p * PIX + 2 * c0) = __builtin_bit_cast(u32x2q, o);
-                }
-            }
-            RCX_STAMP(4)
+            for (int q = 0; q < 16; ++q) d[m1][q] = 0.f;
+            d[m1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1f[2 * m1 + 0], bfr[0], d[m1], 0, 0, 0);
+            d[m1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1f[2 * m1 + 1], bfr[1], d[m1], 0, 0, 0);
         }
-    }
+#ifdef RCX_STEM_STAMPS
+        asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, d[M1 - 1][15]))));       // the products have landed
+        RCX_STAMP(3)
+#endif
+    };
+    // + b1, gelu, bf16 -> the h1 tile (pixels outside the intermediate's plane: zeros, the second conv's padding; channels past CM: zero weights and bias), for the
+    // channel groups g = G0, G0 + GS, .. < GE of product tile m1 that lie below KC: their GELUs in lockstep (rcx_gelu.h), then the converts, selects and writes as a block
+    auto epilogue = [&](auto M1I, auto G0, auto GS, auto GE, const f32x16& d, int p, bool inside) {
+        constexpr int m1 = decltype(M1I)::value, g0 = decltype(G0)::value, gs = decltype(GS)::value, ge = decltype(GE)::value;
+        constexpr int GA = KC - 32 * m1 >= 32 ? 4 : (KC - 32 * m1) / 8, GL = GA < ge ? GA : ge, NG = GL > g0 ? (GL - g0 + gs - 1) / gs : 0;
+        if constexpr (NG > 0) {
+            gelu_f32x2 v[2 * NG];
+#pragma unroll
+            for (int k = 0; k < NG; ++k) {
+                const int g = g0 + gs * k;
+                const f32x4q bb = b1r[m1][g];
+                v[2 * k] = gelu_f32x2{d[4 * g] + bb.x, d[4 * g + 1] + bb.y};
+                v[2 * k + 1] = gelu_f32x2{d[4 * g + 2] + bb.z, d[4 * g + 3] + bb.w};
+            }
+            gelu2_batch<2 * NG>(v);
+            RCX_STAMP(4)
+#pragma unroll
+            for (int k = 0; k < NG; ++k) {
+                const int c0 = 32 * m1 + 8 * (g0 + gs * k) + 4 * h;
+                const gelu_f32x2 a = v[2 * k], b = v[2 * k + 1];
+                bf16x4 o;
+                o[0] = (__bf16)(inside ? a.x : 0.f); o[1] = (__bf16)(inside ? a.y : 0.f); o[2] = (__bf16)(inside ? b.x : 0.f); o[3] = (__bf16)(inside ? b.y : 0.f);
+                *reinterpret_cast<u32x2q*>(Lh + (size_t)p * PIX + 2 * c0) = __builtin_bit_cast(u32x2q, o);
+            }
+            RCX_STAMP(5)
+        }
+    };
+    using C0 = std::integral_constant<int, 0>;
+    using C1 = std::integral_constant<int, 1>;
+    using C2 = std::integral_constant<int, 2>;
+    using C4 = std::integral_constant<int, 4>;
+    auto epilogue_half = [&](auto HF, const f32x16 (&d)[M1], int p, bool inside) {   // groups 2 HF, 2 HF + 1 of every product tile
+        constexpr int hf = decltype(HF)::value;
+        epilogue(C0{}, std::integral_constant<int, 2 * hf>{}, C1{}, std::integral_constant<int, 2 * hf + 2>{}, d[0], p, inside);
+        if constexpr (M1 == 2) epilogue(C1{}, std::integral_constant<int, 2 * hf>{}, C1{}, std::integral_constant<int, 2 * hf + 2>{}, d[M1 - 1], p, inside);
+    };
+    auto epilogue_every_other = [&](auto PAR, const f32x16 (&d)[M1], int p, bool inside) {      // groups PAR, PAR + 2
+        epilogue(C0{}, PAR, C2{}, C4{}, d[0], p, inside);
+        if constexpr (M1 == 2) epilogue(C1{}, PAR, C2{}, C4{}, d[M1 - 1], p, inside);
+    };
+    // The schedule (sched_barrier: the compiler keeps the pieces in this order; the waits it places are counted, the h1 writes behind a gather stay in flight):
+    // the requests of pixel tile t + 1 go out before the GELU of pixel tile t, its products are issued between the two halves of that GELU and run under the second.
+    f32x16 dA[M1], dB[M1];
+    unsigned va[16], vb[16];
+    gather(pxp[0], va);
+    RCX_STAMP(2)
+    products(va, dA);
+    gather(pxp[1], vb);
+    RCX_STAMP(2)
+    __builtin_amdgcn_sched_barrier(0);
+    epilogue_half(C0{}, dA, pp[0], pin[0]);
+    __builtin_amdgcn_sched_barrier(0);
+    products(vb, dB);
+    __builtin_amdgcn_sched_barrier(0);
+    epilogue_half(C1{}, dA, pp[0], pin[0]);
+    __builtin_amdgcn_sched_barrier(0);
+    gather(pxp[2], va);
+    RCX_STAMP(2)
+    __builtin_amdgcn_sched_barrier(0);
+    epilogue_half(C0{}, dB, pp[1], pin[1]);
+    __builtin_amdgcn_sched_barrier(0);
+    products(va, dA);
+    __builtin_amdgcn_sched_barrier(0);
+    epilogue_half(C1{}, dB, pp[1], pin[1]);
+    __builtin_amdgcn_sched_barrier(0);
+    if (wave & 1) epilogue_every_other(C1{}, dA, pp[2], pin[2]);
+    else epilogue_every_other(C0{}, dA, pp[2], pin[2]);
     __syncthreads();
-    RCX_STAMP(5)
-    if (tile + (int)gridDim.x < ntiles) request_x(tile + gridDim.x);
     RCX_STAMP(6)
+    if (tile + (int)gridDim.x < ntiles) request_x(tile + gridDim.x);
+    RCX_STAMP(7)
 
     // ---- B. conv2: wave w takes the (output tile mt, pixel tile nt) pairs w, w + 4, ...; pixel q of the 8 x 8 tile = (q / 8, q % 8)
-    for (int pr = wave; pr < 2 * MT; pr += 4) {
+#pragma unroll
+    for (int pi = 0; pi < NPR; ++pi) {
+        const int pr = wave + 4 * pi;
+        if (pr >= 2 * MT) break;
         const int mt = pr >> 1, nt = pr & 1;
         const int q = 32 * nt + r, py = q >> 3, px = q & 7;      // (the product's pixel of this lane)
         const unsigned char* const hp = Lh + (size_t)((2 * py) * R + 2 * px) * PIX + 16 * h;
@@ -225,23 +318,23 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
         }
 #ifdef RCX_STEM_STAMPS
         asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, d0[15]))), "s"(__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, d1[15]))));
-        RCX_STAMP(7)
+        RCX_STAMP(8)
 #endif
         // + b2 -> bf16 -> this wave's LDS image (pixel r: 64 bytes, its 8-byte pieces XOR-ed with (r >> 1) & 7: a store's 16 lanes hit 16 bank pairs), then out with a
         // pixel's 64 bytes contiguous across 4 lanes (16 bytes each; 8 lanes of 8 bytes where 2 CO or y is not 16-byte aligned): a request covers whole 64-byte runs of y
-        // instead of 8 bytes of each of 32 pixels
+        // instead of 8 bytes of each of 32 pixels.  GO: the eight pairs' GELUs in lockstep, then the converts and the four writes as a block
+        gelu_f32x2 v[8];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const f32x4q bb = *reinterpret_cast<const f32x4q*>(Lb2 + 32 * mt + 8 * g + 4 * h);
+            const f32x4q bb = b2r[pi][g];
+            v[2 * g] = gelu_f32x2{d0[4 * g + 0] + d1[4 * g + 0] + bb.x, d0[4 * g + 1] + d1[4 * g + 1] + bb.y};
+            v[2 * g + 1] = gelu_f32x2{d0[4 * g + 2] + d1[4 * g + 2] + bb.z, d0[4 * g + 3] + d1[4 * g + 3] + bb.w};
+        }
+        if constexpr (GO) gelu2_batch<8>(v);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
             bf16x4 o;
-            if constexpr (GO) {
-                const gelu_f32x2 a = gelu2(gelu_f32x2{d0[4 * g + 0] + d1[4 * g + 0] + bb.x, d0[4 * g + 1] + d1[4 * g + 1] + bb.y});
-                const gelu_f32x2 b = gelu2(gelu_f32x2{d0[4 * g + 2] + d1[4 * g + 2] + bb.z, d0[4 * g + 3] + d1[4 * g + 3] + bb.w});
-                o[0] = (__bf16)a.x; o[1] = (__bf16)a.y; o[2] = (__bf16)b.x; o[3] = (__bf16)b.y;
-            } else {
-                o[0] = (__bf16)(d0[4 * g + 0] + d1[4 * g + 0] + bb.x); o[1] = (__bf16)(d0[4 * g + 1] + d1[4 * g + 1] + bb.y);
-                o[2] = (__bf16)(d0[4 * g + 2] + d1[4 * g + 2] + bb.z); o[3] = (__bf16)(d0[4 * g + 3] + d1[4 * g + 3] + bb.w);
-            }
+            o[0] = (__bf16)v[2 * g].x; o[1] = (__bf16)v[2 * g].y; o[2] = (__bf16)v[2 * g + 1].x; o[3] = (__bf16)v[2 * g + 1].y;
             *reinterpret_cast<u32x2q*>(Ly + 64 * r + 8 * ((2 * g + h) ^ ((r >> 1) & 7))) = __builtin_bit_cast(u32x2q, o);
         }
         wave_sync();
@@ -261,15 +354,15 @@ k_stem(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const u32x4q* __res
             }
         }
         wave_sync();                                   // (MT = 3: the wave's next pair writes the image again)
-        RCX_STAMP(8)
+        RCX_STAMP(9)
     }
 #ifdef RCX_STEM_STAMPS
-    tsum[9] += 1;
+    tsum[10] += 1;
 #endif
     }
 #ifdef RCX_STEM_STAMPS
     if (lane == 0)
-        for (int k = 0; k < 10; ++k) stamps[((size_t)blockIdx.x * 4 + wave) * 10 + k] = tsum[k];
+        for (int k = 0; k < 11; ++k) stamps[((size_t)blockIdx.x * 4 + wave) * 11 + k] = tsum[k];
 #endif
 }
 
@@ -304,7 +397,7 @@ static hipError_t launch_stem(const void* x, void* y, const void* w1, const floa
     const int H1 = (H + 1) / 2, W1 = (W + 1) / 2, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2, tx = (W2 + 7) / 8, ty = (H2 + 7) / 8;
     constexpr int KS = 9 * (KC / 16), PIX = 2 * KC + 16;
     constexpr int M1 = (CM + 31) / 32;
-    const size_t lds = (size_t)(MT * KS + 2 * M1) * 1024 + (size_t)320 * PIX + (size_t)38 * 216 + sizeof(float) * 32 * (M1 + MT) + (size_t)4 * stem::YIMG;
+    const size_t lds = (size_t)(MT * KS + 2 * M1) * 1024 + (size_t)320 * PIX + (size_t)38 * 216 + (size_t)4 * stem::YIMG;      // (the biases live in registers)
     // rows of x as 8-byte pieces where every row of every image starts on one (else as single bf16); 16-byte stores where every pixel of y does (else 8-byte)
     const bool xw = W % 4 == 0 && ((size_t)x & 7) == 0;
     const int y16 = CO % 8 == 0 && ((size_t)y & 15) == 0;
@@ -380,7 +473,7 @@ hipError_t stem_front_fwd(const void* x, void* y, const void* w1, const float* b
 }  // namespace rcx
 
 #ifdef RCX_STEM_STAMPS
-// the diagnostic build: this translation unit alone as a shared object (tools/stem_timeline.py); stamps = [grid][4 waves][10] cycle sums
+// the diagnostic build: this translation unit alone as a shared object (tools/stem_timeline.py); stamps = [grid][4 waves][11] cycle sums
 extern "C" int rcx_stem_diag_fwd(const void* x, void* y, const void* w1frag, const float* b1, const void* w2frag, const float* b2, int N, int H, int W, int CM, int CO, void* stamps, void* stream)
 {
     rcx::g_stamps = (unsigned long long*)stamps;

@@ -5,7 +5,9 @@ the phase boundaries of every wave, summed over the workgroup's tiles into a buf
     python tools/stem_timeline.py --build            # compile recnext_amd/lib/librcx_stem_diag.so (no GPU needed)
     python tools/stem_timeline.py [--lib PATH]       # run it: cycles per tile, median (p10 - p90) over workgroups, per wave
 
-The stamps fence the schedule (each drains the wave's LDS reads), so read the SHARES, not the length, of this build."""
+The stamps fence the schedule (each drains the wave's LDS reads: in this build a pixel tile's gather has landed before the previous one's GELU starts, and the
+products are waited for before the GELU's second half, which the product build overlaps), so read the SHARES, not the length, of this build.  In phase A a wave
+gathers and multiplies three pixel tiles and takes 2.5 of them through GELU and write (the last round is shared by the waves of a pair)."""
 import argparse
 import ctypes
 import os
@@ -15,8 +17,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 DIAG = os.path.join(ROOT, "recnext_amd", "lib", "librcx_stem_diag.so")
-SEGMENTS = ["x tile -> LDS (+ wait for x)", "wait at barrier 1", "A gather (LDS reads back)", "A products", "A bias + GELU + h1 write", "wait at barrier 2", "request next x",
-            "B products (reads + MFMA)", "B bias + stores"]
+SEGMENTS = ["x tile -> LDS (+ wait for x)", "wait at barrier 1", "A gather (LDS reads back)", "A products", "A bias + GELU", "A convert + h1 write", "wait at barrier 2",
+            "request next x", "B products (reads + MFMA)", "B bias + stores"]
+NS = len(SEGMENTS)                                                       # the kernel's tsum[NS] counts the tiles a workgroup walked
 
 
 def build():
@@ -49,7 +52,7 @@ def main():
     lib = ctypes.CDLL(a.lib)
     lib.rcx_stem_diag_fwd.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
-    stamps = torch.zeros(4 * cus, 4, 10, dtype=torch.int64, device=dev)  # at most four workgroups per compute unit
+    stamps = torch.zeros(4 * cus, 4, NS + 1, dtype=torch.int64, device=dev)  # at most four workgroups per compute unit
     torch.cuda.synchronize()
     for _ in range(3):                                                   # warm: the last launch's stamps are read
         stamps.zero_()
@@ -58,9 +61,9 @@ def main():
         torch.cuda.synchronize()
     print(f"stem timeline, N={n} CM={cm} CO={co} {h}x{w}: diagnostic output {'identical to' if torch.equal(y, ref) else 'DIFFERS from'} the product build's")
     s = stamps.cpu().double()
-    s = s[s[:, 0, 9] > 0]                                                # workgroups that ran
-    tiles = s[:, :, 9:10]
-    per = s[:, :, :9] / tiles                                            # cycles per tile
+    s = s[s[:, 0, NS] > 0]                                               # workgroups that ran
+    tiles = s[:, :, NS:NS + 1]
+    per = s[:, :, :NS] / tiles                                            # cycles per tile
     print(f"{s.shape[0]} workgroups, {float(tiles[:, 0, 0].median()):.1f} tiles each (median); cycles per tile of one wave: median (p10 - p90) over workgroups")
     q = lambda t, p: float(torch.quantile(t, p))
     for k, name in enumerate(SEGMENTS):
