@@ -566,6 +566,44 @@ int rcx_repdw_train_bwd(const void* x, const float* g, const float* w3, const fl
                         float* gbeta_a, float* gw1, float* gb1, float* ggamma_b, float* gbeta_b, void* workspace, size_t workspace_bytes,
                         int N, int H, int W, int C, float eps_b, int dtype, void* stream);
 
+/*
+ * A depthwise ConvNorm of the training step as one operator, forward and backward: the slice mixers' down[0] (5x5, stride 2), pe (3x3), conv (5x5 on
+ * x + resize(a)) and LinearAttention3's pe (lsnet/model/recattn.py:54-67, :89-112), the BatchNorm on batch statistics, so nothing can be folded.
+ * x, gx: N x H x W x C of `dtype` (float32, bf16 or f16), aligned to one element; y, g = dL/dy: N x Ho x Wo x C of `dtype`, Ho = (H - 1) / stride + 1,
+ * Wo likewise, R = N Ho Wo rows of C contiguous channels; a, ga: N x Hc x Wc x C float32, or NULL (the plain form; Hc, Wc are then ignored); u: R x C
+ * float32; w, gw (C,1,k,k) and every other parameter, statistic and parameter gradient (C): float32, aligned to 4 bytes.  k = 3 | 5, zero padding k / 2,
+ * stride = 1 | 2 (the up-add form: stride 1 only), all arithmetic float32.
+ *   z = x + a(floor(h Hc / H), floor(w Wc / W))   (nearest, the float index arithmetic of rcx_upadd_dwconv_fwd)        u = sum_d w[d] z(p stride + d - k/2) + b
+ *   rcx_dwconv_bn_train_fwd  y = gamma (u - mean u) ia + beta, ia = 1 / sqrt(var u + eps) (biased variance), rounded once from float32; writes u, mean u
+ *                            and ia; b may be NULL; with running_mean / running_var (both or neither; in-out), as nn.BatchNorm2d with the unbiased
+ *                            variance R / (R - 1).  Three launches: conv + statistics in one pass (u is stored), finalize, apply from u.
+ *   rcx_dwconv_bn_train_bwd  from x, a, the stored u and the two saved statistics; g is read in y's dtype as it is.  uhat = (u - mean u) ia,
+ *                            S0 = sum g, Su = sum g uhat, gu = gamma ia (g - S0 / R - uhat Su / R):
+ *                              gbeta = S0, ggamma = Su, gb = 0 (exactly: a bias in front of a BatchNorm on batch statistics has no gradient; written as zeros)
+ *                              gw[d] = sum_p gu(p) z(p stride + d - k/2)
+ *                              gx(q) = sum_d w[d] gu(p), p stride + d - k/2 = q     (gu from g and u at those p: u is never formed again)
+ *                              ga(r) = sum of gx, before its rounding, over the fine pixels whose nearest source is r, in raster order (a gather)
+ *                            Every output may be NULL, not all of them; ga needs a.  Launches: sums, finalize; one for gx and ga (skipped when both are
+ *                            NULL); two for gw (per-workgroup tap partials, their reduction; skipped when gw is NULL).  Outputs are overwritten.
+ * Statistics are pivoted (n, mean, M2) partials combined pairwise in a fixed tree and then in index order, as rcx_batchnorm_*: never sum u and sum u^2,
+ * no atomics, no waiting between workgroups; 16-byte accesses where C is a multiple of 8 (16-bit) / 4 (float32) and every pointer is aligned to 16
+ * bytes, an element-wide path otherwise; the tiling depends on (rows, C, dtype) and that choice alone, so repeat launches are bit-identical, and an
+ * image's u, y and gx do not depend on the other images but through the statistics.
+ * workspace: rcx_dwconv_bn_train_workspace_bytes(...) bytes (0 for an unsupported problem), aligned to 4, for both entries.
+ * rcx_dwconv_bn_train_supported: 1 / 0, a rule on (N, H, W, C, k, stride, has_coarse, dtype) alone.
+ * RCX_ERR_BAD_ARG: a NULL required pointer, one running pointer without the other, every output NULL, ga without a, a non-positive extent, R = 1, an
+ * unknown dtype, a misaligned pointer, an output or the workspace overlapping an input or each other; RCX_ERR_UNSUPPORTED: k not 3 or 5, stride not 1 or
+ * 2, the up-add form with stride 2, 2^31 or more elements; RCX_ERR_WORKSPACE: a workspace smaller than the query.  All decided before any HIP call.
+ */
+int rcx_dwconv_bn_train_supported(int N, int H, int W, int C, int k, int stride, int has_coarse, int dtype);
+size_t rcx_dwconv_bn_train_workspace_bytes(int N, int H, int W, int C, int k, int stride, int has_coarse, int dtype);
+int rcx_dwconv_bn_train_fwd(const void* x, const float* a, int Hc, int Wc, const float* w, const float* b, const float* gamma, const float* beta,
+                            float* running_mean, float* running_var, void* y, float* u, float* save_mean, float* save_invstd, void* workspace,
+                            size_t workspace_bytes, int N, int H, int W, int C, int k, int stride, float momentum, float eps, int dtype, void* stream);
+int rcx_dwconv_bn_train_bwd(const void* x, const float* a, int Hc, int Wc, const float* u, const void* g, const float* w, const float* gamma, const float* mean,
+                            const float* invstd, void* gx, float* ga, float* gw, float* gb, float* ggamma, float* gbeta, void* workspace, size_t workspace_bytes,
+                            int N, int H, int W, int C, int k, int stride, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,10 @@ SIGNATURES = {
     "rcx_repdw_train_workspace_bytes": (_sz, [_i] * 5),
     "rcx_repdw_train_fwd": (_i, [_vp] * 19 + [_sz] + [_i] * 4 + [ctypes.c_float] * 4 + [_i, _vp]),
     "rcx_repdw_train_bwd": (_i, [_vp] * 21 + [_sz] + [_i] * 4 + [ctypes.c_float] + [_i, _vp]),
+    "rcx_dwconv_bn_train_supported": (_i, [_i] * 8),
+    "rcx_dwconv_bn_train_workspace_bytes": (_sz, [_i] * 8),
+    "rcx_dwconv_bn_train_fwd": (_i, [_vp, _vp, _i, _i] + [_vp] * 11 + [_sz] + [_i] * 6 + [ctypes.c_float] * 2 + [_i, _vp]),
+    "rcx_dwconv_bn_train_bwd": (_i, [_vp, _vp, _i, _i] + [_vp] * 13 + [_sz] + [_i] * 7 + [_vp]),
 }
 
 _lib = None

@@ -1614,4 +1614,76 @@ int rcx_repdw_train_bwd(const void* x, const float* g, const float* w3, const fl
     return e == hipSuccess ? 0 : hip_fail(e, fn);
 }
 
+// A depthwise ConvNorm of a training step as one operator (rcx_dwbn.hip): k = 3 | 5, stride 1 | 2, the up-add form at stride 1 only, and what the
+// BatchNorm kernels take: fewer than 2^31 elements.
+int rcx_dwconv_bn_train_supported(int N, int H, int W, int C, int k, int stride, int has_coarse, int dtype)
+{
+    return rcx::dwconv_bn_train_applicable(N, H, W, C, k, stride, has_coarse, dtype) ? 1 : 0;
+}
+
+size_t rcx_dwconv_bn_train_workspace_bytes(int N, int H, int W, int C, int k, int stride, int has_coarse, int dtype)
+{
+    if (!rcx::dwconv_bn_train_applicable(N, H, W, C, k, stride, has_coarse, dtype)) return 0;
+    return rcx::dwconv_bn_train_workspace_bytes(N, H, W, C, k, stride, dtype);
+}
+
+namespace {
+// the checks the two entries share, ahead of check_bn: the conv's form, the coarse plane, R = 1
+int check_dwbn(const char* fn, int N, int H, int W, int k, int stride, const float* a, int Hc, int Wc)
+{
+    if (k != 3 && k != 5) return fail(RCX_ERR_UNSUPPORTED, "%s: kernel size %d (3 or 5)", fn, k);
+    if (stride != 1 && stride != 2) return fail(RCX_ERR_UNSUPPORTED, "%s: stride %d (1 or 2)", fn, stride);
+    if (a && stride != 1) return fail(RCX_ERR_UNSUPPORTED, "%s: the up-add form (a given) is stride 1 only", fn);
+    if (a && (Hc <= 0 || Wc <= 0)) return fail(RCX_ERR_BAD_ARG, "%s: non-positive coarse extent Hc=%d Wc=%d", fn, Hc, Wc);
+    if (a && ((long long)Hc >= (1ll << 31) / Wc || (long long)N * Hc * Wc >= (1ll << 31)))
+        return fail(RCX_ERR_UNSUPPORTED, "%s: N=%d Hc=%d Wc=%d: 2^31 or more coarse pixels", fn, N, Hc, Wc);
+    if (N > 0 && H > 0 && W > 0 && (long long)N * ((H - 1) / stride + 1) * ((W - 1) / stride + 1) == 1)
+        return fail(RCX_ERR_BAD_ARG, "%s: batch statistics need more than one value per channel (N=%d H=%d W=%d stride %d)", fn, N, H, W, stride);
+    return 0;
+}
+}  // namespace
+
+int rcx_dwconv_bn_train_fwd(const void* x, const float* a, int Hc, int Wc, const float* w, const float* b, const float* gamma, const float* beta,
+                            float* running_mean, float* running_var, void* y, float* u, float* save_mean, float* save_invstd, void* workspace,
+                            size_t workspace_bytes, int N, int H, int W, int C, int k, int stride, float momentum, float eps, int dtype, void* stream)
+{
+    const char* fn = "rcx_dwconv_bn_train_fwd";
+    if (!x || !w || !gamma || !beta || !y || !u || !save_mean || !save_invstd) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (!running_mean != !running_var) return fail(RCX_ERR_BAD_ARG, "%s: running_mean and running_var come together or not at all", fn);
+    if (int rc = check_dwbn(fn, N, H, W, k, stride, a, Hc, Wc)) return rc;
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2, cb = (size_t)C * 4, xb = (size_t)N * H * W * C * es;
+    const size_t R = (size_t)N * ((H - 1) / stride + 1) * ((W - 1) / stride + 1), ab = a ? (size_t)N * Hc * Wc * cb : 0;
+    if (int rc = check_bn(fn, N, H, W, C, dtype, {x, y}, {a, w, b, gamma, beta, running_mean, running_var, u, save_mean, save_invstd, workspace},
+                          {{x, xb}, {a, ab}, {w, (size_t)k * k * cb}, {b, cb}, {gamma, cb}, {beta, cb}},
+                          {{y, R * C * es}, {u, R * cb}, {running_mean, cb}, {running_var, cb}, {save_mean, cb}, {save_invstd, cb}, {workspace, workspace_bytes}}))
+        return rc;
+    const size_t need = rcx::dwconv_bn_train_workspace_bytes(N, H, W, C, k, stride, dtype);
+    if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes, got %zu", fn, need, workspace ? workspace_bytes : (size_t)0);
+    hipError_t e = rcx::dwconv_bn_train_fwd(x, a, Hc, Wc, w, b, gamma, beta, running_mean, running_var, y, u, save_mean, save_invstd, workspace, N, H, W, C, k, stride,
+                                            momentum, eps, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, fn);
+}
+
+int rcx_dwconv_bn_train_bwd(const void* x, const float* a, int Hc, int Wc, const float* u, const void* g, const float* w, const float* gamma, const float* mean,
+                            const float* invstd, void* gx, float* ga, float* gw, float* gb, float* ggamma, float* gbeta, void* workspace, size_t workspace_bytes,
+                            int N, int H, int W, int C, int k, int stride, int dtype, void* stream)
+{
+    const char* fn = "rcx_dwconv_bn_train_bwd";
+    if (!x || !u || !g || !w || !gamma || !mean || !invstd) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (!gx && !ga && !gw && !gb && !ggamma && !gbeta) return fail(RCX_ERR_BAD_ARG, "%s: null pointer for every output (gx, ga, gw, gb, ggamma, gbeta)", fn);
+    if (ga && !a) return fail(RCX_ERR_BAD_ARG, "%s: ga without a (the plain form has no coarse plane)", fn);
+    if (int rc = check_dwbn(fn, N, H, W, k, stride, a, Hc, Wc)) return rc;
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2, cb = (size_t)C * 4, xb = (size_t)N * H * W * C * es;
+    const size_t R = (size_t)N * ((H - 1) / stride + 1) * ((W - 1) / stride + 1), ab = a ? (size_t)N * Hc * Wc * cb : 0;
+    if (int rc = check_bn(fn, N, H, W, C, dtype, {x, g, gx}, {a, u, w, gamma, mean, invstd, ga, gw, gb, ggamma, gbeta, workspace},
+                          {{x, xb}, {a, ab}, {u, R * cb}, {g, R * C * es}, {w, (size_t)k * k * cb}, {gamma, cb}, {mean, cb}, {invstd, cb}},
+                          {{gx, xb}, {ga, ab}, {gw, (size_t)k * k * cb}, {gb, cb}, {ggamma, cb}, {gbeta, cb}, {workspace, workspace_bytes}}))
+        return rc;
+    const size_t need = rcx::dwconv_bn_train_workspace_bytes(N, H, W, C, k, stride, dtype);
+    if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes, got %zu", fn, need, workspace ? workspace_bytes : (size_t)0);
+    hipError_t e = rcx::dwconv_bn_train_bwd(x, a, Hc, Wc, u, g, w, gamma, mean, invstd, gx, ga, gw, gb, ggamma, gbeta, workspace, N, H, W, C, k, stride, dtype,
+                                            (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, fn);
+}
+
 }  // extern "C"

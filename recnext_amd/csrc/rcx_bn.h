@@ -1,5 +1,6 @@
-// What the NHWC per-channel reduction kernels share (rcx_bn.hip: nn.BatchNorm2d; rcx_repdw.hip: RepVGGDW of a training step): the plan of a launch,
-// the pivoted (n, mean, M2) combine, the row walk of a thread, the LDS slots of the fixed tree and the dtype dispatch.
+// What the NHWC per-channel reduction kernels share (rcx_bn.hip: nn.BatchNorm2d; rcx_repdw.hip: RepVGGDW of a training step; rcx_dwbn.hip: a depthwise
+// ConvNorm of a training step): the plan of a launch, the pivoted (n, mean, M2) combine, the row walk of a thread, the LDS slots of the fixed tree, the
+// tree itself and the dtype dispatch.
 #pragma once
 #include <initializer_list>
 #include "rcx_common.h"
@@ -80,6 +81,49 @@ __device__ __forceinline__ int tree_top(int n)
 // LDS of the reduction kernels: [j][ty][tx] floats, tx fastest (no bank conflicts across a row of threads)
 #define BN_SLOT(j) (((j) * TY + ty) * TX + tx)
 #define BN_SLOT_AT(j, yy) (((j) * TY + (yy)) * TX + tx)
+
+// the fixed tree of k_bn_stats over the TY thread rows for one set of V (mean, M2); sm holds 2 V kThreads floats, sn kThreads.  Ends on a barrier.
+template <int V>
+__device__ __forceinline__ void tree_chan(float* sm, float* sn, float n, float (&mean)[V], float (&m2)[V], int TX, int TY, int tx, int ty)
+{
+    for (int s = tree_top(TY); s >= 1; s >>= 1) {
+        if (ty >= s && ty < 2 * s) {
+            sn[ty * TX + tx] = n;
+#pragma unroll
+            for (int j = 0; j < V; ++j) { sm[BN_SLOT(2 * j)] = mean[j]; sm[BN_SLOT(2 * j + 1)] = m2[j]; }
+        }
+        __syncthreads();
+        if (ty < s && ty + s < TY) {
+            const float nb = sn[(ty + s) * TX + tx];
+            float na = n;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                na = n;
+                chan(na, mean[j], m2[j], nb, sm[BN_SLOT_AT(2 * j, ty + s)], sm[BN_SLOT_AT(2 * j + 1, ty + s)]);
+            }
+            n = na;
+        }
+        __syncthreads();
+    }
+}
+
+// ... and for plain sums: K values a thread, added in the same tree.  sm holds K kThreads floats.  Ends on a barrier.
+template <int K>
+__device__ __forceinline__ void tree_sum(float* sm, float (&v)[K], int TX, int TY, int tx, int ty)
+{
+    for (int s = tree_top(TY); s >= 1; s >>= 1) {
+        if (ty >= s && ty < 2 * s) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) sm[BN_SLOT(j)] = v[j];
+        }
+        __syncthreads();
+        if (ty < s && ty + s < TY) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) v[j] += sm[BN_SLOT_AT(j, ty + s)];
+        }
+        __syncthreads();
+    }
+}
 
 inline dim3 grid_of(const Plan& p) { return dim3((unsigned)p.CT, (unsigned)p.P); }
 inline dim3 block_of(const Plan& p) { return dim3((unsigned)p.TX, (unsigned)p.TY); }

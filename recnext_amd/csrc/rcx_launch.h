@@ -243,6 +243,16 @@ hipError_t repdw_train_bwd(const void* x, const float* g, const float* w3, const
                            const float* mean_x, const float* var_x, const float* mean_u, const float* invstd_u, void* gx, float* gw3, float* gb3, float* ggamma_a,
                            float* gbeta_a, float* gw1, float* gb1, float* ggamma_b, float* gbeta_b, void* workspace, int N, int H, int W, int C, float eps_b,
                            int dtype, hipStream_t s);
+// rcx_dwbn.hip: a depthwise ConvNorm of a training step (k x k depthwise conv, k = 3 | 5, stride 1 | 2, on x or on x + nearest-resize(a), + BatchNorm on
+// batch statistics) as one operator; u = the conv's float32 output, stored by the forward and read by the backward
+bool dwconv_bn_train_applicable(long long N, long long H, long long W, long long C, int k, int stride, int has_coarse, int dtype);
+size_t dwconv_bn_train_workspace_bytes(int N, int H, int W, int C, int k, int stride, int dtype);
+hipError_t dwconv_bn_train_fwd(const void* x, const float* a, int Hc, int Wc, const float* w, const float* b, const float* gamma, const float* beta, float* rm,
+                               float* rv, void* y, float* u, float* mean_u, float* invstd_u, void* workspace, int N, int H, int W, int C, int k, int stride,
+                               float momentum, float eps, int dtype, hipStream_t s);
+hipError_t dwconv_bn_train_bwd(const void* x, const float* a, int Hc, int Wc, const float* u, const void* gy, const float* w, const float* gamma, const float* mean_u,
+                               const float* invstd_u, void* gx, float* ga, float* gw, float* gb, float* ggamma, float* gbeta, void* workspace, int N, int H, int W,
+                               int C, int k, int stride, int dtype, hipStream_t s);
 hipError_t recattn_qkcore(const float* d,const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe, float* out, void* workspace,
                           int B, int Hp, int Wp, int C, int heads, hipStream_t s);
 

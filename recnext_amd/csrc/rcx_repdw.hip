@@ -32,6 +32,8 @@ using bn::chan;
 using bn::chunk_rows;
 using bn::thread_rows;
 using bn::tree_top;
+using bn::tree_chan;
+using bn::tree_sum;
 
 // the three reductions, the apply and the input gradient all walk the rows by the plan of the statistics: one P for the workspace
 inline Plan plan_of(int R, int C, int V) { return bn::stats_plan(R, C, V); }
@@ -80,49 +82,6 @@ __device__ __forceinline__ void conv_u(const T* __restrict__ xi, int h, int w, i
     }
 #pragma unroll
     for (int j = 0; j < V; ++j) u[j] += b3[j];
-}
-
-// the fixed tree of k_bn_stats over the TY thread rows for one set of V (mean, M2); sm holds 2 V kThreads floats, sn kThreads.  Ends on a barrier.
-template <int V>
-__device__ __forceinline__ void tree_chan(float* sm, float* sn, float n, float (&mean)[V], float (&m2)[V], int TX, int TY, int tx, int ty)
-{
-    for (int s = tree_top(TY); s >= 1; s >>= 1) {
-        if (ty >= s && ty < 2 * s) {
-            sn[ty * TX + tx] = n;
-#pragma unroll
-            for (int j = 0; j < V; ++j) { sm[BN_SLOT(2 * j)] = mean[j]; sm[BN_SLOT(2 * j + 1)] = m2[j]; }
-        }
-        __syncthreads();
-        if (ty < s && ty + s < TY) {
-            const float nb = sn[(ty + s) * TX + tx];
-            float na = n;
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                na = n;
-                chan(na, mean[j], m2[j], nb, sm[BN_SLOT_AT(2 * j, ty + s)], sm[BN_SLOT_AT(2 * j + 1, ty + s)]);
-            }
-            n = na;
-        }
-        __syncthreads();
-    }
-}
-
-// ... and for plain sums: K values a thread, added in the same tree.  sm holds K kThreads floats.  Ends on a barrier.
-template <int K>
-__device__ __forceinline__ void tree_sum(float* sm, float (&v)[K], int TX, int TY, int tx, int ty)
-{
-    for (int s = tree_top(TY); s >= 1; s >>= 1) {
-        if (ty >= s && ty < 2 * s) {
-#pragma unroll
-            for (int j = 0; j < K; ++j) sm[BN_SLOT(j)] = v[j];
-        }
-        __syncthreads();
-        if (ty < s && ty + s < TY) {
-#pragma unroll
-            for (int j = 0; j < K; ++j) v[j] += sm[BN_SLOT_AT(j, ty + s)];
-        }
-        __syncthreads();
-    }
 }
 
 // part: P x (mean x, M2 x, mean u, M2 u), each (C)

@@ -305,6 +305,37 @@ def use_fused_rep_train(net, all_shapes=False):
     return n
 
 
+def use_fused_conv_norm_train(net, all_shapes=False):
+    """Run the depthwise ``ConvNorm``s of every slice mixer of ``net`` as one HIP operator each in a training step: ``down[0]``, ``pe`` and ``conv`` of every
+    ``RecAttn2d`` (the M / A families) and ``LsRecAttn2d`` (T / S / B) and ``pe`` of every ``LinearAttention3`` -- the modules
+    ``recattn._conv_norm_train`` / ``_upadd_conv_norm_train`` are called with by the mixers -- run ``ops.DwConvBnFn`` (``recnext_amd/dwbn.py``), three
+    launches forward and at most five backward in place of the conv's Function followed by the module's BatchNorm.  (``RepVGGDW.lk`` has its own
+    operator: ``use_fused_rep_train``.)  The call sets a plain attribute on the module and nothing else: state_dict keys, Parameters, buffers and
+    module objects are untouched, strict loads work in either order.  A marked module takes the operator when the tensor is a GPU tensor of float32 /
+    bfloat16 / float16 with more than one output value a channel, the conv's weight (and bias, if it has one) is float32, the norm is exactly
+    ``nn.BatchNorm2d`` or ``HipBatchNorm2d`` in training mode, affine with float32 parameters, float32 running buffers (or none) and a float momentum,
+    the resize mode is ``"nearest"`` (the up-add form) and the shape is one the routing rule keeps (``dwbn.dwconv_bn_train_routed``; ``all_shapes``
+    routes every shape the kernels take); ``num_batches_tracked`` is then bumped by one.  Everything else -- eval-mode or frozen norms, SyncBatchNorm,
+    ``momentum=None``, 16-bit parameters, the folded ``nn.Conv2d`` form, bilinear mode, CPU -- keeps the chain unchanged.  Opt-in: nothing calls it by
+    default.  Returns the number of modules newly marked (0 on a second call)."""
+    from . import lsmodels
+    from .layers import ConvNorm
+    from .recattn import LinearAttention, RecAttn2d
+    n = 0
+    for m in net.modules():
+        if isinstance(m, RecAttn2d):
+            hosts = (m.down[0], m.conv)
+        elif isinstance(m, (LinearAttention, lsmodels.LinearAttention3)):
+            hosts = (m.pe,)
+        else:
+            continue
+        for cn in hosts:
+            if isinstance(cn, ConvNorm):
+                n += 0 if cn.__dict__.get("_fused_conv_norm_train") else 1
+                cn._fused_conv_norm_train = "all" if all_shapes else "measured"
+    return n
+
+
 def use_linear_pointwise(net):
     """Inference-only plumbing: evaluate the (BN-folded) 1x1 convs of every channel mixer through the GEMM library
     (bias in the epilogue) instead of the conv library (bias as a separate kernel).  Returns the number replaced."""

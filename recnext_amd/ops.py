@@ -1042,3 +1042,7 @@ from .lsstem import pack_stem3, stem3, stem3_supported                          
 from .batchnorm import BatchNormFn, batch_norm_backward, batch_norm_frozen, batch_norm_routed, batch_norm_supported, batch_norm_train      # noqa: E402, F401
 # RepVGGDW of a training step as one operator (rcx_repdw_train_*): written in recnext_amd/repdw.py (guard-band cases in tests/test_repdw_gpu.py)
 from .repdw import RepDwFn, repdw_train, repdw_train_backward, repdw_train_routed, repdw_train_supported      # noqa: E402, F401
+
+# A depthwise ConvNorm of a training step as one operator (rcx_dwconv_bn_train_*): written in recnext_amd/dwbn.py (guard-band cases in
+# tests/test_conv_norm_gpu.py)
+from .dwbn import DwConvBnFn, dwconv_bn_train, dwconv_bn_train_backward, dwconv_bn_train_routed, dwconv_bn_train_supported      # noqa: E402, F401

@@ -82,18 +82,48 @@ def head_dim_supported(d):
 
 
 def _conv_norm_train(m, x, stride):
-    """ConvNorm in a training step: HIP depthwise conv (+ autograd), then the module's own BatchNorm (batch statistics)."""
+    """ConvNorm in a training step: HIP depthwise conv (+ autograd), then the module's own BatchNorm (batch statistics); or, for a module
+    models.use_fused_conv_norm_train marked, the two as one HIP operator (ops.DwConvBnFn) where _conv_norm_fused_ok holds."""
     if isinstance(m, nn.Conv2d):
         return _DwConvFn.apply(x, m.weight, m.bias, stride)
+    if m.__dict__.get("_fused_conv_norm_train") and _conv_norm_fused_ok(m, x, stride, None):
+        return _conv_norm_fused(m, x, None, stride)
     return m.norm(_DwConvFn.apply(x, m.conv.weight, m.conv.bias, stride))
 
 
 def _upadd_conv_norm_train(m, x, a, mode):
     """ConvNorm(x + interpolate(a, size(x), mode)) in a training step: resize, add and conv in one HIP launch with a HIP backward (rcx_upadd_dwconv_fwd / _bwd),
-    then the module's own BatchNorm (batch statistics)."""
+    then the module's own BatchNorm (batch statistics); or, for a marked module and mode "nearest", all of it as one HIP operator (ops.DwConvBnFn)."""
     if isinstance(m, nn.Conv2d):
         return _UpAddDwConvFn.apply(x, a, m.weight, m.bias, mode)
+    if m.__dict__.get("_fused_conv_norm_train") and mode == "nearest" and _conv_norm_fused_ok(m, x, 1, a):
+        return _conv_norm_fused(m, x, a, 1)
     return m.norm(_UpAddDwConvFn.apply(x, a, m.conv.weight, m.conv.bias, mode))
+
+
+def _conv_norm_fused_ok(m, x, stride, a):
+    """Whether a depthwise ConvNorm that models.use_fused_conv_norm_train marked runs this call on ops.DwConvBnFn (the conditions of that function's
+    docstring)."""
+    from .lsmodels import _norm_fusable
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in ops._DT):
+        return False
+    conv = m.conv
+    if conv.weight.dtype != torch.float32 or (conv.bias is not None and conv.bias.dtype != torch.float32) or not _norm_fusable(m.norm):
+        return False
+    n, c, h, w = x.shape
+    k = conv.weight.shape[-1]
+    if conv.groups != c or conv.weight.shape[0] != c or conv.weight.shape[-2] != k:
+        return False
+    if a is not None and not (torch.is_tensor(a) and a.is_cuda and a.dim() == 4 and a.dtype in ops._DT and a.shape[:2] == x.shape[:2]):
+        return False
+    return ops.dwconv_bn_train_supported(n, h, w, c, k, stride, a is not None, x.dtype, measured_only=m.__dict__["_fused_conv_norm_train"] != "all")
+
+
+def _conv_norm_fused(m, x, a, stride):
+    bn = m.norm
+    if bn.running_mean is not None and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return ops.DwConvBnFn.apply(ops._nhwc(x), a, m.conv.weight, m.conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, stride, bn.momentum, bn.eps)
 
 
 def _folded(m):
