@@ -604,6 +604,26 @@ int rcx_dwconv_bn_train_bwd(const void* x, const float* a, int Hc, int Wc, const
                             const float* invstd, void* gx, float* ga, float* gw, float* gb, float* ggamma, float* gbeta, void* workspace, size_t workspace_bytes,
                             int N, int H, int W, int C, int k, int stride, int dtype, void* stream);
 
+/*
+ * The classifier head behind the last block, global average pool + linear, in one launch without a workspace: model/recnext.py forward_head
+ * (x.mean((2, 3)), head_drop, head) with RecNextClassifier (two NormLinear heads averaged; one nn.Linear after fuse()) for the M / A families, and
+ * lsnet/model/recattn.py:266-293 (RecNextClassifier) with the forward_head of RecNext (:307-387) for T / S / B and their share-channel variants:
+ *     y[n][k] = bias[k] + sum_c w[k][c] * ((1 / (H W)) sum_p x[n][p][c])                n < N, k < K
+ * x: N x H x W x C, NHWC of `xdtype` (float32, bf16 or f16), aligned to 16 bytes.  y: N x K of `xdtype`, aligned to one element, rounded once, at its
+ * store.  wpack: the K x C weight, row-major as nn.Linear holds it, of `wdtype` = float32 or `xdtype`, aligned to 16 bytes; the kernel widens it
+ * exactly.  bias: float32 (K), aligned to 4 bytes, or NULL.  All arithmetic is float32: the pooled sum (8 pixel slices, 4 when C > 512, each a chain
+ * in pixel order, added as a fixed tree), the product with the float32 1 / (H W), the dot product (a lane's fmaf chain over its own 8 or 16
+ * channels, then a tree over the 64 lanes), the bias.  No 16-bit intermediate, no matrix-core operand, no atomics.  An output is one fixed expression
+ * of its image's pixels and its class's row: the same bits at any N, at any position in the batch and on every launch.
+ * rcx_global_pool_fwd is the pool alone (num_classes = 0, where the head is nn.Identity): y: N x C of `dtype`, the float32 mean rounded once.
+ * Supported (rcx_pool_head_supported: 1 / 0, without a GPU): C a multiple of 8 up to 1024, wdtype float32 or xdtype, any N, H, W, K >= 1 (for
+ * rcx_global_pool_fwd the same rule with K = 1); else RCX_ERR_UNSUPPORTED.  RCX_ERR_BAD_ARG for a NULL x / wpack / y, a non-positive extent, an
+ * unknown dtype, a misaligned pointer, a y that overlaps x, wpack or bias, or 2^31 or more elements in x, wpack or y.  All decided before any HIP call.
+ */
+int rcx_pool_head_supported(int N, int H, int W, int C, int K, int xdtype, int wdtype);
+int rcx_pool_head_fwd(const void* x, const void* wpack, const float* bias, void* y, int N, int H, int W, int C, int K, int xdtype, int wdtype, void* stream);
+int rcx_global_pool_fwd(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

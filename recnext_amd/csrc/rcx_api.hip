@@ -1687,3 +1687,59 @@ int rcx_dwconv_bn_train_bwd(const void* x, const float* a, int Hc, int Wc, const
 }
 
 }  // extern "C"
+
+namespace {
+
+bool ranges_overlap(const void* a, size_t ab, const void* b, size_t bb)
+{
+    const size_t a0 = (size_t)a, b0 = (size_t)b;
+    return a && b && a0 < b0 + bb && b0 < a0 + ab;
+}
+
+// the checks rcx_pool_head_fwd and rcx_global_pool_fwd share (w NULL and K = 1 for the pool alone): 0, or the refusal
+int check_head(const char* fn, const void* x, const void* w, const float* bias, const void* y, int N, int H, int W, int C, int K, int xdtype, int wdtype)
+{
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return fail(RCX_ERR_BAD_ARG, "%s: non-positive extent N=%d H=%d W=%d C=%d K=%d", fn, N, H, W, C, K);
+    if (!known_dtype(xdtype) || !known_dtype(wdtype)) return fail(RCX_ERR_BAD_ARG, "%s: unknown dtype %d / %d", fn, xdtype, wdtype);
+    const size_t es = xdtype == RCX_DTYPE_F32 ? 4 : 2, ws = wdtype == RCX_DTYPE_F32 ? 4 : 2;
+    if ((size_t)x % 16 || (size_t)w % 16 || (size_t)y % es || (size_t)bias % 4)
+        return fail(RCX_ERR_BAD_ARG, "%s: x and the weight must be aligned to 16 bytes, y to one element (%zu bytes), bias to 4", fn, es);
+    const unsigned long long lim = 1ull << 31, xe = (unsigned long long)N * H * W * C, we = (unsigned long long)K * C, ye = (unsigned long long)N * (w ? K : C);
+    if ((unsigned long long)H * W >= lim || xe >= lim || we >= lim || ye >= lim)
+        return fail(RCX_ERR_BAD_ARG, "%s: 2^31 or more elements (x %llu, the weight %llu, y %llu)", fn, xe, we, ye);
+    if (ranges_overlap(y, ye * es, x, xe * es) || ranges_overlap(y, ye * es, w, we * ws) || ranges_overlap(y, ye * es, bias, (size_t)K * 4))
+        return fail(RCX_ERR_BAD_ARG, "%s: y must overlap neither x nor the weight nor the bias", fn);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rcx_pool_head_supported(int N, int H, int W, int C, int K, int xdtype, int wdtype)
+{
+    return rcx::pool_head_applicable(N, H, W, C, K, xdtype, wdtype) ? 1 : 0;
+}
+
+int rcx_pool_head_fwd(const void* x, const void* wpack, const float* bias, void* y, int N, int H, int W, int C, int K, int xdtype, int wdtype, void* stream)
+{
+    const char* fn = "rcx_pool_head_fwd";
+    if (!x || !wpack || !y) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (int rc = check_head(fn, x, wpack, bias, y, N, H, W, C, K, xdtype, wdtype)) return rc;
+    if (!rcx::pool_head_applicable(N, H, W, C, K, xdtype, wdtype))
+        return fail(RCX_ERR_UNSUPPORTED, "%s: C=%d, xdtype=%d, wdtype=%d: C a multiple of 8 up to 1024, the weight float32 or of x's type", fn, C, xdtype, wdtype);
+    hipError_t e = rcx::pool_head_fwd(x, wpack, bias, y, N, H, W, C, K, xdtype, wdtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, fn);
+}
+
+int rcx_global_pool_fwd(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream)
+{
+    const char* fn = "rcx_global_pool_fwd";
+    if (!x || !y) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (int rc = check_head(fn, x, nullptr, nullptr, y, N, H, W, C, 1, dtype, dtype)) return rc;
+    if (!rcx::global_pool_applicable(N, H, W, C, dtype)) return fail(RCX_ERR_UNSUPPORTED, "%s: C=%d: C a multiple of 8 up to 1024", fn, C);
+    hipError_t e = rcx::global_pool_fwd(x, y, N, H, W, C, dtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, fn);
+}
+
+}  // extern "C"

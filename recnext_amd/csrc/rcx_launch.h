@@ -253,6 +253,11 @@ hipError_t dwconv_bn_train_fwd(const void* x, const float* a, int Hc, int Wc, co
 hipError_t dwconv_bn_train_bwd(const void* x, const float* a, int Hc, int Wc, const float* u, const void* gy, const float* w, const float* gamma, const float* mean_u,
                                const float* invstd_u, void* gx, float* ga, float* gw, float* gb, float* ggamma, float* gbeta, void* workspace, int N, int H, int W,
                                int C, int k, int stride, int dtype, hipStream_t s);
+// rcx_head.hip: the classifier head, global average pool + linear (the K x C weight row-major, float32 or x's type), one launch; and the pool alone
+bool pool_head_applicable(long long N, long long H, long long W, long long C, long long K, int xdtype, int wdtype);
+bool global_pool_applicable(long long N, long long H, long long W, long long C, int dtype);
+hipError_t pool_head_fwd(const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int C, int K, int xdtype, int wdtype, hipStream_t s);
+hipError_t global_pool_fwd(const void* x, void* y, int N, int H, int W, int C, int dtype, hipStream_t s);
 hipError_t recattn_qkcore(const float* d,const void* wqk_bf16, const float* bqk, const float* wpe, const float* bpe, float* out, void* workspace,
                           int B, int Hp, int Wp, int C, int heads, hipStream_t s);
 

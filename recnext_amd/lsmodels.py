@@ -442,6 +442,9 @@ class RecNext(nn.Module):
         return self.stages(self.stem(x))
 
     def forward_head(self, x):
+        fused = self.__dict__.get("_fused_head")
+        if fused is not None and fused.usable(self, x):
+            return fused(x)                             # global pool + linear as one launch (models.use_fused_head)
         if self.global_pool == "avg":
             x = x.mean((2, 3))
         return self.head(self.head_drop(x))

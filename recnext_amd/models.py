@@ -175,6 +175,9 @@ class RecNext(nn.Module):
         return self.stages(self.stem(x))
 
     def forward_head(self, x):
+        fused = self.__dict__.get("_fused_head")
+        if fused is not None and fused.usable(self, x):
+            return fused(x)                             # global pool + linear as one launch (models.use_fused_head)
         if self.global_pool == "avg":
             x = x.mean((2, 3))
         return self.head(self.head_drop(x))
@@ -376,6 +379,28 @@ def use_fused_stem(net):
             object.__setattr__(m, "_fused_stem", FusedStem3(seq[0], seq[2], seq[4], _is_exact_gelu(seq[5])))
             n += 1
     return n
+
+
+def use_fused_head(net, all_shapes=False):
+    """Inference-only: evaluate ``forward_head`` -- ``head(head_drop(x.mean((2, 3))))`` -- of a ``RecNext`` (this module's, ``lsmodels``' and the
+    share-channel models built on it) as ONE HIP launch (``ops.pool_head``, rcx_pool_head_fwd: float32 arithmetic, one rounding at the store) where the
+    call allows it, decided per call (``head.FusedHead.usable``): eval mode, ``global_pool == "avg"``, a dense channels_last GPU tensor of float32 /
+    bfloat16 / float16, no gradient wanted, ``net.head`` still the module it was here -- the ``nn.Linear`` ``replace_batchnorm`` leaves (its weight taken
+    as it lies), an eval-mode unfused ``RecNextClassifier`` (folded and averaged in float32 at pack time) or the ``nn.Identity`` of ``num_classes=0``
+    (``ops.global_pool``) -- and a shape the routing rule keeps (``head.pool_head_routed``; ``all_shapes`` routes every shape the kernel takes).
+    Everything else -- training, distillation in train mode, a CPU tensor, NCHW strides, a replaced head -- is the path as it was.  The call sets the
+    plain attribute ``_fused_head`` and nothing else: keys, Parameters and buffers are untouched.  Opt-in: nothing calls it by default.  Returns 1, or
+    0 when ``net`` is no such model or already has the helper for the head it has now (a helper for a head since replaced, by ``replace_batchnorm`` for one,
+    is renewed)."""
+    from . import lsmodels
+    from .head import FusedHead
+    if not isinstance(net, (RecNext, lsmodels.RecNext)):
+        return 0
+    have = net.__dict__.get("_fused_head")
+    if have is not None and have.head is net.head:
+        return 0
+    object.__setattr__(net, "_fused_head", FusedHead(net, all_shapes=all_shapes))
+    return 1
 
 
 def use_fused_mlp(net):

@@ -1046,3 +1046,6 @@ from .repdw import RepDwFn, repdw_train, repdw_train_backward, repdw_train_route
 # A depthwise ConvNorm of a training step as one operator (rcx_dwconv_bn_train_*): written in recnext_amd/dwbn.py (guard-band cases in
 # tests/test_conv_norm_gpu.py)
 from .dwbn import DwConvBnFn, dwconv_bn_train, dwconv_bn_train_backward, dwconv_bn_train_routed, dwconv_bn_train_supported      # noqa: E402, F401
+# The classifier head, global average pool + linear, as one launch (rcx_pool_head_fwd, rcx_global_pool_fwd): written in recnext_amd/head.py (guard-band
+# cases in tests/test_head_gpu.py)
+from .head import global_pool, pack_head, pool_head, pool_head_routed, pool_head_supported      # noqa: E402, F401

@@ -25,7 +25,7 @@ DTYPES = {"fp32": torch.float32, "f32": torch.float32, "bf16": torch.bfloat16, "
 
 
 def build_inference_model(name, device, dtype=torch.bfloat16, token_mixer=None, seed=0, fold_mixer_norm=True,
-                          hip_downsample=True, linear_pointwise=True, pad_hidden=True, fused_mlp=True, fused_stem=True):
+                          hip_downsample=True, linear_pointwise=True, pad_hidden=True, fused_mlp=True, fused_stem=True, fused_head=False):
     """create_model -> replace_batchnorm -> device/eval, as speed_gpu.py:47-50 (plus dtype + channels_last).
 
     ``fold_mixer_norm`` additionally absorbs the BatchNorm after each HIP token mixer into the mixer's last
@@ -34,7 +34,7 @@ def build_inference_model(name, device, dtype=torch.bfloat16, token_mixer=None, 
     channel mixers' GEMMs run at a zero-padded hidden width (``models.pad_mlp_hidden``: RecNeXt-A's 120 / 240 / 480 -> 128 / 256 / 512).
     ``fused_mlp`` (bf16): ``x + channel_mixer(.)`` of the blocks rcx_channel_mlp_fwd has a kernel for as one HIP launch (``models.use_fused_mlp``).
     ``fused_stem`` (bf16): the stem's convs and GELUs on the HIP kernels (``models.use_fused_stem``): M / A's two convs as one launch, T / S / B's three (the
-    share-channel models' too) as two.
+    share-channel models' too) as two.  ``fused_head`` (off by default): the global pool and the classifier as one HIP launch (``models.use_fused_head``).
     """
     torch.manual_seed(seed)
     net = models.create_model(name, num_classes=1000, token_mixer=token_mixer)
@@ -55,6 +55,8 @@ def build_inference_model(name, device, dtype=torch.bfloat16, token_mixer=None, 
                 models.use_fused_mlp(net)
         if fused_stem and dtype == torch.bfloat16:
             models.use_fused_stem(net)
+        if fused_head:
+            models.use_fused_head(net)
     return net
 
 
@@ -136,6 +138,8 @@ def main(argv=None):
     ap.add_argument("--graph", action="store_true", help="replay the forward as one HIP graph (small batches are bound by the host's launches)")
     ap.add_argument("--no-hip-downsample", action="store_true", help="keep the Downsample convs on the library (the comparison run)")
     ap.add_argument("--no-fused-stem", action="store_true", help="keep the stem's convs and GELUs on the library (the comparison run)")
+    ap.add_argument("--fused-head", action="store_true", help="run the global pool + classifier as one HIP launch (the comparison run; off by default)")
+    ap.add_argument("--fused-head-all-shapes", action="store_true", help="with --fused-head: every shape the kernel takes, not only those the routing rule keeps")
     ap.add_argument("--t0", default=T0, type=float)
     ap.add_argument("--t1", default=T1, type=float)
     args = ap.parse_args(argv)
@@ -149,7 +153,9 @@ def main(argv=None):
     ranks = rdist.init("cuda")
     device = str(ranks.device)
     dtype = DTYPES[args.dtype]
-    net = build_inference_model(args.model, device, dtype, hip_downsample=not args.no_hip_downsample, fused_stem=not args.no_fused_stem)
+    net = build_inference_model(args.model, device, dtype, hip_downsample=not args.no_hip_downsample, fused_stem=not args.no_fused_stem, fused_head=args.fused_head)
+    if args.fused_head and args.fused_head_all_shapes:
+        net._fused_head.all_shapes = True
     rdist.barrier(ranks)
     with torch.no_grad():                 # speed_gpu.py:40 switches autograd off for the whole process; scoped here
         rate = throughput(args.model, net, device, args.batch_size, args.resolution, dtype, args.t0, args.t1, ranks=ranks, graph=args.graph)
