@@ -605,6 +605,43 @@ int rcx_dwconv_bn_train_bwd(const void* x, const float* a, int Hc, int Wc, const
                             int N, int H, int W, int C, int k, int stride, int dtype, void* stream);
 
 /*
+ * The two BatchNorms of a channel mixer in the training step, each with what follows it as its epilogue: lsnet/model/recattn.py:199-205 (mlp:
+ * ConvNorm, GELU, ConvNorm), :240-251 and :254-263 (x + drop_path(channel_mixer(.))), :208-223 (the stem's ConvNorm -> GELU pairs), and
+ * model/recnext.py:125-131, :134-146, :149-158, :161-171 for the M / A families, as engine.py:38-71 runs them.  u, gu: N x H x W x C of `dtype` (float32,
+ * bf16 or f16), R = N H W rows of C contiguous channels, aligned to one element; weight, bias, every statistic and parameter gradient float32 (C),
+ * aligned to 4 bytes; all arithmetic float32; y = (u - save_mean) * save_invstd * weight + bias is never stored.
+ *   epilogue = RCX_BN_EPI_GELU   out = z = y Phi(y), Phi(y) = (1 + erf(y / sqrt 2)) / 2, the exact GELU on a float32 erf good to a few ulps (not the
+ *                                fit of rcx_channel_mlp_fwd); out and g = dL/dz of `dtype`; rdtype = dtype; r and scale are ignored.
+ *   epilogue = RCX_BN_EPI_ADD    out = r + scale[n] * y: the residual add behind the mixer with the DropPath mask; scale float32 (N) or NULL (= 1);
+ *                                r, out and g = dL/dout of `rdtype` = dtype or float32 (an autocast step's float32 residual); r may not overlap out.
+ *   rcx_bn_act_train_fwd   the statistics exactly as rcx_batchnorm_train_fwd forms and saves them (the same two launches; running_mean / running_var
+ *                          both or neither, in-out), then one apply launch; out is rounded once, at its store.
+ *   rcx_bn_act_train_bwd   d = g * (Phi(y) + y phi(y)), y formed again from u and the saved statistics (GELU; bias is read), or d = scale[n] * g (ADD;
+ *                          bias is ignored; dL/dr is g itself and has no kernel); with xhat = (u - mean) * invstd:
+ *                            gweight = sum_r d * xhat, gbias = sum_r d, gu = weight * invstd * (d - sum d / R - xhat * sum(d * xhat) / R)
+ *                          gu may be NULL, or the pair (gweight, gbias): not all three, and not one of the pair alone.  Three launches (sums of d,
+ *                          finalize, gu), two without gu; d is formed twice and never stored.  Outputs are overwritten.
+ * The reductions, both access paths (16 bytes where C is a multiple of 8 (16-bit) / 4 (float32) and every pointer read that wide is aligned to 16
+ * bytes, element-wide otherwise), the tiling and the workspace are rcx_batchnorm_*'s: no atomics, no waiting between workgroups, repeat launches
+ * bit-identical.  workspace: rcx_bn_act_workspace_bytes(...) bytes (0 for an unsupported problem), aligned to 4, for both entries.
+ * rcx_bn_act_supported: 1 / 0, a rule on (N H W, C, dtype, rdtype, epilogue) alone.
+ * RCX_ERR_BAD_ARG: a NULL required pointer (r with ADD, bias with the GELU's backward), one running pointer (or one of gweight / gbias) without the
+ * other, every output NULL, an unknown epilogue or dtype, a non-positive extent, R = 1, a misaligned pointer, an output or the workspace overlapping an
+ * input or each other; RCX_ERR_UNSUPPORTED: rdtype neither dtype nor (ADD) float32, 2^31 or more elements; RCX_ERR_WORKSPACE: a workspace smaller than
+ * the query.  All decided before any HIP call.
+ */
+#define RCX_BN_EPI_GELU 0
+#define RCX_BN_EPI_ADD 1
+int rcx_bn_act_supported(int N, int H, int W, int C, int dtype, int rdtype, int epilogue);
+size_t rcx_bn_act_workspace_bytes(int N, int H, int W, int C, int dtype, int rdtype, int epilogue);
+int rcx_bn_act_train_fwd(const void* u, const void* r, const float* scale, void* out, const float* weight, const float* bias, float* running_mean,
+                         float* running_var, float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes, int N, int H, int W, int C,
+                         float momentum, float eps, int epilogue, int dtype, int rdtype, void* stream);
+int rcx_bn_act_train_bwd(const void* u, const void* g, const float* scale, const float* weight, const float* bias, const float* mean, const float* invstd,
+                         void* gu, float* gweight, float* gbias, void* workspace, size_t workspace_bytes, int N, int H, int W, int C, int epilogue, int dtype,
+                         int rdtype, void* stream);
+
+/*
  * The classifier head behind the last block, global average pool + linear, in one launch without a workspace: model/recnext.py forward_head
  * (x.mean((2, 3)), head_drop, head) with RecNextClassifier (two NormLinear heads averaged; one nn.Linear after fuse()) for the M / A families, and
  * lsnet/model/recattn.py:266-293 (RecNextClassifier) with the forward_head of RecNext (:307-387) for T / S / B and their share-channel variants:

@@ -106,6 +106,10 @@ SIGNATURES = {
     "rcx_dwconv_bn_train_workspace_bytes": (_sz, [_i] * 8),
     "rcx_dwconv_bn_train_fwd": (_i, [_vp, _vp, _i, _i] + [_vp] * 11 + [_sz] + [_i] * 6 + [ctypes.c_float] * 2 + [_i, _vp]),
     "rcx_dwconv_bn_train_bwd": (_i, [_vp, _vp, _i, _i] + [_vp] * 13 + [_sz] + [_i] * 7 + [_vp]),
+    "rcx_bn_act_supported": (_i, [_i] * 7),
+    "rcx_bn_act_workspace_bytes": (_sz, [_i] * 7),
+    "rcx_bn_act_train_fwd": (_i, [_vp] * 11 + [_sz] + [_i] * 4 + [ctypes.c_float] * 2 + [_i] * 3 + [_vp]),
+    "rcx_bn_act_train_bwd": (_i, [_vp] * 11 + [_sz] + [_i] * 7 + [_vp]),
     "rcx_pool_head_supported": (_i, [_i] * 7),
     "rcx_pool_head_fwd": (_i, [_vp] * 4 + [_i] * 7 + [_vp]),
     "rcx_global_pool_fwd": (_i, [_vp] * 2 + [_i] * 5 + [_vp]),

@@ -1686,6 +1686,82 @@ int rcx_dwconv_bn_train_bwd(const void* x, const float* a, int Hc, int Wc, const
     return e == hipSuccess ? 0 : hip_fail(e, fn);
 }
 
+// A channel mixer's BatchNorm of a training step with its epilogue (rcx_bnact.hip): the exact GELU behind it, or the residual add with the DropPath scale.
+// What it takes is what the BatchNorm kernels take: fewer than 2^31 elements.
+int rcx_bn_act_supported(int N, int H, int W, int C, int dtype, int rdtype, int epilogue)
+{
+    return rcx::bn_act_applicable(N, H, W, C, dtype, rdtype, epilogue) ? 1 : 0;
+}
+
+size_t rcx_bn_act_workspace_bytes(int N, int H, int W, int C, int dtype, int rdtype, int epilogue)
+{
+    if (!rcx::bn_act_applicable(N, H, W, C, dtype, rdtype, epilogue)) return 0;
+    return rcx::bn_act_workspace_bytes(N * H * W, C, dtype);
+}
+
+namespace {
+// the checks the two entries share, ahead of check_bn: the epilogue, the residual's dtype, R = 1
+int check_bn_act(const char* fn, int N, int H, int W, int epilogue, int dtype, int rdtype)
+{
+    if (epilogue != RCX_BN_EPI_GELU && epilogue != RCX_BN_EPI_ADD) return fail(RCX_ERR_BAD_ARG, "%s: unknown epilogue %d", fn, epilogue);
+    if (!known_dtype(rdtype)) return fail(RCX_ERR_BAD_ARG, "%s: unknown dtype %d of the residual", fn, rdtype);
+    if (known_dtype(dtype) && rdtype != dtype && !(epilogue == RCX_BN_EPI_ADD && rdtype == RCX_DTYPE_F32))
+        return fail(RCX_ERR_UNSUPPORTED, "%s: rdtype %d with dtype %d (the residual is of u's type, or float32 with the ADD epilogue)", fn, rdtype, dtype);
+    if (N > 0 && H > 0 && W > 0 && (long long)N * H * W == 1)
+        return fail(RCX_ERR_BAD_ARG, "%s: batch statistics need more than one value per channel (N=%d H=%d W=%d)", fn, N, H, W);
+    return 0;
+}
+}  // namespace
+
+int rcx_bn_act_train_fwd(const void* u, const void* r, const float* scale, void* out, const float* weight, const float* bias, float* running_mean,
+                         float* running_var, float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes, int N, int H, int W, int C,
+                         float momentum, float eps, int epilogue, int dtype, int rdtype, void* stream)
+{
+    const char* fn = "rcx_bn_act_train_fwd";
+    const bool add = epilogue == RCX_BN_EPI_ADD;
+    if (!add) { r = nullptr; scale = nullptr; }                                    // used by ADD only
+    if (!u || !out || !weight || !bias || !save_mean || !save_invstd || (add && !r)) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (!running_mean != !running_var) return fail(RCX_ERR_BAD_ARG, "%s: running_mean and running_var come together or not at all", fn);
+    if (int rc = check_bn_act(fn, N, H, W, epilogue, dtype, rdtype)) return rc;
+    const bool res32 = rdtype != dtype;
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2, rs = rdtype == RCX_DTYPE_F32 ? 4 : 2, ne = (size_t)N * H * W * C, cb = (size_t)C * 4;
+    if (int rc = check_bn(fn, N, H, W, C, dtype, {u, res32 ? nullptr : r, res32 ? nullptr : out},
+                          {res32 ? r : nullptr, res32 ? out : nullptr, scale, weight, bias, running_mean, running_var, save_mean, save_invstd, workspace},
+                          {{u, ne * es}, {r, ne * rs}, {scale, (size_t)N * 4}, {weight, cb}, {bias, cb}},
+                          {{out, ne * rs}, {running_mean, cb}, {running_var, cb}, {save_mean, cb}, {save_invstd, cb}, {workspace, workspace_bytes}}))
+        return rc;
+    const size_t need = rcx::bn_act_workspace_bytes(N * H * W, C, dtype);
+    if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes, got %zu", fn, need, workspace ? workspace_bytes : (size_t)0);
+    hipError_t e = rcx::bn_act_train_fwd(u, r, scale, out, weight, bias, running_mean, running_var, save_mean, save_invstd, workspace, N * H * W, C, H * W, momentum,
+                                         eps, epilogue, dtype, rdtype, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, fn);
+}
+
+int rcx_bn_act_train_bwd(const void* u, const void* g, const float* scale, const float* weight, const float* bias, const float* mean, const float* invstd,
+                         void* gu, float* gweight, float* gbias, void* workspace, size_t workspace_bytes, int N, int H, int W, int C, int epilogue, int dtype,
+                         int rdtype, void* stream)
+{
+    const char* fn = "rcx_bn_act_train_bwd";
+    const bool add = epilogue == RCX_BN_EPI_ADD;
+    if (add) bias = nullptr;                                                       // the GELU's backward forms y again; ADD's does not
+    else scale = nullptr;
+    if (!u || !g || !weight || !mean || !invstd || (!add && !bias)) return fail(RCX_ERR_BAD_ARG, "%s: null pointer", fn);
+    if (!gu && !gweight && !gbias) return fail(RCX_ERR_BAD_ARG, "%s: null pointer for every output (gu, gweight and gbias)", fn);
+    if (!gweight != !gbias) return fail(RCX_ERR_BAD_ARG, "%s: gweight and gbias come together or not at all", fn);
+    if (int rc = check_bn_act(fn, N, H, W, epilogue, dtype, rdtype)) return rc;
+    const bool res32 = rdtype != dtype;
+    const size_t es = dtype == RCX_DTYPE_F32 ? 4 : 2, rs = rdtype == RCX_DTYPE_F32 ? 4 : 2, ne = (size_t)N * H * W * C, cb = (size_t)C * 4;
+    if (int rc = check_bn(fn, N, H, W, C, dtype, {u, res32 ? nullptr : g, gu}, {res32 ? g : nullptr, scale, weight, bias, mean, invstd, gweight, gbias, workspace},
+                          {{u, ne * es}, {g, ne * rs}, {scale, (size_t)N * 4}, {weight, cb}, {bias, cb}, {mean, cb}, {invstd, cb}},
+                          {{gu, ne * es}, {gweight, cb}, {gbias, cb}, {workspace, workspace_bytes}}))
+        return rc;
+    const size_t need = rcx::bn_act_workspace_bytes(N * H * W, C, dtype);
+    if (!workspace || workspace_bytes < need) return fail(RCX_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes, got %zu", fn, need, workspace ? workspace_bytes : (size_t)0);
+    hipError_t e = rcx::bn_act_train_bwd(u, g, scale, weight, bias, mean, invstd, gu, gweight, gbias, workspace, N * H * W, C, H * W, epilogue, dtype, rdtype,
+                                         (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, fn);
+}
+
 }  // extern "C"
 
 namespace {

@@ -137,5 +137,12 @@ inline dim3 block_of(const Plan& p) { return dim3((unsigned)p.TX, (unsigned)p.TY
         default: return hipErrorInvalidValue;                                                \
     }
 
+// rcx_bn.hip's own launches for the operators that put another apply behind them (rcx_bnact.hip): k_bn_stats + k_bn_finalize exactly as
+// batchnorm_train_fwd launches them (ws: batchnorm_workspace_bytes; `wide`: the caller's can_wide over every pointer it reads V-wide), and
+// k_bn_bwd_finalize over P partials of (sum d (C), sum d xhat (C))
+hipError_t launch_stats(const void* x, float* ws, float* save_mean, float* save_invstd, float* run_mean, float* run_var, int R, int C, float momentum, float eps,
+                        int dtype, bool wide, hipStream_t s);
+hipError_t launch_bwd_finalize(const float* ws, float* sums, float* gweight, float* gbias, int C, int P, hipStream_t s);
+
 }  // namespace bn
 }  // namespace rcx

@@ -284,16 +284,25 @@ __global__ void __launch_bounds__(kThreads) k_bn_bwd_dx(const T* __restrict__ x,
 }
 
 
+// the two statistics launches: k_bn_stats, k_bn_finalize (train_fwd's, and through launch_stats those of the operators that bring their own apply)
 template <typename T, int V>
-hipError_t train_fwd(const void* x, void* y, const float* weight, const float* bias, float* run_mean, float* run_var, float* save_mean, float* save_invstd,
-                     float* ws, int R, int C, float momentum, float eps, hipStream_t s)
+hipError_t stats_fwd(const void* x, float* ws, float* save_mean, float* save_invstd, float* run_mean, float* run_var, int R, int C, float momentum, float eps,
+                     hipStream_t s)
 {
-    const Plan ps = stats_plan(R, C, V), pa = apply_plan(R, C, V);
+    const Plan ps = stats_plan(R, C, V);
     hipLaunchKernelGGL((k_bn_stats<T, V>), grid_of(ps), block_of(ps), 0, s, (const T*)x, ws, R, C, ps.G, ps.RB, ps.P);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)((C + kFin - 1) / kFin)), dim3(kFin, kFin), 0, s, (const float*)ws, save_mean, save_invstd, run_mean, run_var,
                        R, C, ps.RB, ps.P, momentum, eps);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    return hipGetLastError();
+}
+
+template <typename T, int V>
+hipError_t train_fwd(const void* x, void* y, const float* weight, const float* bias, float* run_mean, float* run_var, float* save_mean, float* save_invstd,
+                     float* ws, int R, int C, float momentum, float eps, hipStream_t s)
+{
+    if (hipError_t e = stats_fwd<T, V>(x, ws, save_mean, save_invstd, run_mean, run_var, R, C, momentum, eps, s); e != hipSuccess) return e;
+    const Plan pa = apply_plan(R, C, V);
     hipLaunchKernelGGL((k_bn_apply<T, V, false>), grid_of(pa), block_of(pa), 0, s, (const T*)x, (T*)y, weight, bias, (const float*)save_mean,
                        (const float*)save_invstd, (float*)nullptr, R, C, pa.G, pa.RB, eps);
     return hipGetLastError();
@@ -335,6 +344,20 @@ hipError_t bwd(const void* x, const void* gy, const float* weight, const float* 
     return hipSuccess;
 }
 
+
+// stats_fwd for the operators that bring their own apply (rcx_bnact.hip)
+hipError_t launch_stats(const void* x, float* ws, float* save_mean, float* save_invstd, float* run_mean, float* run_var, int R, int C, float momentum, float eps,
+                        int dtype, bool wide, hipStream_t s)
+{
+    BN_DISPATCH(stats_fwd, dtype, wide, x, ws, save_mean, save_invstd, run_mean, run_var, R, C, momentum, eps, s)
+}
+
+// k_bn_bwd_finalize over the P partials another operator's reduction left in ws
+hipError_t launch_bwd_finalize(const float* ws, float* sums, float* gweight, float* gbias, int C, int P, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)((C + kFin - 1) / kFin)), dim3(kFin, kFin), 0, s, ws, sums, gweight, gbias, C, P);
+    return hipGetLastError();
+}
 
 }  // namespace bn
 

@@ -253,6 +253,15 @@ hipError_t dwconv_bn_train_fwd(const void* x, const float* a, int Hc, int Wc, co
 hipError_t dwconv_bn_train_bwd(const void* x, const float* a, int Hc, int Wc, const float* u, const void* gy, const float* w, const float* gamma, const float* mean_u,
                                const float* invstd_u, void* gx, float* ga, float* gw, float* gb, float* ggamma, float* gbeta, void* workspace, int N, int H, int W,
                                int C, int k, int stride, int dtype, hipStream_t s);
+// rcx_bnact.hip: the BatchNorm of a training step (batch statistics) with its epilogue, 0 = the exact GELU behind it, 1 = r + scale[n] * BN(u); r, out
+// and the backward's g of `rdtype` = dtype or float32 (epilogue 1 only); HW = rows an image
+bool bn_act_applicable(long long N, long long H, long long W, long long C, int dtype, int rdtype, int epilogue);
+size_t bn_act_workspace_bytes(int R, int C, int dtype);
+hipError_t bn_act_train_fwd(const void* u, const void* r, const float* scale, void* out, const float* weight, const float* bias, float* run_mean, float* run_var,
+                            float* save_mean, float* save_invstd, void* workspace, int R, int C, int HW, float momentum, float eps, int epilogue, int dtype,
+                            int rdtype, hipStream_t s);
+hipError_t bn_act_train_bwd(const void* u, const void* g, const float* scale, const float* weight, const float* bias, const float* mean, const float* invstd,
+                            void* gu, float* gweight, float* gbias, void* workspace, int R, int C, int HW, int epilogue, int dtype, int rdtype, hipStream_t s);
 // rcx_head.hip: the classifier head, global average pool + linear (the K x C weight row-major, float32 or x's type), one launch; and the pool alone
 bool pool_head_applicable(long long N, long long H, long long W, long long C, long long K, int xdtype, int wdtype);
 bool global_pool_applicable(long long N, long long H, long long W, long long C, int dtype);

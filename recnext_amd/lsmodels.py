@@ -26,6 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from . import bnact                 # after ops, which re-exports from it
 from .layers import ConvNorm as _ConvNorm
 from .layers import DropPath
 from .dwconv import DwConvFn
@@ -326,6 +327,10 @@ class MetaNeXtBlock(nn.Module):
         fused = self.__dict__.get("_fused_mlp")
         if fused is not None and not self.training and fused.usable(self.channel_mixer, t, r):
             return fused(t, r)                              # r + channel_mixer(t) in one launch (models.use_fused_mlp)
+        if bnact.ATTR in self.channel_mixer.__dict__:       # models.use_fused_mixer_norms_train: the two norms with their epilogues in a training forward
+            mode = bnact.mixer_ready(self.channel_mixer, t)
+            if mode is not None:
+                return bnact.run_mixer(self.channel_mixer, t, r, self.drop_path, mode)
         return r + self.drop_path(self.channel_mixer(t))
 
 
@@ -385,6 +390,10 @@ class Downsample(nn.Module):
         fused = self.__dict__.get("_fused_mlp")
         if fused is not None and not self.training and fused.usable(self.channel_mixer, x, x):
             return fused(x, x)
+        if bnact.ATTR in self.channel_mixer.__dict__:
+            mode = bnact.mixer_ready(self.channel_mixer, x)
+            if mode is not None:
+                return bnact.run_mixer(self.channel_mixer, x, x, self.drop_path, mode)
         return x + self.drop_path(self.channel_mixer(x))
 
 
@@ -399,6 +408,10 @@ class RecNextStem(nn.Module):
         fused = self.__dict__.get("_fused_stem")
         if fused is not None and not self.training and fused.usable(self.stem, x):
             return fused(x)                             # two launches (models.use_fused_stem)
+        if bnact.ATTR in self.__dict__:                 # models.use_fused_mixer_norms_train: ConvNorm -> GELU on BnGeluFn in a training forward
+            mode = bnact.stem_ready(self, x)
+            if mode is not None:
+                return bnact.run_stem(self.stem, x, mode)
         return self.stem(x)
 
 

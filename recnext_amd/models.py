@@ -12,6 +12,8 @@ restatement in the same skeleton; the default is always the HIP module.
 import torch
 import torch.nn as nn
 
+from . import ops
+from . import bnact                 # after ops, which re-exports from it
 from .layers import ConvNorm, DropPath, NormLinear
 from .recattn import RecAttn2d
 from .recconv import RecConv2d
@@ -55,6 +57,10 @@ class RecNextStem(nn.Module):
         fused = self.__dict__.get("_fused_stem")
         if fused is not None and not self.training and fused.usable(self.stem, x):
             return fused(x)                             # one launch (use_fused_stem)
+        if bnact.ATTR in self.__dict__:                 # use_fused_mixer_norms_train: ConvNorm -> GELU on BnGeluFn in a training forward
+            mode = bnact.stem_ready(self, x)
+            if mode is not None:
+                return bnact.run_stem(self.stem, x, mode)
         return self.stem(x)
 
 
@@ -77,6 +83,10 @@ class MetaNeXtBlock(nn.Module):
         fused = self.__dict__.get("_fused_mlp")
         if fused is not None and not self.training and fused.usable(self.channel_mixer, t, x):
             return fused(t, x)                          # x + channel_mixer(t) in one launch (use_fused_mlp)
+        if bnact.ATTR in self.channel_mixer.__dict__:   # use_fused_mixer_norms_train: the mixer's two norms with their epilogues in a training forward
+            mode = bnact.mixer_ready(self.channel_mixer, t)
+            if mode is not None:
+                return bnact.run_mixer(self.channel_mixer, t, x, self.drop_path, mode)
         return x + self.drop_path(self.channel_mixer(t))
 
 
@@ -111,6 +121,10 @@ class Downsample(nn.Module):
         fused = self.__dict__.get("_fused_mlp")
         if fused is not None and not self.training and fused.usable(self.channel_mixer, x, x):
             return fused(x, x)
+        if bnact.ATTR in self.channel_mixer.__dict__:
+            mode = bnact.mixer_ready(self.channel_mixer, x)
+            if mode is not None:
+                return bnact.run_mixer(self.channel_mixer, x, x, None, mode)
         return x + self.channel_mixer(x)
 
 
@@ -336,6 +350,31 @@ def use_fused_conv_norm_train(net, all_shapes=False):
             if isinstance(cn, ConvNorm):
                 n += 0 if cn.__dict__.get("_fused_conv_norm_train") else 1
                 cn._fused_conv_norm_train = "all" if all_shapes else "measured"
+    return n
+
+
+def use_fused_mixer_norms_train(net, all_shapes=False):
+    """Run the two BatchNorms of every channel mixer of ``net`` with what follows them as one HIP operator each in a training step: a marked mixer
+    ``[ConvNorm, GELU, ConvNorm]`` runs ``seq[0].conv(t) -> ops.BnGeluFn -> seq[2].conv(z) -> ops.BnAddFn(u2, r, mask)`` (``recnext_amd/bnact.py``):
+    ``GELU(BN(u1))`` without a stored ``BN(u1)``, and ``r + drop_path(BN(u2))`` with the DropPath mask drawn as ``DropPath.forward`` draws it (the same
+    random stream, the same values), three launches forward and three backward each in place of the BatchNorm, the GELU, the mask multiply and the add.
+    A marked stem runs each ``ConvNorm -> exact GELU`` pair on ``ops.BnGeluFn``; a ``ConvNorm`` followed by ``nn.Identity`` keeps the chain.  Marked:
+    the ``channel_mixer`` of every ``MetaNeXtBlock`` / ``Downsample`` of this module and of ``lsmodels`` (the share-channel models' blocks among them) and
+    both ``RecNextStem``s.  The call sets a plain attribute on the ``nn.Sequential`` (on the stem module) and nothing else: state_dict keys, Parameters,
+    buffers and module objects are untouched, strict loads work in either order.  A marked module takes the operators when the tensor is a GPU tensor
+    of float32 / bfloat16 / float16 with more than one value a channel, the mixer is still ``[ConvNorm, exact GELU, ConvNorm]`` with the very layers it
+    was marked with, each norm is exactly ``nn.BatchNorm2d`` or ``HipBatchNorm2d`` in training mode, affine with float32 parameters, float32 running
+    buffers (or none) and a float momentum, and -- norm by norm -- the shape is one the routing rule keeps (``bnact.bn_act_routed``; ``all_shapes``
+    routes every shape the kernels take); that norm's ``num_batches_tracked`` is then bumped by one.  Everything else -- eval mode, frozen norms,
+    SyncBatchNorm, ``momentum=None``, 16-bit parameters, the ``replace_batchnorm``ed form, the inference-only ``_fused_mlp`` path, CPU -- keeps the chain
+    unchanged.  Opt-in: nothing calls it by default.  Returns the number of modules newly marked (0 on a second call)."""
+    from . import lsmodels
+    n = 0
+    for m in net.modules():
+        if isinstance(m, _mlp_hosts()) and isinstance(m.channel_mixer, nn.Sequential):
+            n += bnact.mark(m.channel_mixer, m.channel_mixer, all_shapes)
+        elif isinstance(m, (RecNextStem, lsmodels.RecNextStem)) and isinstance(m.stem, nn.Sequential):
+            n += bnact.mark(m, m.stem, all_shapes)
     return n
 
 

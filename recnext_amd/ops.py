@@ -1049,3 +1049,6 @@ from .dwbn import DwConvBnFn, dwconv_bn_train, dwconv_bn_train_backward, dwconv_
 # The classifier head, global average pool + linear, as one launch (rcx_pool_head_fwd, rcx_global_pool_fwd): written in recnext_amd/head.py (guard-band
 # cases in tests/test_head_gpu.py)
 from .head import global_pool, pack_head, pool_head, pool_head_routed, pool_head_supported      # noqa: E402, F401
+# A channel mixer's BatchNorm + GELU and BatchNorm + residual of a training step (rcx_bn_act_*): written in recnext_amd/bnact.py (guard-band cases in
+# tests/test_bnact_gpu.py)
+from .bnact import BnAddFn, BnGeluFn, bn_act_routed, bn_act_supported, bn_add_train, bn_add_train_backward, bn_gelu_train, bn_gelu_train_backward      # noqa: E402, F401

@@ -21,6 +21,9 @@ ap.add_argument("--steps", type=int, default=8)
 ap.add_argument("--which", default="hip,aten")
 ap.add_argument("--graph", action="store_true", help="capture the whole step (forward, backward, AdamW) in one HIP graph and replay it: "
                 "the eager step is bound by the host's ~2000 launches below batch ~128")
+ap.add_argument("--fused-mixer-norms", action="store_true", help="run the channel mixers' BatchNorm + GELU and BatchNorm + residual as one HIP operator each "
+                "(models.use_fused_mixer_norms_train): the shapes its routing rule keeps")
+ap.add_argument("--fused-mixer-norms-all", action="store_true", help="... and every shape the kernels take, the rule set aside")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 for which in args.which.split(","):
@@ -30,6 +33,7 @@ for which in args.which.split(","):
     net = net.to(dev).to(memory_format=torch.channels_last).train()
     if which == "hip":
         models.use_hip_downsample(net)                         # Downsample depthwise conv: HIP forward + backward
+    fused_mn = models.use_fused_mixer_norms_train(net, all_shapes=args.fused_mixer_norms_all) if (args.fused_mixer_norms or args.fused_mixer_norms_all) else 0
     opt = torch.optim.AdamW(net.parameters(), lr=1e-3, capturable=args.graph)
     x = torch.randn(args.batch, 3, 224, 224, device=dev).contiguous(memory_format=torch.channels_last)
     y = torch.randint(0, 1000, (args.batch,), device=dev)
@@ -72,5 +76,5 @@ for which in args.which.split(","):
     e.record()
     torch.cuda.synchronize()
     ms = s.elapsed_time(e) / args.steps
-    print(json.dumps({"model": args.model, "token_mixers": which, "batch": args.batch, "hip_graph": bool(args.graph), "ms_per_step": round(ms, 2),
+    print(json.dumps({"model": args.model, "token_mixers": which, "batch": args.batch, "hip_graph": bool(args.graph), "fused_mixer_norms": fused_mn, "fused_mixer_norms_all": bool(args.fused_mixer_norms_all), "ms_per_step": round(ms, 2),
                       "images_per_s": round(args.batch / ms * 1e3, 1), "loss": round(float(loss), 4)}), flush=True)

@@ -5,7 +5,7 @@ instantiations for bf16 / float32 activations of the fused kernels (k_recconv_cp
 tiled step kernels (k_upadd_cpt, k_down5_cpt, k_down7m2_cpt), and every instantiation of the input adjoint (k_recconv_adj_cpl14,
 k_recconv_adj_cpl7), and RecAttn2d's wide-head attention kernels (k_recattn_short_w, k_recattn_kv_w, k_recattn_out_w: every instantiation), and the
 channel mixer's kernels (k_channel_mlp, k_channel_mlp_stream, k_channel_mlp_pair, k_channel_mlp_res128, k_channel_mlp_wide; the 320-channel stream kernel is reported only), and the
-backward of the T / S / B grouped Downsample conv (k_ls_down_gx, k_ls_down_gw: every instantiation), and the training step's BatchNorm (rcx_bn.hip's k_bn_*: every instantiation) and its one-operator RepVGGDW (rcx_repdw.hip's k_rep_*: every instantiation) and depthwise ConvNorm (rcx_dwbn.hip's k_dwbn_*: every instantiation), and the classifier head (rcx_head.hip's k_head_*: every instantiation); the
+backward of the T / S / B grouped Downsample conv (k_ls_down_gx, k_ls_down_gw: every instantiation), and the training step's BatchNorm (rcx_bn.hip's k_bn_*: every instantiation) and its one-operator RepVGGDW (rcx_repdw.hip's k_rep_*: every instantiation) and depthwise ConvNorm (rcx_dwbn.hip's k_dwbn_*: every instantiation) and the channel mixers' BatchNorm with its GELU or residual epilogue (rcx_bnact.hip's k_bnact_*: every instantiation), and the classifier head (rcx_head.hip's k_head_*: every instantiation); the
 training-forward and float16 instantiations and the other matrix-core attention kernels (rcx_qkcore's 32-wide and padded heads) are reported only.
 usage: check_scratch.py file.s [file.s ...]"""
 import re
@@ -75,6 +75,8 @@ for (path, r), name in zip(rows, names):
         gated = True                                       # RepVGGDW of a training step (rcx_repdw.hip): every instantiation, by the mangled name
     elif re.search(r"3rcx4dwbn\d+k_dwbn_", r["name"]):
         gated = True                                       # a depthwise ConvNorm of a training step (rcx_dwbn.hip): every instantiation, by the mangled name
+    elif re.search(r"3rcx5bnact\d+k_bnact_", r["name"]):
+        gated = True                                       # the channel mixers' BatchNorm + GELU / + residual of a training step (rcx_bnact.hip): every instantiation
     elif re.search(r"3rcx4head\d+k_head_", r["name"]):
         gated = True                                       # the classifier head (rcx_head.hip): every instantiation, by the mangled name
     elif re.match(r"mlp::k_channel_mlp(_pair|_stream|_res128|_wide)?<", short):
