@@ -4,17 +4,15 @@ the residual add behind the mixer with the optional per-sample DropPath scale.  
 (lsnet/model/recattn.py:199-205, :240-263; model/recnext.py:125-171) and the stems (:208-223; :134-146); ``run_mixer`` / ``run_stem`` below are what the
 marked modules' forwards call, and everything they do not route is the operator chain, unchanged to the bit.
 
-recnext_amd.ops exports the functions (``ops.bn_gelu_train`` ...); they are written here because tests/test_guard_cpu.py asks a row in the case table
-of tests/test_guard_bands_gpu.py of every launching function whose source is in ops.py, and these entries' guard-band cases are in
-tests/test_bnact_gpu.py, which passes this module to tests/guard.py as one of ``modules=`` (as recnext_amd/batchnorm.py does): outputs, statistics,
-gradients and the workspace are allocated by this module's own ``torch.empty``.  A CPU tensor raises."""
-import functools
-
+recnext_amd.ops exports the functions (``ops.bn_gelu_train`` ...); why they are written here is said once, in recnext_amd/_trainop.py; their
+guard-band cases are in tests/test_bnact_gpu.py.  A CPU tensor raises."""
 import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .batchnorm import _check_vec, _check_x, _dense_nhwc
+from ._trainop import (check_like, check_rows, check_running, check_vec, check_x, esize, gpu_tensor_ok, grad_in, grads_out, ptr, rows_routed, supported,
+                       workspace)
+from .batchnorm import bump, norm_fusable
 from .layers import ConvNorm, DropPath, _is_exact_gelu
 
 EPILOGUES = {"gelu": 0, "add": 1}                  # RCX_BN_EPI_GELU, RCX_BN_EPI_ADD
@@ -35,8 +33,7 @@ ROUTED = {(32, 2, "gelu"): (200704, 802816), (128, 2, "gelu"): (50176, 200704), 
 
 def bn_act_routed(n, h, w, c, dtype, epilogue):
     """Whether the routing rule keeps (N, H, W, C) of dtype with this epilogue on the operator: a rule on (R = N H W, C, element size, epilogue) alone."""
-    lo, hi = ROUTED.get((int(c), 4 if dtype == torch.float32 else 2, epilogue), (1, 0))
-    return lo <= int(n) * int(h) * int(w) <= hi
+    return rows_routed(ROUTED, (int(c), esize(dtype), epilogue), int(n) * int(h) * int(w))
 
 
 def bn_act_supported(n, h, w, c, dtype, epilogue, measured_only=False, rdtype=None):
@@ -46,45 +43,20 @@ def bn_act_supported(n, h, w, c, dtype, epilogue, measured_only=False, rdtype=No
     rdtype = dtype if rdtype is None else rdtype
     if dtype not in ops._DT or rdtype not in ops._DT or epilogue not in EPILOGUES:
         return False
-    if not _lib_supported(int(n), int(h), int(w), int(c), ops._DT[dtype], ops._DT[rdtype], EPILOGUES[epilogue]):
+    if not supported("rcx_bn_act_supported", n, h, w, c, ops._DT[dtype], ops._DT[rdtype], EPILOGUES[epilogue]):
         return False
     return not measured_only or bn_act_routed(n, h, w, c, dtype, epilogue)
 
 
-@functools.lru_cache(maxsize=1024)
-def _lib_supported(n, h, w, c, dt, rdt, epi):
-    """rcx_bn_act_supported, a rule on its arguments alone: asked of the library once a shape."""
-    return _lib.load().rcx_bn_act_supported(n, h, w, c, dt, rdt, epi) > 0
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _check_common(fn, u, vecs, epilogue, rdtype=None):
-    _check_x(fn, u, "u")
+    check_x(fn, u, "u")
     n, c, h, w = u.shape
     for name, t in vecs:
-        _check_vec(fn, t, c, u.device, name)
-    if n * h * w == 1:
-        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(u.shape)}")
+        check_vec(fn, t, c, u.device, name)
+    check_rows(n * h * w, tuple(u.shape))
     if not bn_act_supported(n, h, w, c, u.dtype, epilogue, rdtype=rdtype):
         raise ValueError(f"{fn}: no kernel for N={n}, H={h}, W={w}, C={c}, {u.dtype}" + (f" with a {rdtype} residual" if rdtype is not None else "")
                          + " (bn_act_supported)")
-
-
-def _check_like(fn, t, u, name, dtypes):
-    _check_x(fn, t, name)
-    if t.shape != u.shape or t.dtype not in dtypes or t.device != u.device:
-        raise ValueError(f"{fn}: {name} is {tuple(t.shape)} {t.dtype} on {t.device}, wanted {tuple(u.shape)} {' or '.join(map(str, dtypes))} on {u.device}")
-
-
-def _check_running(fn, u, running_mean, running_var):
-    if (running_mean is None) != (running_var is None):
-        raise ValueError(f"{fn}: running_mean and running_var come together or not at all")
-    if running_mean is not None:
-        _check_vec(fn, running_mean, u.shape[1], u.device, "running_mean")
-        _check_vec(fn, running_var, u.shape[1], u.device, "running_var")
 
 
 def _check_scale(fn, scale, u):
@@ -93,22 +65,16 @@ def _check_scale(fn, scale, u):
         raise ValueError(f"{fn}: scale must be a contiguous float32 ({u.shape[0]},) tensor on {u.device}, or None")
 
 
-def _workspace(u, rdtype, epilogue):
-    n, c, h, w = u.shape
-    nbytes = _lib.load().rcx_bn_act_workspace_bytes(n, h, w, c, ops._DT[u.dtype], ops._DT[rdtype], EPILOGUES[epilogue])
-    return torch.empty(nbytes, dtype=torch.uint8, device=u.device), nbytes
-
-
 def _forward(epilogue, u, r, scale, weight, bias, running_mean, running_var, momentum, eps):
     n, c, h, w = u.shape
     rdtype = u.dtype if r is None else r.dtype
-    out = torch.empty((n, h, w, c), dtype=rdtype, device=u.device).permute(0, 3, 1, 2)
+    out = ops._empty_nhwc(n, c, h, w, rdtype, u.device)
     mean = torch.empty(c, dtype=torch.float32, device=u.device)
     invstd = torch.empty(c, dtype=torch.float32, device=u.device)
-    ws, nbytes = _workspace(u, rdtype, epilogue)
+    ws, nbytes = workspace("rcx_bn_act_workspace_bytes", u.device, n, h, w, c, ops._DT[u.dtype], ops._DT[rdtype], EPILOGUES[epilogue])
     with ops._on(u.device):
-        rc = _lib.load().rcx_bn_act_train_fwd(u.data_ptr(), _ptr(r), _ptr(scale), out.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(running_mean),
-                                              _ptr(running_var), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), nbytes, n, h, w, c, float(momentum),
+        rc = _lib.load().rcx_bn_act_train_fwd(u.data_ptr(), ptr(r), ptr(scale), out.data_ptr(), weight.data_ptr(), bias.data_ptr(), ptr(running_mean),
+                                              ptr(running_var), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), nbytes, n, h, w, c, float(momentum),
                                               float(eps), EPILOGUES[epilogue], ops._dt(u), ops._DT[rdtype], ops._stream(u.device))
     _lib.check(rc, "rcx_bn_act_train_fwd")
     return out, mean, invstd
@@ -118,13 +84,13 @@ def _backward(fn, epilogue, u, g, scale, weight, bias, mean, invstd, need_input_
     if not (need_input_grad or need_param_grads):
         raise ValueError(f"{fn}: no gradient asked for")
     n, c, h, w = u.shape
-    gu = torch.empty((n, h, w, c), dtype=u.dtype, device=u.device).permute(0, 3, 1, 2) if need_input_grad else None
+    gu = ops._empty_nhwc(n, c, h, w, u.dtype, u.device) if need_input_grad else None
     gw = torch.empty(c, dtype=torch.float32, device=u.device) if need_param_grads else None
     gb = torch.empty(c, dtype=torch.float32, device=u.device) if need_param_grads else None
-    ws, nbytes = _workspace(u, g.dtype, epilogue)
+    ws, nbytes = workspace("rcx_bn_act_workspace_bytes", u.device, n, h, w, c, ops._DT[u.dtype], ops._DT[g.dtype], EPILOGUES[epilogue])
     with ops._on(u.device):
-        rc = _lib.load().rcx_bn_act_train_bwd(u.data_ptr(), g.data_ptr(), _ptr(scale), weight.data_ptr(), _ptr(bias), mean.data_ptr(), invstd.data_ptr(),
-                                              _ptr(gu), _ptr(gw), _ptr(gb), ws.data_ptr(), nbytes, n, h, w, c, EPILOGUES[epilogue], ops._dt(u),
+        rc = _lib.load().rcx_bn_act_train_bwd(u.data_ptr(), g.data_ptr(), ptr(scale), weight.data_ptr(), ptr(bias), mean.data_ptr(), invstd.data_ptr(),
+                                              ptr(gu), ptr(gw), ptr(gb), ws.data_ptr(), nbytes, n, h, w, c, EPILOGUES[epilogue], ops._dt(u),
                                               ops._DT[g.dtype], ops._stream(u.device))
     _lib.check(rc, "rcx_bn_act_train_bwd")
     return gu, gw, gb
@@ -136,7 +102,7 @@ def bn_gelu_train(u, weight, bias, running_mean=None, running_var=None, momentum
     running_mean / running_var (both or neither) are updated in place.  BN(u) is never stored."""
     fn = "bn_gelu_train"
     _check_common(fn, u, (("weight", weight), ("bias", bias)), "gelu")
-    _check_running(fn, u, running_mean, running_var)
+    check_running(fn, (running_mean, running_var), u.shape[1], u.device, ("running_mean", "running_var"))
     return _forward("gelu", u, None, None, weight, bias, running_mean, running_var, momentum, eps)
 
 
@@ -145,7 +111,7 @@ def bn_gelu_train_backward(u, gz, weight, bias, mean, invstd, need_input_grad=Tr
     -> (gu like u | None, gweight float32 (C) | None, gbias float32 (C) | None)."""
     fn = "bn_gelu_train_backward"
     _check_common(fn, u, (("weight", weight), ("bias", bias), ("mean", mean), ("invstd", invstd)), "gelu")
-    _check_like(fn, gz, u, "gz", (u.dtype,))
+    check_like(fn, gz, "gz", u.shape, (u.dtype,), u.device)
     return _backward(fn, "gelu", u, gz, None, weight, bias, mean, invstd, need_input_grad, need_param_grads)
 
 
@@ -153,10 +119,10 @@ def bn_add_train(u, r, weight, bias, scale=None, running_mean=None, running_var=
     """r + scale.view(N, 1, 1, 1) * F.batch_norm(u, ..., training=True) on dense channels_last u and r (rcx_bn_act_train_fwd, RCX_BN_EPI_ADD): r of u's
     dtype or float32 (an autocast step's residual); scale float32 (N) or None (= 1): the DropPath mask.  -> (out like r, save_mean, save_invstd)."""
     fn = "bn_add_train"
-    _check_x(fn, u, "u")
-    _check_like(fn, r, u, "r", (u.dtype, torch.float32))
+    check_x(fn, u, "u")
+    check_like(fn, r, "r", u.shape, (u.dtype, torch.float32), u.device)
     _check_common(fn, u, (("weight", weight), ("bias", bias)), "add", r.dtype)
-    _check_running(fn, u, running_mean, running_var)
+    check_running(fn, (running_mean, running_var), u.shape[1], u.device, ("running_mean", "running_var"))
     _check_scale(fn, scale, u)
     return _forward("add", u, r, scale, weight, bias, running_mean, running_var, momentum, eps)
 
@@ -165,17 +131,11 @@ def bn_add_train_backward(u, g, weight, mean, invstd, scale=None, need_input_gra
     """Backward of bn_add_train towards u and the norm's parameters (rcx_bn_act_train_bwd): g = dL/dout in out's dtype (u's or float32); the BatchNorm
     backward reads scale[n] g.  dL/dr is g itself and is not computed here.  -> (gu like u | None, gweight | None, gbias | None)."""
     fn = "bn_add_train_backward"
-    _check_x(fn, u, "u")
-    _check_like(fn, g, u, "g", (u.dtype, torch.float32))
+    check_x(fn, u, "u")
+    check_like(fn, g, "g", u.shape, (u.dtype, torch.float32), u.device)
     _check_common(fn, u, (("weight", weight), ("mean", mean), ("invstd", invstd)), "add", g.dtype)
     _check_scale(fn, scale, u)
     return _backward(fn, "add", u, g, scale, weight, None, mean, invstd, need_input_grad, need_param_grads)
-
-
-def _grad_like(g, dtype):
-    if g.dtype != dtype:
-        g = g.to(dtype)
-    return g if _dense_nhwc(g) else ops._nhwc(g, "g")
 
 
 class BnGeluFn(torch.autograd.Function):
@@ -196,9 +156,9 @@ class BnGeluFn(torch.autograd.Function):
         need_u, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         if not (need_u or need_p):
             return (None,) * 7
-        gu, gw, gb = bn_gelu_train_backward(u, _grad_like(gz, u.dtype), weight.detach(), bias.detach(), mean, invstd, need_input_grad=need_u,
+        gu, gw, gb = bn_gelu_train_backward(u, grad_in(gz, u.dtype), weight.detach(), bias.detach(), mean, invstd, need_input_grad=need_u,
                                             need_param_grads=need_p)
-        return (gu, gw.to(weight.dtype) if ctx.needs_input_grad[1] else None, gb.to(bias.dtype) if ctx.needs_input_grad[2] else None, None, None, None, None)
+        return (gu, *grads_out((gw, gb), (weight.dtype, bias.dtype), ctx.needs_input_grad[1:3]), None, None, None, None)
 
 
 class BnAddFn(torch.autograd.Function):
@@ -221,10 +181,9 @@ class BnAddFn(torch.autograd.Function):
         need_u, need_p = need[0], need[3] or need[4]
         gu = gw = gb = None
         if need_u or need_p:
-            gd = g if g.dtype in (u.dtype, torch.float32) else g.to(u.dtype)
-            gd = gd if _dense_nhwc(gd) else ops._nhwc(gd, "g")
+            gd = grad_in(g, g.dtype if g.dtype == torch.float32 else u.dtype)         # float32 (an autocast step's residual) is taken as it is
             gu, gw, gb = bn_add_train_backward(u, gd, weight.detach(), mean, invstd, scale, need_input_grad=need_u, need_param_grads=need_p)
-        return (gu, g if need[1] else None, None, gw.to(weight.dtype) if need[3] else None, gb.to(ctx.bias_dtype) if need[4] else None, None, None, None, None)
+        return (gu, g if need[1] else None, None, *grads_out((gw, gb), (weight.dtype, ctx.bias_dtype), need[3:5]), None, None, None, None)
 
 
 # ---- what a marked channel mixer / stem runs (models.use_fused_mixer_norms_train) ---------------------------------------------------------------------------
@@ -237,27 +196,20 @@ def mark(host, layers, all_shapes):
     return new
 
 
-def _norm_fusable(bn):
-    global _norm_fusable                                   # lsmodels imports this module: bound at the first call, then lsmodels' own function
-    from .lsmodels import _norm_fusable
-    return _norm_fusable(bn)
-
-
 def _hooked(*mods):
     """Whether a forward hook or pre-hook is registered on one of the modules themselves."""
     return any(m._forward_hooks or m._forward_pre_hooks for m in mods)
 
 
 def _conv_norm_ok(cn):
-    """A ConvNorm whose norm the operators reproduce (lsmodels._norm_fusable: exactly nn.BatchNorm2d or HipBatchNorm2d in training mode, affine float32
-    parameters, float32 running buffers or none, a float momentum); the replace_batchnorm'ed nn.Conv2d is not one."""
-    return isinstance(cn, ConvNorm) and isinstance(cn.conv, nn.Conv2d) and _norm_fusable(cn.norm)
+    """A ConvNorm whose norm the operators reproduce (batchnorm.norm_fusable); the replace_batchnorm'ed nn.Conv2d is not one."""
+    return isinstance(cn, ConvNorm) and isinstance(cn.conv, nn.Conv2d) and norm_fusable(cn.norm)
 
 
 def _marked(host, seq, x):
     """The mark's mode if `seq` is still the very layers `host` was marked with and x is a GPU tensor the kernels take, else None."""
     m = host.__dict__.get(ATTR)
-    if not m or not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in ops._DT):
+    if not m or not gpu_tensor_ok(x):
         return None
     if len(seq) != len(m) - 1 or any(a is not b for a, b in zip(seq, m[1:])):
         return None
@@ -267,7 +219,7 @@ def _marked(host, seq, x):
 def _routes(u, bn, epilogue, mode, rdtype=None):
     """Whether this norm's call runs on the operator: a 4-D GPU tensor of a dtype and shape the kernels take with more than one value a channel, the
     norm's tensors on its device, and a shape the routing rule keeps (every supported shape in mode "all")."""
-    if not (torch.is_tensor(u) and u.is_cuda and u.dim() == 4 and u.dtype in ops._DT and u.numel() > u.shape[1]):
+    if not (gpu_tensor_ok(u) and u.numel() > u.shape[1]):
         return False
     n, c, h, w = u.shape
     if c != bn.num_features or bn.weight.device != u.device:
@@ -275,15 +227,8 @@ def _routes(u, bn, epilogue, mode, rdtype=None):
     return bn_act_supported(n, h, w, c, u.dtype, epilogue, measured_only=mode != "all", rdtype=rdtype)
 
 
-def _bump(bn):
-    run = bn.running_mean is not None
-    if run and bn.num_batches_tracked is not None:
-        bn.num_batches_tracked.add_(1)
-    return (bn.running_mean, bn.running_var) if run else (None, None)
-
-
 def _bn_gelu(bn, u):
-    rm, rv = _bump(bn)
+    rm, rv = bump(bn)
     return BnGeluFn.apply(ops._nhwc(u, "u"), bn.weight, bn.bias, rm, rv, bn.momentum, bn.eps)
 
 
@@ -318,7 +263,7 @@ def run_mixer(seq, t, r, drop_path, mode):
     if not plain and drop_path.training and drop_path.drop_prob != 0.0:
         keep = 1.0 - drop_path.drop_prob
         scale = u2.new_empty((u2.shape[0], 1, 1, 1)).bernoulli_(keep).div_(keep).float().view(-1)
-    rm, rv = _bump(bn)
+    rm, rv = bump(bn)
     return BnAddFn.apply(ops._nhwc(u2, "u"), ops._nhwc(r, "r"), scale, bn.weight, bn.bias, rm, rv, bn.momentum, bn.eps)
 
 

@@ -4,14 +4,13 @@
 conv's float32 output u the saved activations (the count of the operator chain: x, a and the BatchNorm's input).  ``recattn._conv_norm_train`` and
 ``_upadd_conv_norm_train`` call ``DwConvBnFn`` for the modules ``models.use_fused_conv_norm_train`` marked; everything else keeps the operator chain.
 
-recnext_amd.ops exports the functions (``ops.dwconv_bn_train`` ...); they are written here because tests/test_guard_cpu.py asks a row in the case table
-of tests/test_guard_bands_gpu.py of every launching function whose source is in ops.py, and these entries' guard-band cases are in
-tests/test_conv_norm_gpu.py, which passes this module to tests/guard.py as one of ``modules=`` (as recnext_amd/repdw.py does): outputs, statistics,
-gradients and the workspace are allocated by this module's own ``torch.empty``.  A CPU tensor raises."""
+recnext_amd.ops exports the functions (``ops.dwconv_bn_train`` ...); why they are written here is said once, in recnext_amd/_trainop.py; their
+guard-band cases are in tests/test_conv_norm_gpu.py.  A CPU tensor raises."""
 import torch
 
 from . import _lib, ops
-from .batchnorm import _check_vec, _check_x, _dense_nhwc
+from ._trainop import (carve_f32, check_dw_weight, check_like, check_rows, check_running, check_vec, check_x, dense_nhwc, esize, grad_in, grads_out, ptr,
+                       rows_routed, supported, workspace)
 
 # The routing rule (DESIGN.md section 5.z3, profiles/r24_conv_norm_train.txt): (C, k, stride, has_coarse, element size of x) -> the output rows
 # R = N Ho Wo at which the operator's forward + backward beat the operator chain by more than the chain's own spread at batch 128, in wall and in GPU
@@ -25,17 +24,15 @@ ROUTED = {(32, 3, 1, False, 4): (12544, 50176), (64, 3, 1, False, 4): (3136, 501
 
 def dwconv_bn_train_routed(n, h, w, c, k, stride, has_coarse, dtype):
     """Whether the routing rule keeps the shape on the fused operator: a rule on (R = N Ho Wo, C, k, stride, has_coarse, element size) alone."""
-    lo, hi = ROUTED.get((int(c), int(k), int(stride), bool(has_coarse), 4 if dtype == torch.float32 else 2), (1, 0))
-    s = int(stride)
-    return lo <= int(n) * ((int(h) - 1) // s + 1) * ((int(w) - 1) // s + 1) <= hi
+    ho, wo = _out_hw(int(h), int(w), int(stride))
+    return rows_routed(ROUTED, (int(c), int(k), int(stride), bool(has_coarse), esize(dtype)), int(n) * ho * wo)
 
 
 def dwconv_bn_train_supported(n, h, w, c, k, stride, has_coarse, dtype, measured_only=False):
     """Whether the kernels take x of (N, H, W, C) and dtype with a k x k conv of this stride (rcx_dwconv_bn_train_supported: k 3 or 5, stride 1 or 2, the
     up-add form at stride 1, fewer than 2^31 elements; one output value a channel is refused by the functions, as torch refuses it) and, with
     measured_only, the routing rule keeps it (dwconv_bn_train_routed)."""
-    if dtype not in ops._DT or _lib.load().rcx_dwconv_bn_train_supported(int(n), int(h), int(w), int(c), int(k), int(stride), int(bool(has_coarse)),
-                                                                         ops._DT[dtype]) <= 0:
+    if dtype not in ops._DT or not supported("rcx_dwconv_bn_train_supported", n, h, w, c, k, stride, bool(has_coarse), ops._DT[dtype]):
         return False
     return not measured_only or dwconv_bn_train_routed(n, h, w, c, k, stride, has_coarse, dtype)
 
@@ -46,38 +43,24 @@ def _out_hw(h, w, stride):
 
 def _check(fn, x, w, a, stride, vecs):
     """-> (k, Ho, Wo, Hc, Wc) after the checks every entry shares."""
-    _check_x(fn, x)
+    check_x(fn, x)
     n, c, h, wd = x.shape
     for name, t in vecs:
         if t is not None:
-            _check_vec(fn, t, c, x.device, name)
-    if not torch.is_tensor(w) or w.dtype != torch.float32 or w.dim() != 4 or tuple(w.shape) != (c, 1, w.shape[-1], w.shape[-1]) or w.device != x.device \
-            or not w.is_contiguous():
-        raise ValueError(f"{fn}: w must be a contiguous float32 ({c}, 1, k, k) tensor on {x.device}")
-    k = w.shape[-1]
+            check_vec(fn, t, c, x.device, name)
+    k = check_dw_weight(fn, w, c, x.device, "w")
     hc = wc = 0
     if a is not None:
-        _check_x(fn, a, "a")
+        check_x(fn, a, "a")
         if a.dtype != torch.float32 or a.shape[0] != n or a.shape[1] != c or a.device != x.device:
             raise ValueError(f"{fn}: a is {tuple(a.shape)} {a.dtype} on {a.device}, wanted float32 ({n}, {c}, Hc, Wc) on {x.device}")
         hc, wc = a.shape[2], a.shape[3]
     ho, wo = _out_hw(h, wd, stride) if stride in (1, 2) else (0, 0)
-    if n * ho * wo == 1:
-        raise ValueError(f"Expected more than 1 value per channel when training, got input size {(n, c, ho, wo)}")
+    check_rows(n * ho * wo, (n, c, ho, wo))
     if not dwconv_bn_train_supported(n, h, wd, c, k, stride, a is not None, x.dtype):
         raise ValueError(f"{fn}: no kernel for N={n}, H={h}, W={wd}, C={c}, k={k}, stride={stride}, {'up-add, ' if a is not None else ''}{x.dtype} "
                          "(dwconv_bn_train_supported)")
     return k, ho, wo, hc, wc
-
-
-def _workspace(x, k, stride, has_coarse):
-    n, c, h, w = x.shape
-    nbytes = _lib.load().rcx_dwconv_bn_train_workspace_bytes(n, h, w, c, k, stride, int(has_coarse), ops._DT[x.dtype])
-    return torch.empty(nbytes, dtype=torch.uint8, device=x.device), nbytes
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
 
 
 def dwconv_bn_train(x, w, b, gamma, beta, a=None, stride=1, running=None, momentum=0.1, eps=1e-5):
@@ -88,19 +71,14 @@ def dwconv_bn_train(x, w, b, gamma, beta, a=None, stride=1, running=None, moment
     fn = "dwconv_bn_train"
     k, ho, wo, hc, wc = _check(fn, x, w, a, stride, (("b", b), ("gamma", gamma), ("beta", beta)))
     n, c, h, wd = x.shape
-    if running is not None:
-        if len(running) != 2:
-            raise ValueError(f"{fn}: running is the two buffers (running_mean, running_var) or None")
-        for i, t in enumerate(running):
-            _check_vec(fn, t, c, x.device, f"running[{i}]")
-    y = torch.empty((n, ho, wo, c), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)
-    u = torch.empty((n, ho, wo, c), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2)
+    run = check_running(fn, running, c, x.device, ("running_mean", "running_var"))
+    y = ops._empty_nhwc(n, c, ho, wo, x.dtype, x.device)
+    u = ops._empty_nhwc(n, c, ho, wo, torch.float32, x.device)
     stats = torch.empty((2, c), dtype=torch.float32, device=x.device)
-    ws, nbytes = _workspace(x, k, stride, a is not None)
-    run = [t.data_ptr() for t in running] if running is not None else [None, None]
+    ws, nbytes = workspace("rcx_dwconv_bn_train_workspace_bytes", x.device, n, h, wd, c, k, stride, int(a is not None), ops._DT[x.dtype])
     sp = stats.data_ptr()
     with ops._on(x.device):
-        rc = _lib.load().rcx_dwconv_bn_train_fwd(x.data_ptr(), _ptr(a), hc, wc, w.data_ptr(), _ptr(b), gamma.data_ptr(), beta.data_ptr(), run[0], run[1],
+        rc = _lib.load().rcx_dwconv_bn_train_fwd(x.data_ptr(), ptr(a), hc, wc, w.data_ptr(), ptr(b), gamma.data_ptr(), beta.data_ptr(), run[0], run[1],
                                                  y.data_ptr(), u.data_ptr(), sp, sp + 4 * c, ws.data_ptr(), nbytes, n, h, wd, c, k, int(stride),
                                                  float(momentum), float(eps), ops._dt(x), ops._stream(x.device))
     _lib.check(rc, "rcx_dwconv_bn_train_fwd")
@@ -120,28 +98,23 @@ def dwconv_bn_train_backward(x, g, w, gamma, stats, u, a=None, stride=1, need_in
     need_coarse_grad = (a is not None) if need_coarse_grad is None else bool(need_coarse_grad)
     if need_coarse_grad and a is None:
         raise ValueError(f"{fn}: need_coarse_grad without a")
-    _check_x(fn, g, "g")
-    if tuple(g.shape) != (n, c, ho, wo) or g.dtype != x.dtype or g.device != x.device:
-        raise ValueError(f"{fn}: g is {tuple(g.shape)} {g.dtype} on {g.device}, wanted {x.dtype} {(n, c, ho, wo)} on {x.device}")
-    if not torch.is_tensor(u) or u.dim() != 4 or tuple(u.shape) != (n, c, ho, wo) or u.dtype != torch.float32 or u.device != x.device or not _dense_nhwc(u):
+    check_like(fn, g, "g", (n, c, ho, wo), (x.dtype,), x.device)
+    if not torch.is_tensor(u) or u.dim() != 4 or tuple(u.shape) != (n, c, ho, wo) or u.dtype != torch.float32 or u.device != x.device or not dense_nhwc(u):
         raise ValueError(f"{fn}: u must be the dense channels_last float32 {(n, c, ho, wo)} tensor dwconv_bn_train returned")
     if not torch.is_tensor(stats) or stats.dtype != torch.float32 or tuple(stats.shape) != (2, c) or stats.device != x.device or not stats.is_contiguous():
         raise ValueError(f"{fn}: stats must be the contiguous float32 (2, {c}) tensor dwconv_bn_train returned")
     if not (need_input_grad or need_coarse_grad or need_param_grads):
         raise ValueError(f"{fn}: no gradient asked for")
-    gx = torch.empty((n, h, wd, c), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2) if need_input_grad else None
-    ga = torch.empty((n, hc, wc, c), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2) if need_coarse_grad else None
+    gx = ops._empty_nhwc(n, c, h, wd, x.dtype, x.device) if need_input_grad else None
+    ga = ops._empty_nhwc(n, c, hc, wc, torch.float32, x.device) if need_coarse_grad else None
     grads, gp = None, [None] * 4
     if need_param_grads:
-        kk = k * k
-        buf = torch.empty((kk + 3) * c, dtype=torch.float32, device=x.device)
-        grads = (buf[:kk * c].view(c, 1, k, k),) + tuple(buf[(kk + i) * c:(kk + 1 + i) * c] for i in range(3))
-        gp = [buf.data_ptr()] + [buf.data_ptr() + 4 * (kk + i) * c for i in range(3)]
-    ws, nbytes = _workspace(x, k, stride, a is not None)
+        grads, gp = carve_f32([(c, 1, k, k)] + [(c,)] * 3, x.device)                  # GRADS: (k k + 3) C floats, one allocation
+    ws, nbytes = workspace("rcx_dwconv_bn_train_workspace_bytes", x.device, n, h, wd, c, k, stride, int(a is not None), ops._DT[x.dtype])
     sp = stats.data_ptr()
     with ops._on(x.device):
-        rc = _lib.load().rcx_dwconv_bn_train_bwd(x.data_ptr(), _ptr(a), hc, wc, u.data_ptr(), g.data_ptr(), w.data_ptr(), gamma.data_ptr(), sp, sp + 4 * c,
-                                                 _ptr(gx), _ptr(ga), *gp, ws.data_ptr(), nbytes, n, h, wd, c, k, int(stride), ops._dt(x), ops._stream(x.device))
+        rc = _lib.load().rcx_dwconv_bn_train_bwd(x.data_ptr(), ptr(a), hc, wc, u.data_ptr(), g.data_ptr(), w.data_ptr(), gamma.data_ptr(), sp, sp + 4 * c,
+                                                 ptr(gx), ptr(ga), *gp, ws.data_ptr(), nbytes, n, h, wd, c, k, int(stride), ops._dt(x), ops._stream(x.device))
     _lib.check(rc, "rcx_dwconv_bn_train_bwd")
     return gx, ga, grads
 
@@ -169,18 +142,8 @@ class DwConvBnFn(torch.autograd.Function):
         need_x, need_a, need_p = need[0], a32 is not None and need[1], any(need[2:6])
         if not (need_x or need_a or need_p):
             return (None,) * 11
-        if g.dtype != x.dtype:
-            g = g.to(x.dtype)
-        if not _dense_nhwc(g):
-            g = ops._nhwc(g, "g")
-        gx, ga, grads = dwconv_bn_train_backward(x, g, w, gamma, stats, u, a32, ctx.stride, need_input_grad=need_x, need_coarse_grad=need_a,
+        gx, ga, grads = dwconv_bn_train_backward(x, grad_in(g, x.dtype), w, gamma, stats, u, a32, ctx.stride, need_input_grad=need_x, need_coarse_grad=need_a,
                                                  need_param_grads=need_p)
         if ga is not None and ga.dtype != ctx.adtype:
             ga = ga.to(ctx.adtype)
-        out = [gx, ga] + [None] * 9
-        if grads is not None:
-            dts = (w.dtype, ctx.bdtype, gamma.dtype, ctx.betadtype)
-            for i, t in enumerate(grads):
-                if need[2 + i] and dts[i] is not None:
-                    out[2 + i] = t if dts[i] == torch.float32 else t.to(dts[i])
-        return tuple(out)
+        return (gx, ga, *grads_out(grads, (w.dtype, ctx.bdtype, gamma.dtype, ctx.betadtype), need[2:6]), *(None,) * 5)

@@ -10,6 +10,7 @@ this module's own ``torch.empty``.  A CPU tensor raises; there is no fallback.""
 import torch
 
 from . import _lib, ops
+from ._trainop import esize, ptr, rows_routed
 
 # The routing rule (profiles/r25_head.txt): (C, H W, element size of x) -> the batch sizes N from the smallest to the largest at
 # which the launch beat the library chain (mean + F.linear) by more than the chain's own spread in that job, both from Python (device events around
@@ -22,8 +23,7 @@ ROUTED = {(320, 49, 2): (1, 64), (512, 49, 2): (1, 64), (512, 16, 2): (1, 64)}
 
 def pool_head_routed(n, h, w, c, k, dtype):
     """Whether the routing rule keeps the shape on the HIP head: a rule on (N, H W, C, element size) alone."""
-    lo, hi = ROUTED.get((int(c), int(h) * int(w), 4 if dtype == torch.float32 else 2), (1, 0))
-    return lo <= int(n) <= hi
+    return rows_routed(ROUTED, (int(c), int(h) * int(w), esize(dtype)), int(n))          # this table's bounds are batch sizes
 
 
 def pool_head_supported(n, h, w, c, k, dtype, wdtype=None, measured_only=False):
@@ -138,7 +138,7 @@ def pool_head(x, wpack, bias, k):
         raise _lib.RcxError(f"pool_head: no kernel for N={n}, H={h}, W={w}, C={c}, K={k}, {x.dtype} with a {wpack.dtype} weight (pool_head_supported)")
     y = torch.empty((n, k), dtype=x.dtype, device=x.device)
     with ops._on(x.device):
-        rc = _lib.load().rcx_pool_head_fwd(x.data_ptr(), wpack.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(), n, h, w, c, k,
+        rc = _lib.load().rcx_pool_head_fwd(x.data_ptr(), wpack.data_ptr(), ptr(bias), y.data_ptr(), n, h, w, c, k,
                                            ops._dt(x), ops._DT[wpack.dtype], ops._stream(x.device))
     _lib.check(rc, "rcx_pool_head_fwd")
     return y

@@ -11,6 +11,7 @@ this module to tests/guard.py as one of ``modules=``."""
 import torch
 
 from . import _lib, ops
+from ._trainop import ptr
 
 
 def grouped_conv2d_supported(n, h, w, cin, cout, groups, k, stride, dtype):
@@ -50,7 +51,7 @@ def grouped_conv2d(x, wpack, bias, groups, k=5, stride=2):
     x = ops._nhwc(x, "x")
     y = ops._empty_nhwc(n, cout, (h + 1) // 2, (w + 1) // 2, x.dtype, x.device)
     with ops._on(x.device):
-        rc = _lib.load().rcx_grouped_conv2d_fwd(x.data_ptr(), y.data_ptr(), wpack.data_ptr(), bias.data_ptr() if bias is not None else None,
+        rc = _lib.load().rcx_grouped_conv2d_fwd(x.data_ptr(), y.data_ptr(), wpack.data_ptr(), ptr(bias),
                                                 n, h, w, cin, cout, groups, k, stride, ops._dt(x), ops._stream(x.device))
     _lib.check(rc, "rcx_grouped_conv2d_fwd")
     return y
@@ -96,7 +97,6 @@ def grouped_conv2d_backward(x, gy, wpack, groups, need_input_grad=True, need_wei
     if gw is not None or gb is not None:
         nbytes = lib.rcx_grouped_conv2d_bwd_workspace_bytes(n, h, w, cin, cout, groups, k, stride, ops._DT[x.dtype])
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
     with ops._on(x.device):
         rc = lib.rcx_grouped_conv2d_bwd(x.data_ptr(), gy.data_ptr(), wpack.data_ptr(), ptr(gx), ptr(gw), ptr(gb), ptr(ws), nbytes,
                                         n, h, w, cin, cout, groups, k, stride, ops._dt(x), ops._stream(x.device))

@@ -27,6 +27,8 @@ import torch.nn.functional as F
 
 from . import ops
 from . import bnact                 # after ops, which re-exports from it
+from ._trainop import gpu_tensor_ok
+from .batchnorm import bump, norm_fusable
 from .layers import ConvNorm as _ConvNorm
 from .layers import DropPath
 from .dwconv import DwConvFn
@@ -97,27 +99,15 @@ def _rep_train(m, x):
     return lk + y + x
 
 
-def _norm_fusable(bn):
-    """A BatchNorm the fused RepVGGDW operator reproduces: exactly nn.BatchNorm2d or HipBatchNorm2d, training, affine with float32 parameters, float32
-    running buffers or none, a float momentum."""
-    from .batchnorm import HipBatchNorm2d
-    if type(bn) not in (nn.BatchNorm2d, HipBatchNorm2d) or not bn.training or not isinstance(bn.momentum, float):
-        return False
-    if bn.weight is None or bn.bias is None or bn.weight.dtype != torch.float32 or bn.bias.dtype != torch.float32:
-        return False
-    rm, rv = bn.running_mean, bn.running_var
-    return (rm is None and rv is None) or (rm is not None and rv is not None and rm.dtype == torch.float32 and rv.dtype == torch.float32)
-
-
 def _rep_fused_ok(m, x):
     """Whether a RepVGGDW that models.use_fused_rep_train marked runs this call on ops.RepDwFn (the conditions of that function's docstring)."""
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in ops._DT and x.numel() > x.shape[1]):
+    if not (gpu_tensor_ok(x) and x.numel() > x.shape[1]):
         return False
     if not isinstance(m, RepVGGDW) or isinstance(m.lk, nn.Conv2d) or isinstance(m.sk, nn.Conv2d):
         return False
     for cn in (m.lk, m.sk):
         conv = cn.conv
-        if conv.bias is None or conv.weight.dtype != torch.float32 or conv.bias.dtype != torch.float32 or not _norm_fusable(cn.norm):
+        if conv.bias is None or conv.weight.dtype != torch.float32 or conv.bias.dtype != torch.float32 or not norm_fusable(cn.norm):
             return False
     if (m.lk.norm.running_mean is None) != (m.sk.norm.running_mean is None):
         return False
@@ -127,11 +117,8 @@ def _rep_fused_ok(m, x):
 
 def _rep_fused(m, x):
     na, nb = m.lk.norm, m.sk.norm
-    for bn in (na, nb):
-        if bn.running_mean is not None and bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
     return ops.RepDwFn.apply(ops._nhwc(x), m.lk.conv.weight, m.lk.conv.bias, na.weight, na.bias, m.sk.conv.weight, m.sk.conv.bias, nb.weight, nb.bias,
-                             na.running_mean, na.running_var, nb.running_mean, nb.running_var, na.momentum, na.eps, nb.momentum, nb.eps)
+                             *bump(na), *bump(nb), na.momentum, na.eps, nb.momentum, nb.eps)
 
 
 def _rep_params(m):

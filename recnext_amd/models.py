@@ -303,23 +303,29 @@ def use_hip_batchnorm(net, all_shapes=False):
     return n
 
 
+def _mark(module, attr, all_shapes):
+    """Mark `module` for one of the ``use_fused_*_train`` operators: the plain attribute `attr` = "all" | "measured".  -> 1 if newly marked, else 0.
+
+    What the three calls share.  The mark is a plain attribute and nothing else: state_dict keys, Parameters, buffers and module objects are
+    untouched, strict loads work in either order.  A marked module takes its operator in a call when the tensor is a GPU tensor of float32 /
+    bfloat16 / float16 with more than one (output) value a channel, every norm it takes over is exactly ``nn.BatchNorm2d`` or ``HipBatchNorm2d`` in
+    training mode, affine with float32 parameters, float32 running buffers (or none) and a float momentum (``batchnorm.norm_fusable``), and the
+    shape is one the operator's routing rule keeps (``all_shapes`` routes every shape the kernels take); each such norm's ``num_batches_tracked`` is
+    then bumped by one (``batchnorm.bump``).  Everything else -- eval-mode or frozen norms, SyncBatchNorm, ``momentum=None``, 16-bit parameters, a
+    folded ``nn.Conv2d``, CPU -- keeps the operator chain, unchanged.  Opt-in: nothing calls them by default; each returns the number of modules
+    newly marked (0 on a second call)."""
+    new = 0 if module.__dict__.get(attr) else 1
+    setattr(module, attr, "all" if all_shapes else "measured")
+    return new
+
+
 def use_fused_rep_train(net, all_shapes=False):
     """Run every unfused ``RepVGGDW`` of ``net`` (the T / S / B models of ``lsmodels`` and the share-channel models of ``lsshare``) as one HIP operator
     in a training step: ``ops.RepDwFn`` (``recnext_amd/repdw.py``), three launches forward and at most four backward in place of the operator chain of
-    ``lsmodels._rep_train``.  The call sets a plain attribute on the module and nothing else: state_dict keys, Parameters, buffers and module objects
-    are untouched, strict loads work in either order.  A marked module takes the operator when the tensor is a GPU tensor of float32 / bfloat16 /
-    float16 with more than one value a channel, both convs have float32 weights and biases, both norms are exactly ``nn.BatchNorm2d`` or
-    ``HipBatchNorm2d`` in training mode, affine with float32 parameters, float32 running buffers (or none) and a float momentum, and the shape is one
-    the routing rule keeps (``repdw.repdw_train_routed``; ``all_shapes`` routes every shape the kernels take); both ``num_batches_tracked`` are then
-    bumped by one.  Everything else -- eval-mode or frozen norms, SyncBatchNorm, ``momentum=None``, 16-bit parameters, the fused ``nn.Conv2d`` form,
-    CPU -- keeps the chain unchanged.  Opt-in: nothing calls it by default.  Returns the number of modules newly marked (0 on a second call)."""
+    ``lsmodels._rep_train``.  The mark, what a marked module asks of a call and what keeps the chain: ``_mark``.  Particular to this one: both convs
+    have float32 weights and biases, both norms have running buffers or neither has, and the rule is ``repdw.repdw_train_routed``."""
     from . import lsmodels
-    n = 0
-    for m in net.modules():
-        if isinstance(m, lsmodels.RepVGGDW):
-            n += 0 if m.__dict__.get("_fused_rep_train") else 1
-            m._fused_rep_train = "all" if all_shapes else "measured"
-    return n
+    return sum(_mark(m, "_fused_rep_train", all_shapes) for m in net.modules() if isinstance(m, lsmodels.RepVGGDW))
 
 
 def use_fused_conv_norm_train(net, all_shapes=False):
@@ -327,14 +333,9 @@ def use_fused_conv_norm_train(net, all_shapes=False):
     ``RecAttn2d`` (the M / A families) and ``LsRecAttn2d`` (T / S / B) and ``pe`` of every ``LinearAttention3`` -- the modules
     ``recattn._conv_norm_train`` / ``_upadd_conv_norm_train`` are called with by the mixers -- run ``ops.DwConvBnFn`` (``recnext_amd/dwbn.py``), three
     launches forward and at most five backward in place of the conv's Function followed by the module's BatchNorm.  (``RepVGGDW.lk`` has its own
-    operator: ``use_fused_rep_train``.)  The call sets a plain attribute on the module and nothing else: state_dict keys, Parameters, buffers and
-    module objects are untouched, strict loads work in either order.  A marked module takes the operator when the tensor is a GPU tensor of float32 /
-    bfloat16 / float16 with more than one output value a channel, the conv's weight (and bias, if it has one) is float32, the norm is exactly
-    ``nn.BatchNorm2d`` or ``HipBatchNorm2d`` in training mode, affine with float32 parameters, float32 running buffers (or none) and a float momentum,
-    the resize mode is ``"nearest"`` (the up-add form) and the shape is one the routing rule keeps (``dwbn.dwconv_bn_train_routed``; ``all_shapes``
-    routes every shape the kernels take); ``num_batches_tracked`` is then bumped by one.  Everything else -- eval-mode or frozen norms, SyncBatchNorm,
-    ``momentum=None``, 16-bit parameters, the folded ``nn.Conv2d`` form, bilinear mode, CPU -- keeps the chain unchanged.  Opt-in: nothing calls it by
-    default.  Returns the number of modules newly marked (0 on a second call)."""
+    operator: ``use_fused_rep_train``.)  The mark, what a marked module asks of a call and what keeps the chain: ``_mark``.  Particular to this one: the
+    conv's weight (and bias, if it has one) is float32, the resize mode of the up-add form is ``"nearest"`` (bilinear keeps the chain), and the rule is
+    ``dwbn.dwconv_bn_train_routed``, on the output rows."""
     from . import lsmodels
     from .layers import ConvNorm
     from .recattn import LinearAttention, RecAttn2d
@@ -348,8 +349,7 @@ def use_fused_conv_norm_train(net, all_shapes=False):
             continue
         for cn in hosts:
             if isinstance(cn, ConvNorm):
-                n += 0 if cn.__dict__.get("_fused_conv_norm_train") else 1
-                cn._fused_conv_norm_train = "all" if all_shapes else "measured"
+                n += _mark(cn, "_fused_conv_norm_train", all_shapes)
     return n
 
 
@@ -360,14 +360,10 @@ def use_fused_mixer_norms_train(net, all_shapes=False):
     random stream, the same values), three launches forward and three backward each in place of the BatchNorm, the GELU, the mask multiply and the add.
     A marked stem runs each ``ConvNorm -> exact GELU`` pair on ``ops.BnGeluFn``; a ``ConvNorm`` followed by ``nn.Identity`` keeps the chain.  Marked:
     the ``channel_mixer`` of every ``MetaNeXtBlock`` / ``Downsample`` of this module and of ``lsmodels`` (the share-channel models' blocks among them) and
-    both ``RecNextStem``s.  The call sets a plain attribute on the ``nn.Sequential`` (on the stem module) and nothing else: state_dict keys, Parameters,
-    buffers and module objects are untouched, strict loads work in either order.  A marked module takes the operators when the tensor is a GPU tensor
-    of float32 / bfloat16 / float16 with more than one value a channel, the mixer is still ``[ConvNorm, exact GELU, ConvNorm]`` with the very layers it
-    was marked with, each norm is exactly ``nn.BatchNorm2d`` or ``HipBatchNorm2d`` in training mode, affine with float32 parameters, float32 running
-    buffers (or none) and a float momentum, and -- norm by norm -- the shape is one the routing rule keeps (``bnact.bn_act_routed``; ``all_shapes``
-    routes every shape the kernels take); that norm's ``num_batches_tracked`` is then bumped by one.  Everything else -- eval mode, frozen norms,
-    SyncBatchNorm, ``momentum=None``, 16-bit parameters, the ``replace_batchnorm``ed form, the inference-only ``_fused_mlp`` path, CPU -- keeps the chain
-    unchanged.  Opt-in: nothing calls it by default.  Returns the number of modules newly marked (0 on a second call)."""
+    both ``RecNextStem``s.  The mark, what a marked module asks of a call and what keeps the chain: ``_mark``.  Particular to this one: the attribute is
+    set on the ``nn.Sequential`` (on the stem module) and holds the very layers besides the mode (``bnact.mark``), the mixer must still be ``[ConvNorm,
+    exact GELU, ConvNorm]`` of those layers, unhooked, each norm decides for itself by ``bnact.bn_act_routed``, and the inference-only ``_fused_mlp``
+    path comes first."""
     from . import lsmodels
     n = 0
     for m in net.modules():

@@ -81,6 +81,11 @@ def _empty_nhwc(n, c, h, w, dtype, device):
     return torch.empty((n, h, w, c), dtype=dtype, device=device).permute(0, 3, 1, 2)
 
 
+def _empty_flat(numel, dtype, device):
+    """A 1-D scratch or gradient block; allocated here, as _empty_nhwc's outputs are, so that tests/guard.py sees what recnext_amd/_trainop.py asks for."""
+    return torch.empty(numel, dtype=dtype, device=device)
+
+
 def _check_bwd_args(fn, x, shapes=(), packs=(), others=()):
     """Extent checks of a backward entry, run before anything is allocated or launched: the C entry points see raw pointers only, so a tensor
     smaller than the extents derived from x would be read out of range on the device.  shapes: (name, tensor, expected shape | None = only x's

@@ -18,6 +18,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from ._trainop import gpu_tensor_ok
+from .batchnorm import bump, norm_fusable
 from .dwconv import DwConvFn as _DwConvFn
 from .dwconv import UpAddDwConvFn as _UpAddDwConvFn
 from .layers import ConvNorm
@@ -104,26 +106,23 @@ def _upadd_conv_norm_train(m, x, a, mode):
 def _conv_norm_fused_ok(m, x, stride, a):
     """Whether a depthwise ConvNorm that models.use_fused_conv_norm_train marked runs this call on ops.DwConvBnFn (the conditions of that function's
     docstring)."""
-    from .lsmodels import _norm_fusable
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in ops._DT):
+    if not gpu_tensor_ok(x):
         return False
     conv = m.conv
-    if conv.weight.dtype != torch.float32 or (conv.bias is not None and conv.bias.dtype != torch.float32) or not _norm_fusable(m.norm):
+    if conv.weight.dtype != torch.float32 or (conv.bias is not None and conv.bias.dtype != torch.float32) or not norm_fusable(m.norm):
         return False
     n, c, h, w = x.shape
     k = conv.weight.shape[-1]
     if conv.groups != c or conv.weight.shape[0] != c or conv.weight.shape[-2] != k:
         return False
-    if a is not None and not (torch.is_tensor(a) and a.is_cuda and a.dim() == 4 and a.dtype in ops._DT and a.shape[:2] == x.shape[:2]):
+    if a is not None and not (gpu_tensor_ok(a) and a.shape[:2] == x.shape[:2]):
         return False
     return ops.dwconv_bn_train_supported(n, h, w, c, k, stride, a is not None, x.dtype, measured_only=m.__dict__["_fused_conv_norm_train"] != "all")
 
 
 def _conv_norm_fused(m, x, a, stride):
     bn = m.norm
-    if bn.running_mean is not None and bn.num_batches_tracked is not None:
-        bn.num_batches_tracked.add_(1)
-    return ops.DwConvBnFn.apply(ops._nhwc(x), a, m.conv.weight, m.conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, stride, bn.momentum, bn.eps)
+    return ops.DwConvBnFn.apply(ops._nhwc(x), a, m.conv.weight, m.conv.bias, bn.weight, bn.bias, *bump(bn), stride, bn.momentum, bn.eps)
 
 
 def _folded(m):

@@ -3,14 +3,13 @@
 autograd node, and x the only saved tensor of the activation's size.  ``lsmodels._rep_train`` calls ``RepDwFn`` for the modules
 ``models.use_fused_rep_train`` marked; everything else keeps the operator chain.
 
-recnext_amd.ops exports the functions (``ops.repdw_train`` ...); they are written here because tests/test_guard_cpu.py asks a row in the case table of
-tests/test_guard_bands_gpu.py of every launching function whose source is in ops.py, and these entries' guard-band cases are in
-tests/test_repdw_gpu.py, which passes this module to tests/guard.py as one of ``modules=`` (as recnext_amd/batchnorm.py does): outputs, statistics,
-gradients and the workspace are allocated by this module's own ``torch.empty``.  A CPU tensor raises."""
+recnext_amd.ops exports the functions (``ops.repdw_train`` ...); why they are written here is said once, in recnext_amd/_trainop.py; their guard-band
+cases are in tests/test_repdw_gpu.py.  A CPU tensor raises."""
 import torch
 
 from . import _lib, ops
-from .batchnorm import _check_vec, _check_x, _dense_nhwc
+from ._trainop import (carve_f32, check_dw_weight, check_like, check_rows, check_running, check_vec, check_x, esize, grad_in, grads_out, ptr, rows_routed,
+                       supported, workspace)
 
 # The routing rule (DESIGN.md section 5.z2, profiles/r21_rep_train.txt): (C, element size of x) -> the rows R = N H W at which the operator's forward +
 # backward beat the operator chain by more than the chain's own spread at batch 128, in wall and in GPU time, in both jobs measured; from half the
@@ -21,14 +20,13 @@ ROUTED = {(c, es): rows for c, rows in ((128, (12544, 50176)), (256, (3136, 1254
 
 def repdw_train_routed(n, h, w, c, dtype):
     """Whether the routing rule keeps (N, H, W, C) of dtype on the fused operator: a rule on (R = N H W, C, element size) alone."""
-    lo, hi = ROUTED.get((int(c), 4 if dtype == torch.float32 else 2), (1, 0))
-    return lo <= int(n) * int(h) * int(w) <= hi
+    return rows_routed(ROUTED, (int(c), esize(dtype)), int(n) * int(h) * int(w))
 
 
 def repdw_train_supported(n, h, w, c, dtype, measured_only=False):
     """Whether the kernels take (N, H, W, C) of dtype (rcx_repdw_train_supported: fewer than 2^31 elements; R = 1 is refused by the functions, as torch
     refuses it) and, with measured_only, the routing rule keeps it (repdw_train_routed)."""
-    if dtype not in ops._DT or _lib.load().rcx_repdw_train_supported(int(n), int(h), int(w), int(c), ops._DT[dtype]) <= 0:
+    if dtype not in ops._DT or not supported("rcx_repdw_train_supported", n, h, w, c, ops._DT[dtype]):
         return False
     return not measured_only or repdw_train_routed(n, h, w, c, dtype)
 
@@ -36,21 +34,13 @@ def repdw_train_supported(n, h, w, c, dtype, measured_only=False):
 def _check_params(fn, x, vecs, w3, w1):
     c = x.shape[1]
     for name, t in vecs:
-        _check_vec(fn, t, c, x.device, name)
-    for name, t, shape in (("w3", w3, (c, 1, 3, 3)), ("w1", w1, (c, 1, 1, 1))):
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != x.device or not t.is_contiguous():
-            raise ValueError(f"{fn}: {name} must be a contiguous float32 {shape} tensor on {x.device}")
+        check_vec(fn, t, c, x.device, name)
+    check_dw_weight(fn, w3, c, x.device, "w3", 3)
+    check_dw_weight(fn, w1, c, x.device, "w1", 1)
     n, _, h, w = x.shape
-    if n * h * w == 1:
-        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+    check_rows(n * h * w, tuple(x.shape))
     if not repdw_train_supported(n, h, w, c, x.dtype):
         raise ValueError(f"{fn}: no kernel for N={n}, H={h}, W={w}, C={c}, {x.dtype} (repdw_train_supported)")
-
-
-def _workspace(x):
-    n, c, h, w = x.shape
-    nbytes = _lib.load().rcx_repdw_train_workspace_bytes(n, h, w, c, ops._DT[x.dtype])
-    return torch.empty(nbytes, dtype=torch.uint8, device=x.device), nbytes
 
 
 def repdw_train(x, w3, b3, gamma_a, beta_a, w1, b1, gamma_b, beta_b, running=None, momentum_a=0.1, eps_a=1e-5, momentum_b=0.1, eps_b=1e-5):
@@ -59,18 +49,13 @@ def repdw_train(x, w3, b3, gamma_a, beta_a, w1, b1, gamma_b, beta_b, running=Non
     (lk running_mean, lk running_var, sk running_mean, sk running_var), updated in place.  -> (r float32 like x, stats float32 (4, C): mean x, var x,
     mean u, 1 / sqrt(var u + eps_a), u = lk.conv(x)), which repdw_train_backward takes."""
     fn = "repdw_train"
-    _check_x(fn, x)
+    check_x(fn, x)
     n, c, h, w = x.shape
     _check_params(fn, x, (("b3", b3), ("gamma_a", gamma_a), ("beta_a", beta_a), ("b1", b1), ("gamma_b", gamma_b), ("beta_b", beta_b)), w3, w1)
-    if running is not None:
-        if len(running) != 4:
-            raise ValueError(f"{fn}: running is the four buffers (lk mean, lk var, sk mean, sk var) or None")
-        for i, t in enumerate(running):
-            _check_vec(fn, t, c, x.device, f"running[{i}]")
-    r = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2)
+    run = check_running(fn, running, c, x.device, ("lk running_mean", "lk running_var", "sk running_mean", "sk running_var"))
+    r = ops._empty_nhwc(n, c, h, w, torch.float32, x.device)
     stats = torch.empty((4, c), dtype=torch.float32, device=x.device)
-    ws, nbytes = _workspace(x)
-    run = [t.data_ptr() for t in running] if running is not None else [None] * 4
+    ws, nbytes = workspace("rcx_repdw_train_workspace_bytes", x.device, n, h, w, c, ops._DT[x.dtype])
     sp = stats.data_ptr()
     with ops._on(x.device):
         rc = _lib.load().rcx_repdw_train_fwd(x.data_ptr(), r.data_ptr(), w3.data_ptr(), b3.data_ptr(), gamma_a.data_ptr(), beta_a.data_ptr(), w1.data_ptr(),
@@ -88,27 +73,23 @@ def repdw_train_backward(x, g, w3, b3, gamma_a, w1, gamma_b, stats, eps_b=1e-5, 
     """Backward of repdw_train (rcx_repdw_train_bwd) from x and the forward's saved stats; g = dL/dr, float32, dense channels_last.
     -> (gx like x | None, grads | None), grads the float32 tuple GRADS: gw3 (C,1,3,3), gw1 (C,1,1,1), the rest (C); gb3 and gb1 are exact zeros."""
     fn = "repdw_train_backward"
-    _check_x(fn, x)
-    _check_x(fn, g, "g")
-    if g.shape != x.shape or g.dtype != torch.float32 or g.device != x.device:
-        raise ValueError(f"{fn}: g is {tuple(g.shape)} {g.dtype} on {g.device}, wanted float32 {tuple(x.shape)} on {x.device}")
+    check_x(fn, x)
+    check_like(fn, g, "g", x.shape, (torch.float32,), x.device)
     n, c, h, w = x.shape
     _check_params(fn, x, (("b3", b3), ("gamma_a", gamma_a), ("gamma_b", gamma_b)), w3, w1)
     if not torch.is_tensor(stats) or stats.dtype != torch.float32 or tuple(stats.shape) != (4, c) or stats.device != x.device or not stats.is_contiguous():
         raise ValueError(f"{fn}: stats must be the contiguous float32 (4, {c}) tensor repdw_train returned")
     if not (need_input_grad or need_param_grads):
         raise ValueError(f"{fn}: no gradient asked for")
-    gx = torch.empty((n, h, w, c), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2) if need_input_grad else None
+    gx = ops._empty_nhwc(n, c, h, w, x.dtype, x.device) if need_input_grad else None
     grads, gp = None, [None] * 8
     if need_param_grads:
-        buf = torch.empty(16 * c, dtype=torch.float32, device=x.device)
-        grads = (buf[:9 * c].view(c, 1, 3, 3),) + tuple(buf[(9 + i) * c:(10 + i) * c].view((c, 1, 1, 1) if i == 3 else (c,)) for i in range(7))
-        gp = [buf.data_ptr()] + [buf.data_ptr() + 4 * (9 + i) * c for i in range(7)]
-    ws, nbytes = _workspace(x)
+        grads, gp = carve_f32([(c, 1, 3, 3)] + [(c,)] * 3 + [(c, 1, 1, 1)] + [(c,)] * 3, x.device)        # GRADS: 16 C floats, one allocation
+    ws, nbytes = workspace("rcx_repdw_train_workspace_bytes", x.device, n, h, w, c, ops._DT[x.dtype])
     sp = stats.data_ptr()
     with ops._on(x.device):
         rc = _lib.load().rcx_repdw_train_bwd(x.data_ptr(), g.data_ptr(), w3.data_ptr(), b3.data_ptr(), gamma_a.data_ptr(), w1.data_ptr(), gamma_b.data_ptr(),
-                                             sp, sp + 4 * c, sp + 8 * c, sp + 12 * c, gx.data_ptr() if gx is not None else None, *gp, ws.data_ptr(), nbytes,
+                                             sp, sp + 4 * c, sp + 8 * c, sp + 12 * c, ptr(gx), *gp, ws.data_ptr(), nbytes,
                                              n, h, w, c, float(eps_b), ops._dt(x), ops._stream(x.device))
     _lib.check(rc, "rcx_repdw_train_bwd")
     return gx, grads
@@ -137,15 +118,7 @@ class RepDwFn(torch.autograd.Function):
         need_x, need_p = need[0], any(need[1:9])
         if not (need_x or need_p):
             return (None,) * 17
-        if g.dtype != torch.float32:
-            g = g.float()
-        if not _dense_nhwc(g):
-            g = ops._nhwc(g, "g")
-        gx, grads = repdw_train_backward(x, g, w3, b3, gamma_a, w1, gamma_b, stats, ctx.eps_b, need_input_grad=need_x, need_param_grads=need_p)
-        out = [gx] + [None] * 16
-        if grads is not None:
-            params = (w3, b3, gamma_a, None, w1, None, gamma_b, None)
-            for i, t in enumerate(grads):
-                if need[1 + i]:
-                    out[1 + i] = t if params[i] is None or params[i].dtype == torch.float32 else t.to(params[i].dtype)
-        return tuple(out)
+        gx, grads = repdw_train_backward(x, grad_in(g, torch.float32), w3, b3, gamma_a, w1, gamma_b, stats, ctx.eps_b, need_input_grad=need_x,
+                                         need_param_grads=need_p)
+        f32 = torch.float32                                    # beta_a, b1 and beta_b are not saved: float32, as repdw_train took them
+        return (gx, *grads_out(grads, (w3.dtype, b3.dtype, gamma_a.dtype, f32, w1.dtype, f32, gamma_b.dtype, f32), need[1:9]), *(None,) * 8)
